@@ -28,6 +28,11 @@ ranks), each phase bracketed by events recorded right before and right after the
 SMBPO.rollout() call (transitions written by one rollout / its
 time); sac.value = SAC grad-steps/s over the update phases. ms_per_step is the
 full rollout_and_update wall time (max over ranks).
+
+A plain run sets up, warms up, times --steps steps and prints the result line (with
+the rollout kernel's roofline fraction, which comes from the timed steps' own
+events). --full adds the untimed post-passes: sac.mlp_kernels / sac.comm, model_fit
+and cpu_baseline. --dump-outputs DIR writes what the last timed step computed.
 """
 import argparse
 import ctypes
@@ -333,6 +338,40 @@ def launch_ranks(n, argv):
     return rc
 
 
+DUMP_ROLLOUT_BYTES = 48 << 20     # the solver's parameters take ~4 MB more (64 MB in all)
+
+
+def dump_outputs(path, alg, rollout, do_sac):
+    """--dump-outputs: what a caller of the timed step holds after its last call, as
+    float32 / float64 <name>.npy files: the transitions of the last rollout
+    (rollout.<component>, the rows of SMBPO.rollout()'s result; a fixed seeded row
+    sample when they exceed DUMP_ROLLOUT_BYTES), the solver's state after the last
+    update_solver (solver.<state_dict key>, without the model ensemble, which the step
+    does not change) and that update's two critic losses."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    comp = rollout.get(as_dict=True)
+    n = len(rollout)
+    row_bytes = sum(4 * max(1, v[0].numel()) for v in comp.values()) if n else 0
+    if n * row_bytes > DUMP_ROLLOUT_BYTES:
+        keep = np.sort(np.random.RandomState(0).choice(n, DUMP_ROLLOUT_BYTES // row_bytes, replace=False))
+        arrs['rollout.rows'] = torch.from_numpy(keep)
+        keep = torch.from_numpy(keep).to(alg.device)
+        comp = {k: v[keep] for k, v in comp.items()}
+    for k, v in comp.items():
+        arrs['rollout.' + k] = v
+    if do_sac:
+        for k, v in alg.solver.state_dict().items():
+            if torch.is_tensor(v) and not k.startswith('model_ensemble.'):
+                arrs['solver.' + k] = v
+        arrs['loss.critic'] = torch.as_tensor(alg.recent_critic_losses[-1])
+        arrs['loss.constraint_critic'] = torch.as_tensor(alg.recent_cons_critic_losses[-1])
+    for k, v in arrs.items():
+        v = v.detach().cpu()
+        np.save(os.path.join(path, k + '.npy'), v.numpy().astype(np.float64 if v.dtype in (torch.float64, torch.int64)
+                                                                  else np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -346,15 +385,22 @@ def main():
     ap.add_argument('--global-batch', type=int, default=None,
                     help='divide this global batch over the ranks (config 5 does so by default)')
     ap.add_argument('--rollout-only', action='store_true')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--seed', type=int, default=0)
-    ap.add_argument('--no-fit', action='store_true', help='skip the model-fit post-pass')
+    ap.add_argument('--no-fit', action='store_true', help='with --full: skip the model-fit post-pass')
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend for N>1 (nccl = RCCL)')
     ap.add_argument('--fit-steps', type=int, default=None,
                     help="steps of the timed fit call (default: the config's model_steps, the length of "
                          "the reference's fit(steps=) call, src/smbpo.py:214-216)")
     ap.add_argument('--engine', type=int, default=0, help='rollout engine: 0 auto (fused horizon), 1 per-step launches')
     ap.add_argument('--elites', default=None, help='comma-separated elite members (traffic probes)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the untimed post-passes: per-kernel SAC MLP throughput '
+                         'and gradient-exchange time, the model-fit timing and the CPU baseline (a plain run '
+                         'only sets up, warms up, times the steps and prints the result line)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="write what the last timed step computed (the rollout's transitions, the solver's "
+                         'parameters and the last critic losses) as DIR/<name>.npy')
     args = ap.parse_args()
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -416,6 +462,8 @@ def main():
     # production noise: ops.rollout picks the fused engine (2) for H <= 128
     fused_engine = args.engine == 2 or (args.engine == 0 and H <= 128)
 
+    last = {}                       # the last step's rollout result (--dump-outputs)
+
     def one_step(tmr):
         if tmr is not None and fused_engine:
             # Fused engine: the library records tmr.events[0] immediately before the
@@ -432,6 +480,7 @@ def main():
                     alg.update_solver(update_actor=st % 2 == 0, update_multiplier=st % 5 == 0)
             dlib.check(dlib.lib().drpo_event_record(tmr.events[3], dlib.stream()), 'event_record')
             n_dev.add_(out._count)
+            last['rollout'] = out
             return None
         t0 = torch.cuda.Event(enable_timing=True)
         t1 = torch.cuda.Event(enable_timing=True)
@@ -444,6 +493,7 @@ def main():
                 alg.update_solver(update_actor=st % 2 == 0, update_multiplier=st % 5 == 0)
         t2.record()
         n_dev.add_(out._count)            # device-side transition count (no host sync)
+        last['rollout'] = out
         return (t0, t1, t2)
 
     for _ in range(args.warmup):
@@ -488,12 +538,15 @@ def main():
     else:
         wall, roll_s, sac_s, n_all, call_s = tot[0].item(), tot[1].item(), tot[2].item(), tot[3].item(), tot[4].item()
 
-    # post-pass (untimed): per-kernel-class MLP throughput of the SAC update from HIP
-    # events around every MLP launch (drpo_amd.sac_step.LaunchProfiler). Every rank
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, alg, last['rollout'], do_sac)
+
+    # post-pass (untimed, --full): per-kernel-class MLP throughput of the SAC update from
+    # HIP events around every MLP launch (drpo_amd.sac_step.LaunchProfiler). Every rank
     # runs it (the updates all-reduce gradients); rank 0 reports.
     sac_kernels = None
     sac_comm = None
-    if do_sac:
+    if do_sac and args.full:
         from drpo_amd.sac_step import LaunchProfiler
         from drpo_amd.distributed import CommLog
         eng = alg.solver.engine
@@ -515,7 +568,7 @@ def main():
     # fit(steps=K) of the reference's E x 256-row steps on the synthetic replay; under
     # torchrun the members are sharded over the ranks (distributed.MemberShard)
     fit_res = None
-    if not args.no_fit:
+    if args.full and not args.no_fit:
         m = alg.model_ensemble
         m.fit(alg.replay_buffer, steps=2)            # warm-up (workspaces, packing)
         torch.cuda.synchronize()
@@ -620,7 +673,7 @@ def main():
                 res['roofline']['traffic_source'] = os.path.relpath(prof, ROOT)
                 break
     res['lib_digest'] = _lib.build_digest()
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         res['cpu_baseline'] = cpu_baseline(cfgd, args.seed)
     print(json.dumps(res))
     if dist is not None:

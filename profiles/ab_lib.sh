@@ -8,7 +8,7 @@ N=${3:-2}
 mkdir -p $OUT
 export TMPDIR=/tmp
 for i in $(seq $N); do
-  timeout -k 10 300 python -u bench.py --no-cpu-baseline > $OUT/base_$i.json 2> $OUT/base_$i.err || exit 1
-  DRPO_LIB_OVERRIDE=$VAR timeout -k 10 300 python -u bench.py --no-cpu-baseline > $OUT/var_$i.json 2> $OUT/var_$i.err || exit 1
+  timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $OUT/base_$i.json 2> $OUT/base_$i.err || exit 1
+  DRPO_LIB_OVERRIDE=$VAR timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $OUT/var_$i.json 2> $OUT/var_$i.err || exit 1
 done
 python profiles/summ.py $OUT/base_*.json $OUT/var_*.json

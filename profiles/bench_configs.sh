@@ -13,6 +13,6 @@ for c in "$@"; do
   if [ "$c" = "2" ]; then EXTRA=""; fi
   STEPS=20
   if [ "$c" = "5" ]; then STEPS=5; fi
-  timeout -k 10 400 python -u bench.py --config $c --steps $STEPS --warmup 2 $EXTRA > $OUT/bench_c$c.json 2> $OUT/bench_c$c.err
+  timeout -k 10 400 python -u bench.py --full --config $c --steps $STEPS --warmup 2 $EXTRA > $OUT/bench_c$c.json 2> $OUT/bench_c$c.err
 done
 echo done

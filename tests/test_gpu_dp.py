@@ -101,7 +101,7 @@ def test_bench_two_ranks_gloo():
     port = _port()
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
            '127.0.0.1', '--master-port', str(port), os.path.join(os.path.dirname(HERE), 'bench.py'), '--gpus', '2',
-           '--backend', 'gloo', '--steps', '2', '--warmup', '1', '--fit-steps', '2', '--no-cpu-baseline']
+           '--backend', 'gloo', '--steps', '2', '--warmup', '1', '--full', '--fit-steps', '2', '--no-cpu-baseline']
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
@@ -117,7 +117,7 @@ def test_bench_gpus_flag_launches_ranks():
     ranks itself and prints rank 0's single line with n_gpus 2."""
     import json
     cmd = [sys.executable, os.path.join(os.path.dirname(HERE), 'bench.py'), '--gpus', '2', '--backend', 'gloo',
-           '--steps', '2', '--warmup', '1', '--fit-steps', '2', '--no-cpu-baseline']
+           '--steps', '2', '--warmup', '1', '--full', '--fit-steps', '2', '--no-cpu-baseline']
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
