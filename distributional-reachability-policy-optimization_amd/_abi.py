@@ -3,7 +3,8 @@ suite checks every declared symbol is exported and every prototype here exists i
 the header)."""
 import ctypes
 
-from ctypes import c_int, c_int64, c_uint64, c_float, c_double, c_size_t, c_void_p, c_char_p, POINTER
+from ctypes import (c_int, c_int32, c_int64, c_uint8, c_uint32, c_uint64, c_float, c_double, c_size_t, c_void_p,
+                    c_char_p, POINTER)
 
 P = c_void_p
 
@@ -25,8 +26,27 @@ class RolloutDesc(ctypes.Structure):
         ('vs', P), ('va', P), ('vs2', P), ('vr', P), ('vh', P), ('vd', P), ('vv', P),
         ('vptr', P), ('vcap', c_int64),
         ('workspace', P), ('rows_per_tile', c_int), ('step_events', POINTER(c_void_p)),
-        ('engine', c_int), ('eps_layout', c_int),
+        ('engine', c_int), ('eps_layout', c_int), ('env_program', P),
     ]
+
+
+ENV_PROGRAM = 4          # DRPO_ENV_PROGRAM
+PROG_AFFINE, PROG_BALLS = 0, 1
+PROG_MAX_ROWS = PROG_MAX_TERMS = PROG_MAX_CENTRES = PROG_MAX_BOX = 8
+
+
+class EnvProgramRow(ctypes.Structure):
+    """drpo_env_program_row_t"""
+    _fields_ = [('kind', c_uint8), ('n', c_uint8), ('nd', c_uint8), ('pad_', c_uint8), ('dims', c_uint8 * 8),
+                ('pad2_', c_uint32), ('k0', c_double), ('v', c_double * 24)]
+
+
+class EnvProgram(ctypes.Structure):
+    """drpo_env_program_t (uploaded to device memory)"""
+    _fields_ = [('C', c_int32), ('done_on_violation', c_uint8), ('box_n', c_uint8), ('ball_nd', c_uint8),
+                ('pad_', c_uint8), ('box_dims', c_uint8 * 8), ('ball_dims', c_uint8 * 4), ('pad2_', c_uint32),
+                ('box_lo', c_double * 8), ('box_hi', c_double * 8), ('ball_centre', c_double * 3),
+                ('ball_radius', c_double), ('rows', EnvProgramRow * 8)]
 
 
 class PackItem(ctypes.Structure):
@@ -74,6 +94,8 @@ PROTOTYPES = {
     'drpo_rollout_count_offset': (c_size_t, [c_int, c_int, c_int]),
     'drpo_rollout': (c_int, [POINTER(RolloutDesc), P]),
     'drpo_env_constraints': (c_int, [c_int, c_int, c_int, c_double, c_double, P, c_int64, c_int, P, P, P, P]),
+    'drpo_env_constraints_program': (c_int, [P, c_int, P, c_int64, c_int, P, P, P, P]),
+    'drpo_env_program_check': (c_int, [POINTER(EnvProgram), c_int]),
     'drpo_shield_mix': (c_int, [P, P, c_int64, c_int, c_int, P, P]),
     'drpo_shield_select': (c_int, [P, c_int, c_int64, c_int, c_int, c_int, c_float, P, P, P, P, P]),
     'drpo_sample_without_replacement': (c_int, [P, c_int64, c_int64, c_uint64, c_uint64, P]),

@@ -91,4 +91,76 @@ __device__ inline void env_constraints_row(const EnvParams& ep, const float* s, 
   }
 }
 
+// ---------------------------------------------------------------------------
+// Constraint programs (drpo_env_program_t): the interpreter of env id 4.
+// The program is wave-uniform data in device memory that no kernel writes, so it is
+// read through a constant-address-space pointer: every read below has a uniform
+// address and compiles to a scalar load (byte arrays are read as whole words).
+// Double arithmetic without contraction (__dmul_rn / __dadd_rn), so the result is
+// the one ConstraintProgram.evaluate_numpy computes.
+// ---------------------------------------------------------------------------
+typedef const __attribute__((address_space(4))) drpo_env_program_t* EnvProgK;
+typedef const __attribute__((address_space(4))) drpo_env_program_row_t* EnvProgRowK;
+typedef const __attribute__((address_space(4))) uint8_t* EnvProgBytesK;
+typedef const __attribute__((address_space(4))) uint32_t* EnvProgWordsK;
+typedef const __attribute__((address_space(4))) double* EnvProgRealsK;
+
+__device__ __forceinline__ EnvProgK env_program_ptr(const void* dev_prog) {
+  return (EnvProgK)(uintptr_t)dev_prog;
+}
+
+// byte k of a 4-byte aligned byte array
+__device__ __forceinline__ int env_prog_u8(EnvProgBytesK a, int k) {
+  return (int)((((EnvProgWordsK)a)[k >> 2] >> (8 * (k & 3))) & 0xffu);
+}
+
+// || s[dims[0..nd)] - c[0..nd) ||_2, nd = 2 | 3
+__device__ __forceinline__ double env_prog_dist(const float* s, EnvProgBytesK dims, EnvProgRealsK c, int nd) {
+  const double d0 = __dsub_rn((double)s[env_prog_u8(dims, 0)], c[0]);
+  const double d1 = __dsub_rn((double)s[env_prog_u8(dims, 1)], c[1]);
+  double q = __dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1));
+  if (nd == 3) {
+    const double d2 = __dsub_rn((double)s[env_prog_u8(dims, 2)], c[2]);
+    q = __dadd_rn(q, __dmul_rn(d2, d2));
+  }
+  return sqrt(q);
+}
+
+// Same contract as env_constraints_row: s is one state row, writes done, violation,
+// h[prog->C]. The program was checked on the host (drpo_env_program_check) before
+// its upload: every index is < S and every count within its array.
+__device__ inline void env_program_row(EnvProgK prog, const float* s, bool& done, bool& viol, float* h) {
+  const int C = prog->C;
+  bool v = false;
+#pragma unroll
+  for (int c = 0; c < DRPO_PROG_MAX_ROWS; ++c) {
+    if (c >= C) break;
+    EnvProgRowK row = &prog->rows[c];
+    const uint32_t head = *(EnvProgWordsK)row;   // kind | n << 8 | nd << 16
+    const int kind = head & 0xff, n = (head >> 8) & 0xff, nd = (head >> 16) & 0xff;
+    double hv;
+    if (kind == DRPO_PROG_AFFINE) {
+      hv = __dmul_rn(row->v[0], (double)s[env_prog_u8(row->dims, 0)]);
+      for (int k = 1; k < n; ++k) hv = __dadd_rn(hv, __dmul_rn(row->v[k], (double)s[env_prog_u8(row->dims, k)]));
+      hv = __dadd_rn(hv, row->k0);
+    } else {
+      double md = __longlong_as_double(0x7ff0000000000000LL);   // +inf
+      for (int j = 0; j < n; ++j) md = fmin(env_prog_dist(s, row->dims, row->v + j * nd, nd), md);
+      hv = __dsub_rn(row->k0, md);
+    }
+    v = v || (hv > 0.0);
+    h[c] = (float)hv;
+  }
+  viol = v;
+  const uint32_t rule = ((EnvProgWordsK)prog)[1];   // done_on_violation | box_n << 8 | ball_nd << 16
+  const int box_n = (rule >> 8) & 0xff, ball_nd = (rule >> 16) & 0xff;
+  bool dn = (rule & 0xff) != 0 && v;
+  for (int k = 0; k < box_n; ++k) {
+    const double x = (double)s[env_prog_u8(prog->box_dims, k)];
+    dn = dn || (x < prog->box_lo[k]) || (x > prog->box_hi[k]);
+  }
+  if (ball_nd) dn = dn || (env_prog_dist(s, prog->ball_dims, prog->ball_centre, ball_nd) <= prog->ball_radius);
+  done = dn;
+}
+
 }  // namespace drpo

@@ -91,6 +91,8 @@ struct RolloutStepArgs {
   int* inv;
   // LDS strides
   int ldx, ldh, ldm, lds;
+  // env id 4: the constraint program (device memory; read by the PG instantiations only)
+  const void* env_prog;
 };
 
 __device__ __forceinline__ uint32_t prp_round(uint32_t r, uint32_t k) {
@@ -124,7 +126,10 @@ __device__ inline int64_t prp_index(uint64_t i, uint64_t N, int hb, const uint32
   return (int64_t)(x % N);   // unreachable in practice (expected walk < 4)
 }
 
-template <int RB, int NW>
+// PG: the constraint phase runs the program interpreter (env id 4) instead of the
+// built-in functions: an instantiation of its own, so the built-in environments'
+// kernels keep their code and registers
+template <int RB, int NW, bool PG = false>
 __global__ __launch_bounds__(NW * 64) void rollout_step_kernel(RolloutStepArgs p) {
   constexpr int ROWS = RB * 16;
   constexpr int NT = NW * 64;                   // 2 waves per SIMD at NW = 8
@@ -350,7 +355,8 @@ __global__ __launch_bounds__(NW * 64) void rollout_step_kernel(RolloutStepArgs p
     if (tid < rows) {
       bool dn, vl;
       float hh[8];
-      env_constraints_row(p.env, xin + tid * p.ldx, dn, vl, hh);
+      if constexpr (PG) env_program_row(env_program_ptr(p.env_prog), xin + tid * p.ldx, dn, vl, hh);
+      else env_constraints_row(p.env, xin + tid * p.ldx, dn, vl, hh);
       for (int c = 0; c < C; ++c) hval[tid * 8 + c] = hh[c];
       flags[tid] = (dn ? 1 : 0) | (vl ? 2 : 0);
       alive_r = !dn;
@@ -467,6 +473,9 @@ struct PersistArgs {
   const int64_t* vptr_in;
   int64_t* base_slot;
   int members[PERSIST_MAX_H];
+  // env id 4: the constraint program (device memory; read by the PG instantiations only).
+  // Last, so that every other field keeps its kernarg offset.
+  const void* env_prog;
 };
 
 typedef const __attribute__((address_space(4))) PersistArgs* PersistArgsK;   // scalar (constant) loads
@@ -699,7 +708,10 @@ constexpr int PERSIST_L2_LDS = 3;
 // Hm = 200; 0: the general path), so each kernel holds registers for one path only
 // (spilled VGPRs 53 -> 33 / 1 -> 0 against one kernel with a run-time path choice,
 // profiles/r03/pm_ab)
-template <int RB, int NW, bool LW, int PM>
+// PG: the constraint phase (on the step's critical path) runs the program interpreter
+// (env id 4): instantiations of their own, the built-in environments' kernels keep
+// their code, registers and LDS. The program needs no LDS (scalar loads).
+template <int RB, int NW, bool LW, int PM, bool PG = false>
 __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p) {
   constexpr int ROWS = RB * 16;
   constexpr int NT = NW * 64;
@@ -957,7 +969,14 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
       bool in_r = false, dn = false, vl = false;
       if (tid < ROWS && alive_cur[tid]) {
         float hh[8];
-        env_constraints_row(p.env, xin + tid * ldx, dn, vl, hh);
+        if constexpr (PG) {
+          // opaque per step: the program's (loop-invariant) scalar loads stay in the step
+          const void* prog = PARG(env_prog);
+          asm volatile("" : "+s"(prog));
+          env_program_row(env_program_ptr(prog), xin + tid * ldx, dn, vl, hh);
+        } else {
+          env_constraints_row(p.env, xin + tid * ldx, dn, vl, hh);
+        }
         for (int c = 0; c < C; ++c) PARG(st_h)[(sb + tid) * C + c] = hh[c];
         PARG(st_r)[sb + tid] = rew[tid];
         PARG(st_dv)[sb + tid] = (uint8_t)((dn ? 1 : 0) | (vl ? 2 : 0));
@@ -1306,6 +1325,8 @@ static int rollout_fused(const drpo_rollout_desc_t* d, int rpt, int64_t rlen, hi
   a.ldm = round_up(S1, 16) + 4;
   a.lds = round_up(S, 4);
   for (int t = 0; t < H; ++t) a.members[t] = d->members[t];
+  const bool pg = d->env_id == DRPO_ENV_PROGRAM;
+  a.env_prog = pg ? d->env_program : nullptr;
 
   // 8-wave workgroups (16 waves measured 3.5 % slower at config 2, profiles/r02/rollout_ab)
   const size_t lds_bytes = persist_lds_bytes(S, A, d->Ha, d->Hm, rpt, 8);
@@ -1320,7 +1341,18 @@ static int rollout_fused(const drpo_rollout_desc_t* d, int rpt, int64_t rlen, hi
     a.base_slot = off + H + 1;
   }
   if (d->step_events) hipEventRecord((hipEvent_t)d->step_events[0], stream);
-  if (rpt == 32) {
+  if (pg) {
+    if (rpt == 32) {
+      if (paired) rollout_persist_kernel<2, 8, false, 1, true><<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
+      else rollout_persist_kernel<2, 8, false, 0, true><<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
+    } else if (lw) {
+      if (paired) rollout_persist_kernel<1, 8, true, 1, true><<<a.ntiles, 8 * 64, lds_bytes + lw_bytes, stream>>>(a);
+      else rollout_persist_kernel<1, 8, true, 0, true><<<a.ntiles, 8 * 64, lds_bytes + lw_bytes, stream>>>(a);
+    } else {
+      if (paired) rollout_persist_kernel<1, 8, false, 1, true><<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
+      else rollout_persist_kernel<1, 8, false, 0, true><<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
+    }
+  } else if (rpt == 32) {
     if (paired) rollout_persist_kernel<2, 8, false, 1><<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
     else rollout_persist_kernel<2, 8, false, 0><<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
   } else if (lw) {
@@ -1371,8 +1403,16 @@ DRPO_API int drpo_rollout(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
   DRPO_REQUIRE(d->S >= 1 && d->S <= 64 && d->A >= 1 && d->A <= 8, "drpo_rollout: S=%d A=%d out of range", d->S, d->A);
   DRPO_REQUIRE(d->Ha >= 1 && d->Ha <= 256 && d->Hm >= 1 && d->Hm <= 256, "drpo_rollout: hidden dims must be <= 256");
   DRPO_REQUIRE(d->S + 1 <= 64, "drpo_rollout: state_dim+1 must be <= 64");
-  DRPO_REQUIRE(d->C >= 1 && d->C <= 8 && d->C == env_con_dim(d->env_id, d->tracking_n_surr),
-               "drpo_rollout: con_dim %d does not match env %d", d->C, d->env_id);
+  DRPO_REQUIRE(d->env_id >= 0 && d->env_id <= DRPO_ENV_PROGRAM, "drpo_rollout: unknown env id %d", d->env_id);
+  if (d->env_id == DRPO_ENV_PROGRAM)
+    // the program's row count lives in device memory: the caller states it (C) and has
+    // checked the program with drpo_env_program_check before the upload
+    DRPO_REQUIRE(d->C >= 1 && d->C <= DRPO_PROG_MAX_ROWS && d->env_program,
+                 "drpo_rollout: env id %d needs 1 <= con_dim (%d) <= %d and a device program (env_program)", d->env_id,
+                 d->C, (int)DRPO_PROG_MAX_ROWS);
+  else
+    DRPO_REQUIRE(d->C >= 1 && d->C <= 8 && d->C == env_con_dim(d->env_id, d->tracking_n_surr),
+                 "drpo_rollout: con_dim %d does not match env %d", d->C, d->env_id);
   DRPO_REQUIRE(d->B >= 1 && d->H >= 1 && (int64_t)d->B * d->H <= d->vcap,
                "drpo_rollout: B*H=%lld exceeds buffer capacity %lld", (long long)d->B * d->H, (long long)d->vcap);
   DRPO_REQUIRE(d->workspace && d->vptr && d->replay_states, "drpo_rollout: null pointer");
@@ -1420,6 +1460,8 @@ DRPO_API int drpo_rollout(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
   a.ldh = lds_ld(d->Ha > d->Hm ? d->Ha : d->Hm);
   a.ldm = round_up(S1, 16) + 4;
   a.lds = round_up(S, 4);
+  const bool pg = d->env_id == DRPO_ENV_PROGRAM;
+  a.env_prog = pg ? d->env_program : nullptr;
 
   const int tiles = (d->B + rpt - 1) / rpt;
   constexpr int NW = 8;
@@ -1449,7 +1491,10 @@ DRPO_API int drpo_rollout(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
     a.eps_a = d->eps_a ? d->eps_a + (size_t)t * d->B * A : nullptr;
     a.eps_m = d->eps_m ? d->eps_m + (size_t)t * d->B * S1 : nullptr;
     if (d->step_events) hipEventRecord((hipEvent_t)d->step_events[2 * t], stream);
-    if (rpt == 32)
+    if (pg) {
+      if (rpt == 32) rollout_step_kernel<2, NW, true><<<tiles, NW * 64, lds_bytes, stream>>>(a);
+      else rollout_step_kernel<1, NW, true><<<tiles, NW * 64, lds_bytes, stream>>>(a);
+    } else if (rpt == 32)
       rollout_step_kernel<2, NW><<<tiles, NW * 64, lds_bytes, stream>>>(a);
     else
       rollout_step_kernel<1, NW><<<tiles, NW * 64, lds_bytes, stream>>>(a);
@@ -1479,12 +1524,80 @@ DRPO_API int drpo_env_constraints(int env_id, int tracking_surr_start, int track
                                   double env_thr1, const float* states, int64_t n, int S, uint8_t* done,
                                   uint8_t* violation, float* h, drpo_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  DRPO_REQUIRE(env_id != DRPO_ENV_PROGRAM,
+               "drpo_env_constraints: env id %d is a constraint program: call drpo_env_constraints_program", env_id);
   DRPO_REQUIRE(env_id >= 0 && env_id <= 3, "drpo_env_constraints: unknown env id %d", env_id);
   if (n == 0) return DRPO_OK;
   EnvParams ep{env_id, tracking_surr_start, tracking_n_surr, env_thr0, env_thr1};
   const int C = env_con_dim(env_id, tracking_n_surr);
   env_constraints_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(ep, states, n, S, C, done, violation, h);
   DRPO_LAUNCH_CHECK("env_constraints");
+  return DRPO_OK;
+}
+
+// The same for a constraint program: one thread per row.
+__global__ void env_program_kernel(const void* prog, const float* s, int64_t n, int S, int C, uint8_t* done,
+                                   uint8_t* viol, float* h) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  bool dn, vl;
+  float hh[8];
+  env_program_row(env_program_ptr(prog), s + i * S, dn, vl, hh);
+  if (done) done[i] = dn;
+  if (viol) viol[i] = vl;
+  if (h)
+    for (int c = 0; c < C; ++c) h[i * C + c] = hh[c];
+}
+
+DRPO_API int drpo_env_constraints_program(const drpo_env_program_t* dev_prog, int C, const float* states, int64_t n,
+                                          int S, uint8_t* done, uint8_t* violation, float* h, drpo_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  DRPO_REQUIRE(dev_prog && C >= 1 && C <= DRPO_PROG_MAX_ROWS,
+               "drpo_env_constraints_program: needs a device program and 1 <= C (%d) <= %d", C, (int)DRPO_PROG_MAX_ROWS);
+  DRPO_REQUIRE(S >= 1 && S <= 256 && n >= 0, "drpo_env_constraints_program: S=%d n=%lld", S, (long long)n);
+  if (n == 0) return DRPO_OK;
+  DRPO_REQUIRE(states, "drpo_env_constraints_program: null states");
+  env_program_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(dev_prog, states, n, S, C, done, violation, h);
+  DRPO_LAUNCH_CHECK("env_program");
+  return DRPO_OK;
+}
+
+// Host-only validation of a program in host memory (no device needed).
+DRPO_API int drpo_env_program_check(const drpo_env_program_t* q, int S) {
+  DRPO_REQUIRE(q, "drpo_env_program_check: null program");
+  DRPO_REQUIRE(S >= 1 && S <= 256, "drpo_env_program_check: state dim %d out of range (indices are bytes)", S);
+  DRPO_REQUIRE(q->C >= 1 && q->C <= DRPO_PROG_MAX_ROWS, "drpo_env_program_check: %d constraint rows (1..%d)", (int)q->C,
+               (int)DRPO_PROG_MAX_ROWS);
+  for (int c = 0; c < q->C; ++c) {
+    const drpo_env_program_row_t& r = q->rows[c];
+    DRPO_REQUIRE(r.kind == DRPO_PROG_AFFINE || r.kind == DRPO_PROG_BALLS, "drpo_env_program_check: row %d has unknown kind %d",
+                 c, (int)r.kind);
+    int nidx;
+    if (r.kind == DRPO_PROG_AFFINE) {
+      DRPO_REQUIRE(r.n >= 1 && r.n <= DRPO_PROG_MAX_TERMS, "drpo_env_program_check: affine row %d has %d terms (1..%d)", c,
+                   (int)r.n, (int)DRPO_PROG_MAX_TERMS);
+      nidx = r.n;
+    } else {
+      DRPO_REQUIRE(r.n >= 1 && r.n <= DRPO_PROG_MAX_CENTRES, "drpo_env_program_check: balls row %d has %d centres (1..%d)",
+                   c, (int)r.n, (int)DRPO_PROG_MAX_CENTRES);
+      DRPO_REQUIRE(r.nd == 2 || r.nd == 3, "drpo_env_program_check: balls row %d has %d dims (2 or 3)", c, (int)r.nd);
+      nidx = r.nd;
+    }
+    for (int k = 0; k < nidx; ++k)
+      DRPO_REQUIRE(r.dims[k] < S, "drpo_env_program_check: row %d reads state index %d >= state dim %d", c, (int)r.dims[k], S);
+  }
+  DRPO_REQUIRE(q->box_n <= DRPO_PROG_MAX_BOX, "drpo_env_program_check: done box has %d dims (max %d)", (int)q->box_n,
+               (int)DRPO_PROG_MAX_BOX);
+  for (int k = 0; k < q->box_n; ++k)
+    DRPO_REQUIRE(q->box_dims[k] < S, "drpo_env_program_check: done box reads state index %d >= state dim %d",
+                 (int)q->box_dims[k], S);
+  DRPO_REQUIRE(q->ball_nd == 0 || q->ball_nd == 2 || q->ball_nd == 3, "drpo_env_program_check: done ball has %d dims (2 or 3)",
+               (int)q->ball_nd);
+  for (int k = 0; k < q->ball_nd; ++k)
+    DRPO_REQUIRE(q->ball_dims[k] < S, "drpo_env_program_check: done ball reads state index %d >= state dim %d",
+                 (int)q->ball_dims[k], S);
+  DRPO_REQUIRE(q->done_on_violation <= 1, "drpo_env_program_check: done_on_violation %d", (int)q->done_on_violation);
+  DRPO_REQUIRE(q->done_on_violation || q->box_n || q->ball_nd, "drpo_env_program_check: empty done rule");
   return DRPO_OK;
 }
 

@@ -103,6 +103,9 @@ def _rollout_static(alg, policy, B, H):
     d.S, d.A, d.C, d.Ha, d.Hm, d.B, d.H = S, A, C, policy.spec.dims[1], model.hidden_dim, B, H
     d.env_id, d.tracking_surr_start, d.tracking_n_surr = ep['env_id'], ep['tracking_surr_start'], ep['tracking_n_surr']
     d.env_thr0, d.env_thr1 = ep['thr0'], ep['thr1']
+    # constraint program (env id 4): checked against S and uploaded once, cached on the program
+    prog = ep['program'].device(alg.device, S) if 'program' in ep else None
+    d.env_program = 0 if prog is None else prog.data_ptr()
     (d.aW1, d.ab1), (d.aW2, d.ab2), (d.aW3, d.ab3) = [(W.data_ptr(), b.data_ptr()) for W, b in pa]
     (d.mW1, d.mb1), (d.mW2, d.mb2) = [(W.data_ptr(), b.data_ptr()) for W, b in trunk]
     (d.dW1, d.db1), (d.dW2, d.db2) = [(W.data_ptr(), b.data_ptr()) for W, b in diff]
@@ -120,7 +123,7 @@ def _rollout_static(alg, policy, B, H):
     d.members = members
     off = L.drpo_rollout_count_offset(B, S, H)
     count = ws[off:off + 8].view(torch.int64)[0]
-    hit = cache[key] = (d, members, count)
+    hit = cache[key] = (d, members, count, prog)   # prog: keeps the uploaded program alive
     return hit
 
 
@@ -170,7 +173,7 @@ def rollout(alg, policy, initial_states, noise, timer=None, eps_layout=0):
     start_ptr = vb.pointer if vb._host_ptr is not None else None
     policy.group.ensure_packed()
     model.group.ensure_packed()
-    d, marr, count = _rollout_static(alg, policy, B, H)
+    d, marr, count = _rollout_static(alg, policy, B, H)[:3]
     marr[:] = members
     d.replay_states, d.replay_ptr, d.replay_cap = src.data_ptr(), src_ptr, src_cap
     d.init_idx = 0 if init_idx is None else init_idx.data_ptr()
@@ -273,6 +276,13 @@ def env_constraints(env_params, states):
     done = torch.empty(n, dtype=torch.bool, device=states.device)
     viol = torch.empty(n, dtype=torch.bool, device=states.device)
     h = torch.empty(n, C, dtype=torch.float32, device=states.device)
+    if 'program' in env_params:
+        # a user-defined env's constraint program (env id 4): checked against S on its upload
+        prog = env_params['program'].device(states.device, S)
+        _lib.check(L.drpo_env_constraints_program(_lib.ptr(prog), C, _lib.ptr(states), n, S, _lib.ptr(done),
+                                                  _lib.ptr(viol), _lib.ptr(h), _lib.stream()),
+                   'env_constraints_program')
+        return done, viol, (h[:, 0] if C == 1 else h)
     _lib.check(L.drpo_env_constraints(env_params['env_id'], env_params['tracking_surr_start'],
                                       env_params['tracking_n_surr'], env_params['thr0'],
                                       env_params['thr1'], _lib.ptr(states), n, S, _lib.ptr(done),

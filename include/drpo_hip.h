@@ -35,7 +35,54 @@ enum { DRPO_OK = 0, DRPO_EINVAL = 1, DRPO_EHIP = 2, DRPO_EUNSUPPORTED = 3 };
 enum { DRPO_ACT_NONE = 0, DRPO_ACT_RELU = 1, DRPO_ACT_SILU = 2, DRPO_ACT_TANH = 3 };
 
 /* device environment ids for the batched constraint functions (src/smbpo.py:63-65) */
-enum { DRPO_ENV_POINT_ROBOT = 0, DRPO_ENV_QUADROTOR = 1, DRPO_ENV_CARTPOLE = 2, DRPO_ENV_TRACKING = 3 };
+enum { DRPO_ENV_POINT_ROBOT = 0, DRPO_ENV_QUADROTOR = 1, DRPO_ENV_CARTPOLE = 2, DRPO_ENV_TRACKING = 3,
+       DRPO_ENV_PROGRAM = 4 /* constraint functions described by a drpo_env_program_t */ };
+
+/* ---------------------------------------------------------------- constraint programs
+ * A declarative description of an environment's check_done / check_violation /
+ * get_constraint_values (src/smbpo.py:63-65) for environments the library has no
+ * built-in id for: C constraint rows, each affine (the reference's LinearConstraint
+ * h = A x - b, src/env/poles/constraints.py:159-247) or the distance to the nearest of
+ * a few balls (hazard discs), and a done rule. It is evaluated by an interpreter in
+ * the rollout kernels' constraint phase. States are float32 promoted to double; every
+ * constant is a double, all arithmetic and comparisons are in double (no fused
+ * multiply-add), h is rounded to float32 on output AFTER the violation test h > 0.
+ * Plain data, no pointers; every byte array is 4-byte aligned (the kernels read them
+ * as whole words).                                                              */
+enum { DRPO_PROG_AFFINE = 0, DRPO_PROG_BALLS = 1 };
+enum { DRPO_PROG_MAX_ROWS = 8, DRPO_PROG_MAX_TERMS = 8, DRPO_PROG_MAX_CENTRES = 8, DRPO_PROG_MAX_BOX = 8 };
+
+typedef struct {
+  uint8_t kind;        /* DRPO_PROG_AFFINE: h = sum_k v[k] * s[dims[k]] + k0 (terms added left to right);
+                          DRPO_PROG_BALLS:  h = k0 - min_j || s[dims] - v[j*nd .. j*nd+nd) ||_2 */
+  uint8_t n;           /* affine: terms, 1..8; balls: centres, 1..8 */
+  uint8_t nd;          /* balls: dims, 2 or 3 (affine: 0) */
+  uint8_t pad_;
+  uint8_t dims[8];     /* affine: the state index of each term; balls: the nd state indices */
+  uint32_t pad2_;
+  double k0;           /* affine: bias; balls: radius */
+  double v[24];        /* affine: coefficients [n]; balls: centres [n][nd] */
+} drpo_env_program_row_t;
+
+typedef struct {
+  int32_t C;                   /* constraint rows, 1..8 */
+  uint8_t done_on_violation;   /* done |= any(h > 0) */
+  uint8_t box_n;               /* done |= s[box_dims[k]] < box_lo[k] || s[box_dims[k]] > box_hi[k], k < box_n <= 8 */
+  uint8_t ball_nd;             /* 0: none; 2 | 3: done |= || s[ball_dims] - ball_centre ||_2 <= ball_radius */
+  uint8_t pad_;
+  uint8_t box_dims[8];
+  uint8_t ball_dims[4];
+  uint32_t pad2_;
+  double box_lo[8], box_hi[8];
+  double ball_centre[3], ball_radius;
+  drpo_env_program_row_t rows[8];
+} drpo_env_program_t;
+
+/* Host-only check of a program (in HOST memory) against a state dimension S: kinds,
+ * counts, and every state index < S. The ONLY place a program can be validated: once
+ * uploaded it is device memory to the library, and a bad index would be an
+ * out-of-bounds read in the kernel. DRPO_EINVAL with a message otherwise. */
+int drpo_env_program_check(const drpo_env_program_t* host_prog, int S);
 
 /* ---------------------------------------------------------------- library */
 int drpo_version(void);
@@ -87,6 +134,9 @@ typedef struct {
   int engine;                    /* 0 auto, 1 one launch per horizon step, 2 fused horizon (persistent per tile) */
   int eps_layout;                /* eps_a/eps_m rows: 0 compacted per step (reference draw order; engine 1),
                                     1 original batch row (row i of step t = trajectory i; engine 2) */
+  const void* env_program;       /* env_id == DRPO_ENV_PROGRAM: a drpo_env_program_t in DEVICE memory (caller-
+                                    owned, checked with drpo_env_program_check before its upload, not written
+                                    while a rollout runs), C = its row count; unused otherwise */
 } drpo_rollout_desc_t;
 
 size_t drpo_rollout_workspace_size(int B, int S, int H);
@@ -98,6 +148,10 @@ int drpo_rollout(const drpo_rollout_desc_t* d /* host */, drpo_stream_t stream);
 int drpo_env_constraints(int env_id, int tracking_surr_start, int tracking_n_surr, double env_thr0,
                          double env_thr1, const float* states, int64_t n, int S, uint8_t* done,
                          uint8_t* violation, float* h, drpo_stream_t stream);
+/* the same for a constraint program (device memory, C = its row count); drpo_env_constraints
+ * refuses DRPO_ENV_PROGRAM */
+int drpo_env_constraints_program(const drpo_env_program_t* dev_prog, int C, const float* states, int64_t n, int S,
+                                 uint8_t* done, uint8_t* violation, float* h, drpo_stream_t stream);
 
 /* ---------------------------------------------------------------- safety shields
  * Real-env step shield (SMBPO.step_generator, src/smbpo.py:127-136) and the
