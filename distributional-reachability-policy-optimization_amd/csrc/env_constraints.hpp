@@ -163,4 +163,13 @@ __device__ inline void env_program_row(EnvProgK prog, const float* s, bool& done
   done = dn;
 }
 
+// One state row through the built-in functions of env.id, or (PG) through the program:
+// the one place the rollout engines and the stand-alone kernel make that choice.
+template <bool PG>
+__device__ __forceinline__ void constraint_row(const EnvParams& env, const void* prog, const float* s, bool& done,
+                                               bool& viol, float* h) {
+  if constexpr (PG) env_program_row(env_program_ptr(prog), s, done, viol, h);
+  else env_constraints_row(env, s, done, viol, h);
+}
+
 }  // namespace drpo

@@ -1,21 +1,31 @@
-// Fused imagined-rollout step (SMBPO.rollout, src/smbpo.py:229-249).
+// Imagined model rollouts (SMBPO.rollout, src/smbpo.py:229-249): two engines behind
+// drpo_rollout, and the replay sampler they share.
 //
-// One launch of rollout_step_kernel processes one horizon step for every alive
-// row: each 512-thread workgroup (8 wave64s, 2 per SIMD) owns a 16- or 32-row tile and keeps all of its
-// activations in LDS while it runs
+// Both engines give each 512-thread workgroup (8 wave64s, 2 per SIMD) a 16- or 32-row
+// tile whose activations stay in LDS while it runs
 //   actor MLP S->H->H->2A (ReLU)  +  squashed-Gaussian sample   (src/policy.py:89-97)
 //   elite member MLP trunk/diff/log-var heads (SiLU) + log-var clamp + Gaussian
 //   sample                                                      (src/dynamics.py:112-122,198-203)
-//   env constraint functions                                    (env_constraints.hpp)
-//   the 7-component row write into the circular virtual buffer  (src/sampling.py:128-145)
-// and emits per-tile alive counts plus an in-tile compaction map. The next step's
-// launch performs the order-preserving `next_states[~dones]` compaction
-// (src/smbpo.py:243-246) itself: each workgroup scans the previous step's tile
-// counts and binary-searches the source row of each of its rows, so a horizon
-// step is ONE launch. Row counts and buffer offsets live on the device, so a whole
-// rollout needs no host synchronisation.
-#include <stdarg.h>
-#include <stdio.h>
+//   env constraint functions or a constraint program            (env_constraints.hpp)
+// and both write the 7-component rows into the circular virtual buffer
+// (src/sampling.py:128-145) in the reference's order: step-major, surviving rows in
+// batch order. Row counts and buffer offsets live on the device, so a whole rollout
+// needs no host synchronisation.
+//
+// Engine 1, rollout_step_kernel: the parity reference. One launch per horizon step over
+// the alive rows. The launch performs the order-preserving `next_states[~dones]`
+// compaction (src/smbpo.py:243-246) itself: each workgroup scans the previous step's
+// tile counts and binary-searches the source row of each of its rows. It consumes
+// recorded draws in the reference's compacted layout and keeps libm arithmetic.
+//
+// Engine 2, rollout_persist_kernel: production. One launch for all H steps, each
+// workgroup keeping its tile for the whole horizon; surviving rows go to a staging area
+// and one of two emit tails orders them into the buffer:
+//   H x tiles <= EMIT_SELF_MAX   rollout_emit_self_kernel (count scan, emit and pointer
+//                                advance in one launch)
+//   larger                       rollout_scan_kernel + rollout_emit_kernel +
+//                                rollout_persist_finalize_kernel
+#include <type_traits>
 
 #include <hip/hip_runtime.h>
 
@@ -52,6 +62,7 @@ extern "C" __attribute__((visibility("default"))) int drpo_debug_stamps_rollout(
 
 #include "common.hpp"
 #include "env_constraints.hpp"
+#include "prp.hpp"
 
 using namespace drpo;
 
@@ -95,36 +106,60 @@ struct RolloutStepArgs {
   const void* env_prog;
 };
 
-__device__ __forceinline__ uint32_t prp_round(uint32_t r, uint32_t k) {
-  uint32_t h = r * 0x9E3779B1u ^ k;
-  h ^= h >> 15;
-  h *= 0x85EBCA77u;
-  h ^= h >> 13;
-  h *= 0xC2B2AE3Du;
-  h ^= h >> 16;
-  return h;
+// ---------------------------------------------------------------------------
+// Pieces both engines share. Args: RolloutStepArgs or PersistArgs (the field names agree).
+// ---------------------------------------------------------------------------
+
+// Exclusive scan over the NT threads of a workgroup: each thread passes the total of
+// its own run and gets the sum of the runs of the threads before it; `total` is the
+// sum over all threads. part: NT ints of LDS, free again after the next barrier.
+template <int NT>
+__device__ __forceinline__ int block_exclusive_scan(int run, int* part, int& total) {
+  const int tid = threadIdx.x;
+  part[tid] = run;
+  __syncthreads();
+  if (tid < 64) {   // inclusive scan of the NT partials in one wave
+    constexpr int PPL = NT / 64;
+    int v[PPL], sum = 0;
+    for (int q = 0; q < PPL; ++q) { v[q] = part[tid * PPL + q]; sum += v[q]; }
+    int incl = sum;
+    for (int o = 1; o < 64; o <<= 1) {
+      const int y = __shfl_up(incl, o, 64);
+      if (tid >= o) incl += y;
+    }
+    int e = incl - sum;
+    for (int q = 0; q < PPL; ++q) { e += v[q]; part[tid * PPL + q] = e; }
+  }
+  __syncthreads();
+  total = part[NT - 1];
+  return part[tid] - run;
 }
 
-// Keyed 4-round Feistel permutation of [0, 2^(2*hb)) with cycle walking into
-// [0, N): the first B outputs are B distinct indices (sampling without
-// replacement, the production stand-in for np.random.choice(N, B, replace=False)).
-__device__ inline int64_t prp_index(uint64_t i, uint64_t N, int hb, const uint32_t key[4]) {
-  const uint32_t mask = (hb >= 32) ? 0xFFFFFFFFu : ((1u << hb) - 1u);
-  uint64_t x = i;
-  for (int it = 0; it < 64; ++it) {
-    uint32_t L = (uint32_t)(x >> hb) & mask, R = (uint32_t)x & mask;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      uint32_t F = prp_round(R, key[r]) & mask;
-      uint32_t nl = R;
-      R = L ^ F;
-      L = nl;
-    }
-    x = ((uint64_t)L << hb) | R;
-    if (x < N) return (int64_t)x;
+// normalizer mean / std + 1e-6 and the log-var bounds into four 64-float LDS vectors
+// (issued first: the latency of these tiny loads hides behind what follows)
+template <class Args>
+__device__ __forceinline__ void preload_vecs(const Args& p, float* v_nm, float* v_ns, float* v_lo, float* v_hi) {
+  const int tid = threadIdx.x, S = p.S, S1 = p.S + 1;
+  if (tid < 256) {
+    const int j = tid & 63, w = tid >> 6;
+    if (w == 0 && j < S) v_nm[j] = p.norm_mean[j];
+    if (w == 1 && j < S) v_ns[j] = p.norm_std[j] + 1e-6f;
+    if (w == 2 && j < S1) v_lo[j] = p.min_lv[j];
+    if (w == 3 && j < S1) v_hi[j] = p.max_lv[j];
   }
-  return (int64_t)(x % N);   // unreachable in practice (expected walk < 4)
 }
+
+// physical replay row of batch row `row`: its chronological index (given, or the PRP
+// sample without replacement) turned by the circular buffer's write pointer
+template <class Args>
+__device__ __forceinline__ int64_t replay_row(const Args& p, int row) {
+  const int64_t c = p.init_idx ? p.init_idx[row]
+                               : prp_index((uint64_t)row, (uint64_t)p.replay_len, p.prp_half_bits, p.prp_key);
+  return (p.replay_ptr > p.replay_cap) ? (p.replay_ptr % p.replay_cap + c) % p.replay_cap : c;
+}
+
+// (The gather loop around replay_row stays written out in each kernel: as a helper it
+// changed the persistent kernel's code, +1 % at bench config 4; profiles/rollout_refactor.)
 
 // PG: the constraint phase runs the program interpreter (env id 4) instead of the
 // built-in functions: an instantiation of its own, so the built-in environments'
@@ -159,14 +194,7 @@ __global__ __launch_bounds__(NW * 64) void rollout_step_kernel(RolloutStepArgs p
   float* v_ns = vecs + 64;       // normalizer std + 1e-6
   float* v_lo = vecs + 128;      // min_log_var
   float* v_hi = vecs + 192;      // max_log_var
-  // issue these tiny loads first: their latency hides behind the scan / gather
-  if (tid < 256) {
-    const int j = tid & 63, w = tid >> 6;
-    if (w == 0 && j < S) v_nm[j] = p.norm_mean[j];
-    if (w == 1 && j < S) v_ns[j] = p.norm_std[j] + 1e-6f;
-    if (w == 2 && j < S1) v_lo[j] = p.min_lv[j];
-    if (w == 3 && j < S1) v_hi[j] = p.max_lv[j];
-  }
+  preload_vecs(p, v_nm, v_ns, v_lo, v_hi);
 
   RSTAMP(0);
   // ---- 0. row count / buffer offset of this step + compaction map ----------
@@ -190,28 +218,12 @@ __global__ __launch_bounds__(NW * 64) void rollout_step_kernel(RolloutStepArgs p
         run += p.prev_cnt[ti];
       }
     }
-    s_part[tid] = run;
-    __syncthreads();
-    if (tid < 64) {   // exclusive scan of the NT partials in one wave
-      constexpr int PPL = NT / 64;
-      int v[PPL], sum = 0;
-      for (int q = 0; q < PPL; ++q) { v[q] = s_part[tid * PPL + q]; sum += v[q]; }
-      int incl = sum;
-      for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(incl, o, 64);
-        if (tid >= o) incl += y;
-      }
-      int e = incl - sum;
-      for (int q = 0; q < PPL; ++q) { const int x = v[q]; s_part[tid * PPL + q] = e; e += x; }
-    }
-    __syncthreads();
+    const int base = block_exclusive_scan<NT>(run, s_part, n);   // total alive == n for this step
     for (int i = 0; i < per; ++i) {
       const int ti = b0 + i;
-      if (ti < T) scan[ti] += s_part[tid];
+      if (ti < T) scan[ti] += base;
     }
-    if (tid == NT - 1) scan[T] = s_part[NT - 1] + run;    // total alive == n for this step
     __syncthreads();
-    n = scan[T];
     off = p.off[p.t - 1] + n_prev;
     if (tid < ROWS && row0 + tid < n) {   // binary search: last tile with scan[tile] <= i
       const int i = row0 + tid;
@@ -237,16 +249,8 @@ __global__ __launch_bounds__(NW * 64) void rollout_step_kernel(RolloutStepArgs p
   for (int e = tid; e < ROWS * kpad; e += NT) {
     const int r = e / kpad, k = e - r * kpad;
     float v = 0.f;
-    if (r < rows && k < S) {
-      if (p.t == 0) {
-        int64_t c = p.init_idx ? p.init_idx[row0 + r]
-                               : prp_index((uint64_t)(row0 + r), (uint64_t)p.replay_len, p.prp_half_bits, p.prp_key);
-        int64_t phys = (p.replay_ptr > p.replay_cap) ? (p.replay_ptr % p.replay_cap + c) % p.replay_cap : c;
-        v = p.replay_states[phys * S + k];
-      } else {
-        v = p.prev_nxt[(int64_t)srcrow[r] * S + k];
-      }
-    }
+    if (r < rows && k < S)
+      v = p.t == 0 ? p.replay_states[replay_row(p, row0 + r) * S + k] : p.prev_nxt[(int64_t)srcrow[r] * S + k];
     xin[r * p.ldx + k] = v;
     if (k < S) sraw[r * p.lds + k] = v;
   }
@@ -355,8 +359,7 @@ __global__ __launch_bounds__(NW * 64) void rollout_step_kernel(RolloutStepArgs p
     if (tid < rows) {
       bool dn, vl;
       float hh[8];
-      if constexpr (PG) env_program_row(env_program_ptr(p.env_prog), xin + tid * p.ldx, dn, vl, hh);
-      else env_constraints_row(p.env, xin + tid * p.ldx, dn, vl, hh);
+      constraint_row<PG>(p.env, p.env_prog, xin + tid * p.ldx, dn, vl, hh);
       for (int c = 0; c < C; ++c) hval[tid * 8 + c] = hh[c];
       flags[tid] = (dn ? 1 : 0) | (vl ? 2 : 0);
       alive_r = !dn;
@@ -697,6 +700,14 @@ __device__ __forceinline__ void persist_noise(const float* eps_a, const float* e
   }
 }
 
+// log-var soft clamp into [lo, hi] + Gaussian sample on the hardware transcendentals
+// (the step engine keeps libm's expf / sqrtf on purpose)
+__device__ __forceinline__ float clamp_sample(float mean, float lv, float lo, float hi, float eps) {
+  lv = hi - fast_softplus(hi - lv);
+  lv = lo + fast_softplus(lv - lo);
+  return mean + fast_exp(0.5f * lv) * eps;
+}
+
 // LW: the actor's first layer, its output head and the first PERSIST_L2_LDS k-steps of
 // its hidden layer stay in LDS for the whole launch (the actor is the same every
 // step; with one 16-row tile per CU every weight byte is otherwise re-read from L2
@@ -759,13 +770,7 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
   constexpr bool paired = PM == 1;
   {
   PERSIST_LDS_LAYOUT(0, p.ldx, p.ldh, p.ldm, p.lds)
-  if (tid < 256) {
-    const int j = tid & 63, w = tid >> 6;
-    if (w == 0 && j < S) v_nm[j] = p.norm_mean[j];
-    if (w == 1 && j < S) v_ns[j] = p.norm_std[j] + 1e-6f;
-    if (w == 2 && j < S1) v_lo[j] = p.min_lv[j];
-    if (w == 3 && j < S1) v_hi[j] = p.max_lv[j];
-  }
+  preload_vecs(p, v_nm, v_ns, v_lo, v_hi);
   if constexpr (LW) {
     // packed mirrors: aW1 is [16 cb][1 k-step][256], aW3 [1 cb][16 k-steps][256];
     // aW2 keeps k-steps [0, PERSIST_L2_LDS) of each of its 16 column blocks
@@ -788,10 +793,7 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
     const int r = e / kpad, k = e - r * kpad;
     float v = 0.f;
     if (r < nrows && k < S) {
-      const int64_t c = p.init_idx ? p.init_idx[row0 + r]
-                                   : prp_index((uint64_t)(row0 + r), (uint64_t)p.replay_len, p.prp_half_bits, p.prp_key);
-      const int64_t phys = (p.replay_ptr > p.replay_cap) ? (p.replay_ptr % p.replay_cap + c) % p.replay_cap : c;
-      v = p.replay_states[phys * S + k];
+      v = p.replay_states[replay_row(p, row0 + r) * S + k];
     }
     xin[r * p.ldx + k] = v;
     if (k < S) sraw[r * p.lds + k] = v;
@@ -909,10 +911,8 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
       if (tid < ROWS * S1) {
         const int r = tid / S1, j = tid - r * S1;
         const float mean = (narrow_pair_sum<NW, RB>(red, 0, r, j) + bd) + (j < S ? sraw[r * ldss + j] : 0.f);
-        float lv = narrow_pair_sum<NW, RB>(red, 1, r, j) + bl;
-        lv = v_hi[j] - fast_softplus(v_hi[j] - lv);
-        lv = v_lo[j] + fast_softplus(lv - v_lo[j]);
-        const float x = mean + fast_exp(0.5f * lv) * nz_m[r * 64 + j];
+        const float lv = narrow_pair_sum<NW, RB>(red, 1, r, j) + bl;
+        const float x = clamp_sample(mean, lv, v_lo[j], v_hi[j], nz_m[r * 64 + j]);
         if (j < S) xin[r * ldx + j] = x;
         else rew[r] = x;
       }
@@ -950,10 +950,7 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
       for (int e = tid; e < ROWS * S1; e += NT) {
         const int r = e / S1, j = e - r * S1;
         const float mean = dout[r * ldm + j] + (j < S ? sraw[r * ldss + j] : 0.f);
-        float lv = lout[r * ldm + j];
-        lv = v_hi[j] - fast_softplus(v_hi[j] - lv);
-        lv = v_lo[j] + fast_softplus(lv - v_lo[j]);
-        const float x = mean + fast_exp(0.5f * lv) * nz_m[r * 64 + j];
+        const float x = clamp_sample(mean, lout[r * ldm + j], v_lo[j], v_hi[j], nz_m[r * 64 + j]);
         if (j < S) xin[r * ldx + j] = x;
         else rew[r] = x;
       }
@@ -969,14 +966,13 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
       bool in_r = false, dn = false, vl = false;
       if (tid < ROWS && alive_cur[tid]) {
         float hh[8];
+        const void* prog = nullptr;
         if constexpr (PG) {
           // opaque per step: the program's (loop-invariant) scalar loads stay in the step
-          const void* prog = PARG(env_prog);
+          prog = PARG(env_prog);
           asm volatile("" : "+s"(prog));
-          env_program_row(env_program_ptr(prog), xin + tid * ldx, dn, vl, hh);
-        } else {
-          env_constraints_row(p.env, xin + tid * ldx, dn, vl, hh);
         }
+        constraint_row<PG>(p.env, prog, xin + tid * ldx, dn, vl, hh);
         for (int c = 0; c < C; ++c) PARG(st_h)[(sb + tid) * C + c] = hh[c];
         PARG(st_r)[sb + tid] = rew[tid];
         PARG(st_dv)[sb + tid] = (uint8_t)((dn ? 1 : 0) | (vl ? 2 : 0));
@@ -1032,52 +1028,26 @@ __global__ __launch_bounds__(256) void rollout_scan_kernel(const int* __restrict
   int run = 0;
   for (int i = 0; i < per; ++i)
     if (b0 + i < ntiles) run += c[b0 + i];
-  part[tid] = run;
-  __syncthreads();
-  if (tid < 64) {   // exclusive scan of the 256 partials in one wave
-    int v[4], sum = 0;
-    for (int q = 0; q < 4; ++q) { v[q] = part[tid * 4 + q]; sum += v[q]; }
-    int incl = sum;
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(incl, o, 64);
-      if (tid >= o) incl += y;
-    }
-    int e = incl - sum;
-    for (int q = 0; q < 4; ++q) { const int x = v[q]; part[tid * 4 + q] = e; e += x; }
-    if (tid == 63) n[t] = incl;
-  }
-  __syncthreads();
-  int e = part[tid];
+  int total;
+  int e = block_exclusive_scan<256>(run, part, total);
+  if (tid == 0) n[t] = total;
   for (int i = 0; i < per; ++i)
     if (b0 + i < ntiles) { ps[b0 + i] = e; e += c[b0 + i]; }
 }
 
-// staged rows -> circular virtual buffer, in the reference's order
-template <int ROWS>
-__global__ __launch_bounds__(256) void rollout_emit_kernel(PersistArgs p, const int* __restrict__ pos,
-                                                           const int* __restrict__ n, const int64_t* __restrict__ vptr,
-                                                           int advanced, const int64_t* __restrict__ offs,
-                                                           int64_t vcap, float* __restrict__ vs, float* __restrict__ va,
-                                                           float* __restrict__ vs2, float* __restrict__ vr,
-                                                           float* __restrict__ vh, uint8_t* __restrict__ vd,
-                                                           uint8_t* __restrict__ vv) {
-  __shared__ int64_t s_off;
-  const int t = blockIdx.y, tid = threadIdx.x;
-  if (tid == 0) {
-    int64_t o = 0;
-    for (int u = 0; u < t; ++u) o += n[u];
-    // rollout_scanfin_kernel already advanced the pointer by the total (offs[H])
-    s_off = o + *vptr - (advanced ? offs[p.H] : 0);
-  }
-  __syncthreads();
-  const int slot = blockIdx.x * 256 + tid;
-  const int tile = slot / ROWS, k = slot - tile * ROWS;
-  if (tile >= p.ntiles) return;
-  const size_t ti = (size_t)t * p.ntiles + tile;
-  if (k >= p.cnt[ti]) return;
+// the circular virtual buffer's seven components and its capacity in rows
+struct EmitDst {
+  float *vs, *va, *vs2, *vr, *vh;
+  uint8_t *vd, *vv;
+  int64_t vcap;
+};
+
+// staged row src -> buffer row q. The destinations are restrict parameters (a struct's
+// members cannot say so): the row's loads need not wait for its stores.
+__device__ __forceinline__ void emit_row(const PersistArgs& p, size_t src, int64_t q, float* __restrict__ vs,
+                                         float* __restrict__ va, float* __restrict__ vs2, float* __restrict__ vr,
+                                         float* __restrict__ vh, uint8_t* __restrict__ vd, uint8_t* __restrict__ vv) {
   const int S = p.S, A = p.A, C = p.C;
-  const size_t src = (size_t)t * p.B + (size_t)tile * ROWS + p.inv[ti * ROWS + k];
-  const int64_t q = (s_off + pos[ti] + k) % vcap;
   for (int j = 0; j < S; ++j) {
     vs[q * S + j] = p.st_s[src * S + j];
     vs2[q * S + j] = p.st_s2[src * S + j];
@@ -1088,6 +1058,32 @@ __global__ __launch_bounds__(256) void rollout_emit_kernel(PersistArgs p, const 
   const uint8_t dv = p.st_dv[src];
   vd[q] = dv & 1;
   vv[q] = (dv >> 1) & 1;
+}
+
+// staged row src -> buffer row pos (mod capacity)
+__device__ __forceinline__ void emit_row(const PersistArgs& p, const EmitDst& o, size_t src, int64_t pos) {
+  emit_row(p, src, pos % o.vcap, o.vs, o.va, o.vs2, o.vr, o.vh, o.vd, o.vv);
+}
+
+// staged rows -> circular virtual buffer, in the reference's order
+template <int ROWS>
+__global__ __launch_bounds__(256) void rollout_emit_kernel(PersistArgs p, const int* __restrict__ pos,
+                                                           const int* __restrict__ n, const int64_t* __restrict__ vptr,
+                                                           EmitDst dst) {
+  __shared__ int64_t s_off;
+  const int t = blockIdx.y, tid = threadIdx.x;
+  if (tid == 0) {
+    int64_t o = 0;
+    for (int u = 0; u < t; ++u) o += n[u];
+    s_off = o + *vptr;
+  }
+  __syncthreads();
+  const int slot = blockIdx.x * 256 + tid;
+  const int tile = slot / ROWS, k = slot - tile * ROWS;
+  if (tile >= p.ntiles) return;
+  const size_t ti = (size_t)t * p.ntiles + tile;
+  if (k >= p.cnt[ti]) return;
+  emit_row(p, dst, (size_t)t * p.B + (size_t)tile * ROWS + p.inv[ti * ROWS + k], s_off + pos[ti] + k);
 }
 
 // Small rollouts (H x tiles <= EMIT_SELF_MAX counts): count scan, ordered emit and
@@ -1101,10 +1097,7 @@ constexpr int EMIT_SELF_MAX = 8192;
 template <int ROWS>
 __global__ __launch_bounds__(256) void rollout_emit_self_kernel(PersistArgs p, const int64_t* __restrict__ base_slot,
                                                                 int64_t* __restrict__ vptr, int64_t* __restrict__ off,
-                                                                int64_t vcap, float* __restrict__ vs,
-                                                                float* __restrict__ va, float* __restrict__ vs2,
-                                                                float* __restrict__ vr, float* __restrict__ vh,
-                                                                uint8_t* __restrict__ vd, uint8_t* __restrict__ vv) {
+                                                                EmitDst dst) {
   constexpr int TPB = 256 / ROWS;   // tiles per workgroup
   __shared__ int s_pre[4], s_tot[4], s_loc[TPB];
   const int t = blockIdx.y, tid = threadIdx.x;
@@ -1135,65 +1128,8 @@ __global__ __launch_bounds__(256) void rollout_emit_self_kernel(PersistArgs p, c
   if (tile >= p.ntiles || k >= s_loc[j]) return;
   int loc = 0;
   for (int u = 0; u < j; ++u) loc += s_loc[u];
-  const int S = p.S, A = p.A, C = p.C;
   const size_t ti = (size_t)t * p.ntiles + tile;
-  const size_t src = (size_t)t * p.B + (size_t)tile * ROWS + p.inv[ti * ROWS + k];
-  const int64_t q = (base + pre + loc + k) % vcap;
-  for (int jj = 0; jj < S; ++jj) {
-    vs[q * S + jj] = p.st_s[src * S + jj];
-    vs2[q * S + jj] = p.st_s2[src * S + jj];
-  }
-  for (int d = 0; d < A; ++d) va[q * A + d] = p.st_a[src * A + d];
-  for (int c = 0; c < C; ++c) vh[q * C + c] = p.st_h[src * C + c];
-  vr[q] = p.st_r[src];
-  const uint8_t dv = p.st_dv[src];
-  vd[q] = dv & 1;
-  vv[q] = (dv >> 1) & 1;
-}
-
-// Mid-size rollouts (H x tiles <= 16384 counts): the per-step scans, the step offsets and
-// the pointer advance of rollout_scan_kernel + rollout_persist_finalize_kernel in ONE
-// single-workgroup launch (the emit then reads the advanced pointer minus the total).
-__global__ __launch_bounds__(256) void rollout_scanfin_kernel(const int* __restrict__ cnt, int* __restrict__ pos,
-                                                              int* __restrict__ n, int64_t* __restrict__ off,
-                                                              int64_t* __restrict__ vptr, int ntiles, int H) {
-  __shared__ int part[256];
-  __shared__ int s_tot;
-  const int tid = threadIdx.x;
-  int64_t total = 0;
-  for (int t = 0; t < H; ++t) {
-    const int* c = cnt + (size_t)t * ntiles;
-    int* ps = pos + (size_t)t * ntiles;
-    const int per = (ntiles + 255) / 256, b0 = tid * per;
-    int run = 0;
-    for (int i = 0; i < per; ++i)
-      if (b0 + i < ntiles) run += c[b0 + i];
-    part[tid] = run;
-    __syncthreads();
-    if (tid < 64) {
-      int v[4], sum = 0;
-      for (int q = 0; q < 4; ++q) { v[q] = part[tid * 4 + q]; sum += v[q]; }
-      int incl = sum;
-      for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(incl, o, 64);
-        if (tid >= o) incl += y;
-      }
-      int e = incl - sum;
-      for (int q = 0; q < 4; ++q) { const int x = v[q]; part[tid * 4 + q] = e; e += x; }
-      if (tid == 63) { n[t] = incl; s_tot = incl; }
-    }
-    __syncthreads();
-    int e = part[tid];
-    for (int i = 0; i < per; ++i)
-      if (b0 + i < ntiles) { ps[b0 + i] = e; e += c[b0 + i]; }
-    if (tid == 0) off[t] = total;
-    total += s_tot;
-    __syncthreads();
-  }
-  if (tid == 0) {
-    off[H] = total;
-    *vptr += total;
-  }
+  emit_row(p, dst, (size_t)t * p.B + (size_t)tile * ROWS + p.inv[ti * ROWS + k], base + pre + loc + k);
 }
 
 // off[t] = sum n[<t], off[H] = total; advance the buffer pointer
@@ -1213,68 +1149,83 @@ __global__ void rollout_persist_finalize_kernel(int64_t* vptr, const int* n, int
 
 static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
+// The workspace, piece by piece (in this order, each 256-byte aligned).
 struct RolloutWs {
+  // step engine: double-buffered next states, per-tile alive counts, in-tile maps
   float* nxt[2];
   int* cnt[2];
   int* inv[2];
+  // both engines: n[t] rows of step t; off[t] their buffer offset, off[H] the rows the
+  // last call wrote, off[H + 1] the fused engine's copy of the buffer pointer
   int* n;
   int64_t* off;
+  // fused engine: staging indexed [t][original row] (A, C <= 8 slots), per-(t, tile)
+  // counts / in-tile maps / positions
+  float *st_s, *st_s2, *st_a, *st_r, *st_h;
+  uint8_t* st_dv;
+  int *st_cnt, *st_inv, *pos;
 };
 
-// Byte offsets of the workspace pieces (in order); returns total bytes.
-// pieces 0-7: step-engine scratch + n/off; 8-16: fused-engine staging, indexed
-// [t][original row] (A, C <= 8 slots), per-(t, tile) counts / in-tile maps / positions
-constexpr int WS_PIECES = 17;
-static size_t rollout_ws_offsets(int B, int S, int H, size_t off[WS_PIECES]) {
+// Carves the workspace at `base` (0: the pieces' byte offsets); returns its size in bytes.
+static size_t rollout_ws(int B, int S, int H, uintptr_t base, RolloutWs& w) {
   const size_t HB = (size_t)H * B, T16 = (size_t)B / 16 + 1;
-  const size_t bytes[WS_PIECES] = {sizeof(float) * (size_t)B * S, sizeof(float) * (size_t)B * S,
-                                   sizeof(int) * T16, sizeof(int) * T16,
-                                   sizeof(int) * (size_t)B, sizeof(int) * (size_t)B,
-                                   sizeof(int) * (size_t)(H + 1), sizeof(int64_t) * (size_t)(H + 2),
-                                   sizeof(float) * HB * S, sizeof(float) * HB * S, sizeof(float) * HB * 8,
-                                   sizeof(float) * HB, sizeof(float) * HB * 8, HB,
-                                   sizeof(int) * (size_t)H * T16, sizeof(int) * (size_t)H * (B + 32),
-                                   sizeof(int) * (size_t)H * T16};
   size_t o = 0;
-  for (int i = 0; i < WS_PIECES; ++i) {
-    off[i] = o;
-    o += align256(bytes[i]);
-  }
+  auto take = [&](auto*& piece, size_t bytes) {
+    piece = reinterpret_cast<std::remove_reference_t<decltype(piece)>>(base + o);
+    o += align256(bytes);
+  };
+  take(w.nxt[0], sizeof(float) * (size_t)B * S);
+  take(w.nxt[1], sizeof(float) * (size_t)B * S);
+  take(w.cnt[0], sizeof(int) * T16);
+  take(w.cnt[1], sizeof(int) * T16);
+  take(w.inv[0], sizeof(int) * (size_t)B);
+  take(w.inv[1], sizeof(int) * (size_t)B);
+  take(w.n, sizeof(int) * (size_t)(H + 1));
+  take(w.off, sizeof(int64_t) * (size_t)(H + 2));
+  take(w.st_s, sizeof(float) * HB * S);
+  take(w.st_s2, sizeof(float) * HB * S);
+  take(w.st_a, sizeof(float) * HB * 8);
+  take(w.st_r, sizeof(float) * HB);
+  take(w.st_h, sizeof(float) * HB * 8);
+  take(w.st_dv, HB);
+  take(w.st_cnt, sizeof(int) * (size_t)H * T16);
+  take(w.st_inv, sizeof(int) * (size_t)H * (B + 32));
+  take(w.pos, sizeof(int) * (size_t)H * T16);
   return o;
 }
 
-static RolloutWs rollout_ws(int B, int S, int H, char* base) {
-  size_t o[WS_PIECES];
-  rollout_ws_offsets(B, S, H, o);
-  RolloutWs w;
-  w.nxt[0] = (float*)(base + o[0]);
-  w.nxt[1] = (float*)(base + o[1]);
-  w.cnt[0] = (int*)(base + o[2]);
-  w.cnt[1] = (int*)(base + o[3]);
-  w.inv[0] = (int*)(base + o[4]);
-  w.inv[1] = (int*)(base + o[5]);
-  w.n = (int*)(base + o[6]);
-  w.off = (int64_t*)(base + o[7]);
-  return w;
-}
-
 DRPO_API size_t drpo_rollout_workspace_size(int B, int S, int H) {
-  size_t o[WS_PIECES];
-  return rollout_ws_offsets(B, S, H, o);
+  RolloutWs w;
+  return rollout_ws(B, S, H, 0, w);
 }
 
 // Byte offset (inside the workspace) of the device int64 that holds the number of
 // transitions written by the last drpo_rollout call (off[H]).
 DRPO_API size_t drpo_rollout_count_offset(int B, int S, int H) {
-  size_t o[WS_PIECES];
-  rollout_ws_offsets(B, S, H, o);
-  return o[7] + sizeof(int64_t) * (size_t)H;
+  RolloutWs w;
+  rollout_ws(B, S, H, 0, w);
+  return (size_t)reinterpret_cast<uintptr_t>(w.off + H);
 }
 
-static int hb_for(int64_t n) {
-  int b = 1;
-  while ((1ull << (2 * b)) < (uint64_t)n) ++b;
-  return b;
+// The fields RolloutStepArgs and PersistArgs share, from the descriptor.
+template <class Args>
+static void fill_shared_args(Args& a, const drpo_rollout_desc_t* d, int64_t rlen) {
+  const int S = d->S, A = d->A;
+  a.S = S; a.A = A; a.C = d->C; a.Ha = d->Ha; a.Hm = d->Hm;
+  a.env.id = d->env_id; a.env.surr_start = d->tracking_surr_start; a.env.n_surr = d->tracking_n_surr;
+  a.env.thr0 = d->env_thr0; a.env.thr1 = d->env_thr1;
+  a.aW1 = d->aW1; a.ab1 = d->ab1; a.aW2 = d->aW2; a.ab2 = d->ab2; a.aW3 = d->aW3; a.ab3 = d->ab3;
+  a.norm_mean = d->norm_mean; a.norm_std = d->norm_std; a.min_lv = d->min_lv; a.max_lv = d->max_lv;
+  a.replay_states = d->replay_states; a.init_idx = d->init_idx;
+  a.replay_len = rlen; a.replay_ptr = d->replay_ptr; a.replay_cap = d->replay_cap;
+  a.prp_half_bits = hb_for(rlen);
+  prp_keys(d->seed, d->ctr, a.prp_key);
+  a.seed = d->seed; a.ctr = d->ctr;
+  a.ldx = lds_ld(S + A);
+  a.ldh = lds_ld(d->Ha > d->Hm ? d->Ha : d->Hm);
+  a.ldm = round_up(S + 1, 16) + 4;
+  a.lds = round_up(S, 4);
+  a.env_prog = d->env_id == DRPO_ENV_PROGRAM ? d->env_program : nullptr;
 }
 
 // LDS bytes of rollout_persist_kernel for `rpt`-row tiles (without the LDS-resident
@@ -1289,114 +1240,129 @@ static size_t persist_lds_bytes(int S, int A, int Ha, int Hm, int rpt, int nw) {
                           (size_t)nw * (rpt / 16) * 256 + 256);
 }
 
-// engine 2: fused-horizon kernel + count scan + ordered emit + pointer advance
-static int rollout_fused(const drpo_rollout_desc_t* d, int rpt, int64_t rlen, hipStream_t stream) {
+// LDS bytes of rollout_step_kernel: per row xin, h1-h3, sraw, ao, dout, lout, act, rew,
+// hval, flags, srcrow; then the split-K partials, the scan partials, the previous step's
+// tile prefix and the normalizer / log-var vectors.
+static size_t step_lds_bytes(int S, int A, int Ha, int Hm, int rpt, int nw, int tiles) {
+  const int S1 = S + 1;
+  const int ldx = lds_ld(S + A), ldh = lds_ld(Ha > Hm ? Ha : Hm), ldm = round_up(S1, 16) + 4, ldss = round_up(S, 4);
+  return sizeof(float) * ((size_t)rpt * (ldx + 3 * ldh + ldss + 20 + 2 * ldm + 8 + 1 + 8 + 2) +
+                          (size_t)nw * (rpt / 16) * 256 + nw * 64 + (size_t)tiles + 1 + 256);
+}
+
+// 8-wave workgroups (16 waves measured 3.5 % slower at config 2, profiles/r02/rollout_ab)
+template <int RB, bool LW>
+static void launch_persist(bool paired, bool pg, const PersistArgs& a, size_t lds_bytes, hipStream_t stream) {
+  auto k = paired ? (pg ? rollout_persist_kernel<RB, 8, LW, 1, true> : rollout_persist_kernel<RB, 8, LW, 1, false>)
+                  : (pg ? rollout_persist_kernel<RB, 8, LW, 0, true> : rollout_persist_kernel<RB, 8, LW, 0, false>);
+  k<<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
+}
+
+// engine 2: fused-horizon kernel + one of the two emit tails
+static int rollout_fused(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt, int64_t rlen, hipStream_t stream) {
   DRPO_REQUIRE(d->H <= PERSIST_MAX_H, "drpo_rollout: engine 2 supports horizon <= %d", PERSIST_MAX_H);
   const int S = d->S, A = d->A, S1 = d->S + 1, B = d->B, H = d->H;
-  size_t o[WS_PIECES];
-  rollout_ws_offsets(B, S, H, o);
-  char* base = (char*)d->workspace;
   PersistArgs a{};
-  a.S = S; a.A = A; a.C = d->C; a.Ha = d->Ha; a.Hm = d->Hm; a.B = B; a.H = H;
+  fill_shared_args(a, d, rlen);
+  a.B = B; a.H = H;
   a.ntiles = (B + rpt - 1) / rpt;
-  a.env.id = d->env_id; a.env.surr_start = d->tracking_surr_start; a.env.n_surr = d->tracking_n_surr;
-  a.env.thr0 = d->env_thr0; a.env.thr1 = d->env_thr1;
-  a.aW1 = d->aW1; a.ab1 = d->ab1; a.aW2 = d->aW2; a.ab2 = d->ab2; a.aW3 = d->aW3; a.ab3 = d->ab3;
   a.mW1 = d->mW1; a.mb1 = d->mb1; a.mW2 = d->mW2; a.mb2 = d->mb2; a.dW1 = d->dW1; a.db1 = d->db1;
   a.dW2 = d->dW2; a.db2 = d->db2; a.lW1 = d->lW1; a.lb1 = d->lb1; a.lW2 = d->lW2; a.lb2 = d->lb2;
   a.ms_in = drpo_packed_size(S + A, d->Hm);
   a.ms_hid = drpo_packed_size(d->Hm, d->Hm);
   a.ms_out = drpo_packed_size(d->Hm, S1);
-  a.norm_mean = d->norm_mean; a.norm_std = d->norm_std; a.min_lv = d->min_lv; a.max_lv = d->max_lv;
-  a.replay_states = d->replay_states; a.init_idx = d->init_idx;
-  a.replay_len = rlen; a.replay_ptr = d->replay_ptr; a.replay_cap = d->replay_cap;
-  a.prp_half_bits = hb_for(rlen);
-  for (int i = 0; i < 4; ++i) a.prp_key[i] = (uint32_t)(d->seed >> (8 * i)) * 0x9E3779B9u + (uint32_t)d->ctr * (2 * i + 1) + i;
   a.eps_a = d->eps_a; a.eps_m = d->eps_m;
-  a.seed = d->seed; a.ctr = d->ctr;
-  a.st_s = (float*)(base + o[8]); a.st_s2 = (float*)(base + o[9]); a.st_a = (float*)(base + o[10]);
-  a.st_r = (float*)(base + o[11]); a.st_h = (float*)(base + o[12]); a.st_dv = (uint8_t*)(base + o[13]);
-  a.cnt = (int*)(base + o[14]); a.inv = (int*)(base + o[15]);
-  int* pos = (int*)(base + o[16]);
-  int* n = (int*)(base + o[6]);
-  int64_t* off = (int64_t*)(base + o[7]);
-  a.ldx = lds_ld(S + A);
-  a.ldh = lds_ld(d->Ha > d->Hm ? d->Ha : d->Hm);
-  a.ldm = round_up(S1, 16) + 4;
-  a.lds = round_up(S, 4);
+  a.st_s = w.st_s; a.st_s2 = w.st_s2; a.st_a = w.st_a; a.st_r = w.st_r; a.st_h = w.st_h; a.st_dv = w.st_dv;
+  a.cnt = w.st_cnt; a.inv = w.st_inv;
   for (int t = 0; t < H; ++t) a.members[t] = d->members[t];
-  const bool pg = d->env_id == DRPO_ENV_PROGRAM;
-  a.env_prog = pg ? d->env_program : nullptr;
 
-  // 8-wave workgroups (16 waves measured 3.5 % slower at config 2, profiles/r02/rollout_ab)
   const size_t lds_bytes = persist_lds_bytes(S, A, d->Ha, d->Hm, rpt, 8);
   DRPO_REQUIRE(lds_bytes <= 160 * 1024, "drpo_rollout: LDS %zu too large", lds_bytes);
   // LDS-resident actor weights (see rollout_persist_kernel) when they fit
   const size_t lw_bytes = sizeof(float) * (size_t)(32 + 16 * PERSIST_L2_LDS) * 256;
   const bool lw = rpt == 16 && S <= 16 && d->Ha == 256 && 2 * A <= 16 && lds_bytes + lw_bytes <= 160 * 1024;
   const bool paired = S1 <= 16 && d->Hm == 200;   // the kernel's PM specialisation
+  const bool pg = d->env_id == DRPO_ENV_PROGRAM;
   const bool self_emit = (int64_t)H * a.ntiles <= EMIT_SELF_MAX;
   if (self_emit) {
     a.vptr_in = d->vptr;
-    a.base_slot = off + H + 1;
+    a.base_slot = w.off + H + 1;
   }
   if (d->step_events) hipEventRecord((hipEvent_t)d->step_events[0], stream);
-  if (pg) {
-    if (rpt == 32) {
-      if (paired) rollout_persist_kernel<2, 8, false, 1, true><<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
-      else rollout_persist_kernel<2, 8, false, 0, true><<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
-    } else if (lw) {
-      if (paired) rollout_persist_kernel<1, 8, true, 1, true><<<a.ntiles, 8 * 64, lds_bytes + lw_bytes, stream>>>(a);
-      else rollout_persist_kernel<1, 8, true, 0, true><<<a.ntiles, 8 * 64, lds_bytes + lw_bytes, stream>>>(a);
-    } else {
-      if (paired) rollout_persist_kernel<1, 8, false, 1, true><<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
-      else rollout_persist_kernel<1, 8, false, 0, true><<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
-    }
-  } else if (rpt == 32) {
-    if (paired) rollout_persist_kernel<2, 8, false, 1><<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
-    else rollout_persist_kernel<2, 8, false, 0><<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
-  } else if (lw) {
-    if (paired) rollout_persist_kernel<1, 8, true, 1><<<a.ntiles, 8 * 64, lds_bytes + lw_bytes, stream>>>(a);
-    else rollout_persist_kernel<1, 8, true, 0><<<a.ntiles, 8 * 64, lds_bytes + lw_bytes, stream>>>(a);
-  } else {
-    if (paired) rollout_persist_kernel<1, 8, false, 1><<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
-    else rollout_persist_kernel<1, 8, false, 0><<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
-  }
+  if (rpt == 32) launch_persist<2, false>(paired, pg, a, lds_bytes, stream);
+  else if (lw) launch_persist<1, true>(paired, pg, a, lds_bytes + lw_bytes, stream);
+  else launch_persist<1, false>(paired, pg, a, lds_bytes, stream);
   DRPO_LAUNCH_CHECK("rollout_persist");
   if (d->step_events) hipEventRecord((hipEvent_t)d->step_events[1], stream);
   const dim3 eg((unsigned)((a.ntiles * rpt + 255) / 256), (unsigned)H);
+  const EmitDst dst{d->vs, d->va, d->vs2, d->vr, d->vh, d->vd, d->vv, d->vcap};
   if (self_emit) {
-    if (rpt == 32)
-      rollout_emit_self_kernel<32><<<eg, 256, 0, stream>>>(a, off + H + 1, d->vptr, off, d->vcap, d->vs, d->va,
-                                                           d->vs2, d->vr, d->vh, d->vd, d->vv);
-    else
-      rollout_emit_self_kernel<16><<<eg, 256, 0, stream>>>(a, off + H + 1, d->vptr, off, d->vcap, d->vs, d->va,
-                                                           d->vs2, d->vr, d->vh, d->vd, d->vv);
+    auto k = rpt == 32 ? rollout_emit_self_kernel<32> : rollout_emit_self_kernel<16>;
+    k<<<eg, 256, 0, stream>>>(a, w.off + H + 1, d->vptr, w.off, dst);
     DRPO_LAUNCH_CHECK("rollout_emit_self");
     return DRPO_OK;
   }
-  // mid-size rollouts: scan + offsets + pointer advance in one single-workgroup launch
-  const int fin1 = (int64_t)H * a.ntiles <= 16384;
-  if (fin1) {
-    rollout_scanfin_kernel<<<1, 256, 0, stream>>>(a.cnt, pos, n, off, d->vptr, a.ntiles, H);
-    DRPO_LAUNCH_CHECK("rollout_scanfin");
-  } else {
-    rollout_scan_kernel<<<H, 256, 0, stream>>>(a.cnt, pos, n, a.ntiles);
-    DRPO_LAUNCH_CHECK("rollout_scan");
-  }
-  if (rpt == 32)
-    rollout_emit_kernel<32><<<eg, 256, 0, stream>>>(a, pos, n, d->vptr, fin1, off, d->vcap, d->vs, d->va,
-                                                    d->vs2, d->vr, d->vh, d->vd, d->vv);
-  else
-    rollout_emit_kernel<16><<<eg, 256, 0, stream>>>(a, pos, n, d->vptr, fin1, off, d->vcap, d->vs, d->va,
-                                                    d->vs2, d->vr, d->vh, d->vd, d->vv);
+  rollout_scan_kernel<<<H, 256, 0, stream>>>(a.cnt, w.pos, w.n, a.ntiles);
+  DRPO_LAUNCH_CHECK("rollout_scan");
+  auto k = rpt == 32 ? rollout_emit_kernel<32> : rollout_emit_kernel<16>;
+  k<<<eg, 256, 0, stream>>>(a, w.pos, w.n, d->vptr, dst);
   DRPO_LAUNCH_CHECK("rollout_emit");
-  if (fin1) return DRPO_OK;
-  rollout_persist_finalize_kernel<<<1, 1, 0, stream>>>(d->vptr, n, off, H);
+  rollout_persist_finalize_kernel<<<1, 1, 0, stream>>>(d->vptr, w.n, w.off, H);
   DRPO_LAUNCH_CHECK("rollout_finalize");
   return DRPO_OK;
 }
 
+// engine 1: one launch per horizon step + pointer advance
+static int rollout_stepwise(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt, int64_t rlen,
+                            hipStream_t stream) {
+  const int S = d->S, A = d->A, S1 = d->S + 1;
+  RolloutStepArgs a{};
+  fill_shared_args(a, d, rlen);
+  a.Bmax = d->B;
+  a.vs = d->vs; a.va = d->va; a.vs2 = d->vs2; a.vr = d->vr; a.vh = d->vh; a.vd = d->vd; a.vv = d->vv;
+  a.vptr = d->vptr; a.vcap = d->vcap;
+  a.n = w.n; a.off = w.off;
+
+  const int tiles = (d->B + rpt - 1) / rpt;
+  constexpr int NW = 8;
+  const size_t lds_bytes = step_lds_bytes(S, A, d->Ha, d->Hm, rpt, NW, tiles);
+  DRPO_REQUIRE(lds_bytes <= 160 * 1024, "drpo_rollout: LDS %zu too large", lds_bytes);
+  const bool pg = d->env_id == DRPO_ENV_PROGRAM;
+  auto k = rpt == 32 ? (pg ? rollout_step_kernel<2, NW, true> : rollout_step_kernel<2, NW, false>)
+                     : (pg ? rollout_step_kernel<1, NW, true> : rollout_step_kernel<1, NW, false>);
+
+  const int E_out_in[6][2] = {{d->Hm, S + A}, {d->Hm, d->Hm}, {d->Hm, d->Hm}, {S1, d->Hm}, {d->Hm, d->Hm}, {S1, d->Hm}};
+  const float* Wb[6] = {d->mW1, d->mW2, d->dW1, d->dW2, d->lW1, d->lW2};
+  const float* Bb[6] = {d->mb1, d->mb2, d->db1, d->db2, d->lb1, d->lb2};
+
+  for (int t = 0; t < d->H; ++t) {
+    const int m = d->members[t];
+    const float* Wm[6];
+    const float* Bm[6];
+    for (int i = 0; i < 6; ++i) {
+      // packed mirrors: member stride = drpo_packed_size(in, out)
+      Wm[i] = Wb[i] + (size_t)m * drpo_packed_size(E_out_in[i][1], E_out_in[i][0]);
+      Bm[i] = Bb[i] + (size_t)m * E_out_in[i][0];
+    }
+    a.mW1 = Wm[0]; a.mW2 = Wm[1]; a.dW1 = Wm[2]; a.dW2 = Wm[3]; a.lW1 = Wm[4]; a.lW2 = Wm[5];
+    a.mb1 = Bm[0]; a.mb2 = Bm[1]; a.db1 = Bm[2]; a.db2 = Bm[3]; a.lb1 = Bm[4]; a.lb2 = Bm[5];
+    a.t = t;
+    const int cur = t & 1, prv = cur ^ 1;
+    a.prev_nxt = w.nxt[prv]; a.prev_cnt = w.cnt[prv]; a.prev_inv = w.inv[prv];
+    a.nxt = w.nxt[cur]; a.cnt = w.cnt[cur]; a.inv = w.inv[cur];
+    a.eps_a = d->eps_a ? d->eps_a + (size_t)t * d->B * A : nullptr;
+    a.eps_m = d->eps_m ? d->eps_m + (size_t)t * d->B * S1 : nullptr;
+    if (d->step_events) hipEventRecord((hipEvent_t)d->step_events[2 * t], stream);
+    k<<<tiles, NW * 64, lds_bytes, stream>>>(a);
+    DRPO_LAUNCH_CHECK("rollout_step");
+    if (d->step_events) hipEventRecord((hipEvent_t)d->step_events[2 * t + 1], stream);
+  }
+  rollout_finalize_kernel<<<1, 1, 0, stream>>>(d->vptr, w.n, w.off, d->H);
+  DRPO_LAUNCH_CHECK("rollout_finalize");
+  return DRPO_OK;
+}
+
+// validation, tile choice, engine choice
 DRPO_API int drpo_rollout(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   DRPO_REQUIRE(d, "drpo_rollout: null descriptor");
@@ -1423,7 +1389,6 @@ DRPO_API int drpo_rollout(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
   if (d->env_id == ENV_TRACKING)
     DRPO_REQUIRE(d->tracking_surr_start + 4 * d->tracking_n_surr <= d->S, "drpo_rollout: tracking layout");
 
-  RolloutWs w = rollout_ws(d->B, d->S, d->H, (char*)d->workspace);
   // 32-row tiles halve the weight bytes per MFMA once the batch fills the chip with
   // them (B >= 8192), when the wider tile still fits the LDS (not for tracking's S=51)
   const int rpt = d->rows_per_tile ? d->rows_per_tile
@@ -1431,7 +1396,6 @@ DRPO_API int drpo_rollout(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
                                               persist_lds_bytes(d->S, d->A, d->Ha, d->Hm, 32, 8) <= 160 * 1024
                                           ? 32 : 16);
   DRPO_REQUIRE(rpt == 16 || rpt == 32, "drpo_rollout: rows_per_tile must be 16 or 32");
-  const int S = d->S, A = d->A, S1 = d->S + 1;
   DRPO_REQUIRE(d->engine >= 0 && d->engine <= 2 && (d->eps_layout == 0 || d->eps_layout == 1),
                "drpo_rollout: engine %d / eps_layout %d", d->engine, d->eps_layout);
   DRPO_REQUIRE((d->eps_a == nullptr) == (d->eps_m == nullptr), "drpo_rollout: eps_a and eps_m go together");
@@ -1440,165 +1404,9 @@ DRPO_API int drpo_rollout(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
   if (d->eps_a)
     DRPO_REQUIRE(d->eps_layout == engine - 1, "drpo_rollout: eps_layout %d cannot drive engine %d (compacted draws "
                  "need engine 1, original-row draws engine 2)", d->eps_layout, engine);
-  if (engine == 2) return rollout_fused(d, rpt, rlen, stream);
-
-  RolloutStepArgs a{};
-  a.S = S; a.A = A; a.C = d->C; a.Ha = d->Ha; a.Hm = d->Hm; a.Bmax = d->B;
-  a.env.id = d->env_id; a.env.surr_start = d->tracking_surr_start; a.env.n_surr = d->tracking_n_surr;
-  a.env.thr0 = d->env_thr0; a.env.thr1 = d->env_thr1;
-  a.aW1 = d->aW1; a.ab1 = d->ab1; a.aW2 = d->aW2; a.ab2 = d->ab2; a.aW3 = d->aW3; a.ab3 = d->ab3;
-  a.norm_mean = d->norm_mean; a.norm_std = d->norm_std; a.min_lv = d->min_lv; a.max_lv = d->max_lv;
-  a.replay_states = d->replay_states; a.init_idx = d->init_idx;
-  a.replay_len = rlen; a.replay_ptr = d->replay_ptr; a.replay_cap = d->replay_cap;
-  a.prp_half_bits = hb_for(rlen);
-  for (int i = 0; i < 4; ++i) a.prp_key[i] = (uint32_t)(d->seed >> (8 * i)) * 0x9E3779B9u + (uint32_t)d->ctr * (2 * i + 1) + i;
-  a.seed = d->seed; a.ctr = d->ctr;
-  a.vs = d->vs; a.va = d->va; a.vs2 = d->vs2; a.vr = d->vr; a.vh = d->vh; a.vd = d->vd; a.vv = d->vv;
-  a.vptr = d->vptr; a.vcap = d->vcap;
-  a.n = w.n; a.off = w.off;
-  a.ldx = lds_ld(S + A);
-  a.ldh = lds_ld(d->Ha > d->Hm ? d->Ha : d->Hm);
-  a.ldm = round_up(S1, 16) + 4;
-  a.lds = round_up(S, 4);
-  const bool pg = d->env_id == DRPO_ENV_PROGRAM;
-  a.env_prog = pg ? d->env_program : nullptr;
-
-  const int tiles = (d->B + rpt - 1) / rpt;
-  constexpr int NW = 8;
-  const size_t lds_bytes = sizeof(float) * ((size_t)rpt * (a.ldx + 3 * a.ldh + a.lds + 20 + 2 * a.ldm + 8 + 1 + 8 + 2) +
-                                            (size_t)NW * (rpt / 16) * 256 + NW * 64 + (size_t)tiles + 1 + 256);
-  DRPO_REQUIRE(lds_bytes <= 160 * 1024, "drpo_rollout: LDS %zu too large", lds_bytes);
-
-  const int E_out_in[6][2] = {{d->Hm, S + A}, {d->Hm, d->Hm}, {d->Hm, d->Hm}, {S1, d->Hm}, {d->Hm, d->Hm}, {S1, d->Hm}};
-  const float* Wb[6] = {d->mW1, d->mW2, d->dW1, d->dW2, d->lW1, d->lW2};
-  const float* Bb[6] = {d->mb1, d->mb2, d->db1, d->db2, d->lb1, d->lb2};
-
-  for (int t = 0; t < d->H; ++t) {
-    const int m = d->members[t];
-    const float* Wm[6];
-    const float* Bm[6];
-    for (int i = 0; i < 6; ++i) {
-      // packed mirrors: member stride = drpo_packed_size(in, out)
-      Wm[i] = Wb[i] + (size_t)m * drpo_packed_size(E_out_in[i][1], E_out_in[i][0]);
-      Bm[i] = Bb[i] + (size_t)m * E_out_in[i][0];
-    }
-    a.mW1 = Wm[0]; a.mW2 = Wm[1]; a.dW1 = Wm[2]; a.dW2 = Wm[3]; a.lW1 = Wm[4]; a.lW2 = Wm[5];
-    a.mb1 = Bm[0]; a.mb2 = Bm[1]; a.db1 = Bm[2]; a.db2 = Bm[3]; a.lb1 = Bm[4]; a.lb2 = Bm[5];
-    a.t = t;
-    const int cur = t & 1, prv = cur ^ 1;
-    a.prev_nxt = w.nxt[prv]; a.prev_cnt = w.cnt[prv]; a.prev_inv = w.inv[prv];
-    a.nxt = w.nxt[cur]; a.cnt = w.cnt[cur]; a.inv = w.inv[cur];
-    a.eps_a = d->eps_a ? d->eps_a + (size_t)t * d->B * A : nullptr;
-    a.eps_m = d->eps_m ? d->eps_m + (size_t)t * d->B * S1 : nullptr;
-    if (d->step_events) hipEventRecord((hipEvent_t)d->step_events[2 * t], stream);
-    if (pg) {
-      if (rpt == 32) rollout_step_kernel<2, NW, true><<<tiles, NW * 64, lds_bytes, stream>>>(a);
-      else rollout_step_kernel<1, NW, true><<<tiles, NW * 64, lds_bytes, stream>>>(a);
-    } else if (rpt == 32)
-      rollout_step_kernel<2, NW><<<tiles, NW * 64, lds_bytes, stream>>>(a);
-    else
-      rollout_step_kernel<1, NW><<<tiles, NW * 64, lds_bytes, stream>>>(a);
-    DRPO_LAUNCH_CHECK("rollout_step");
-    if (d->step_events) hipEventRecord((hipEvent_t)d->step_events[2 * t + 1], stream);
-  }
-  rollout_finalize_kernel<<<1, 1, 0, stream>>>(d->vptr, w.n, w.off, d->H);
-  DRPO_LAUNCH_CHECK("rollout_finalize");
-  return DRPO_OK;
-}
-
-// Standalone batched constraint evaluation (tests, evaluation, robust target).
-__global__ void env_constraints_kernel(EnvParams ep, const float* s, int64_t n, int S, int C, uint8_t* done,
-                                       uint8_t* viol, float* h) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  bool dn, vl;
-  float hh[8];
-  env_constraints_row(ep, s + i * S, dn, vl, hh);
-  if (done) done[i] = dn;
-  if (viol) viol[i] = vl;
-  if (h)
-    for (int c = 0; c < C; ++c) h[i * C + c] = hh[c];
-}
-
-DRPO_API int drpo_env_constraints(int env_id, int tracking_surr_start, int tracking_n_surr, double env_thr0,
-                                  double env_thr1, const float* states, int64_t n, int S, uint8_t* done,
-                                  uint8_t* violation, float* h, drpo_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DRPO_REQUIRE(env_id != DRPO_ENV_PROGRAM,
-               "drpo_env_constraints: env id %d is a constraint program: call drpo_env_constraints_program", env_id);
-  DRPO_REQUIRE(env_id >= 0 && env_id <= 3, "drpo_env_constraints: unknown env id %d", env_id);
-  if (n == 0) return DRPO_OK;
-  EnvParams ep{env_id, tracking_surr_start, tracking_n_surr, env_thr0, env_thr1};
-  const int C = env_con_dim(env_id, tracking_n_surr);
-  env_constraints_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(ep, states, n, S, C, done, violation, h);
-  DRPO_LAUNCH_CHECK("env_constraints");
-  return DRPO_OK;
-}
-
-// The same for a constraint program: one thread per row.
-__global__ void env_program_kernel(const void* prog, const float* s, int64_t n, int S, int C, uint8_t* done,
-                                   uint8_t* viol, float* h) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  bool dn, vl;
-  float hh[8];
-  env_program_row(env_program_ptr(prog), s + i * S, dn, vl, hh);
-  if (done) done[i] = dn;
-  if (viol) viol[i] = vl;
-  if (h)
-    for (int c = 0; c < C; ++c) h[i * C + c] = hh[c];
-}
-
-DRPO_API int drpo_env_constraints_program(const drpo_env_program_t* dev_prog, int C, const float* states, int64_t n,
-                                          int S, uint8_t* done, uint8_t* violation, float* h, drpo_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DRPO_REQUIRE(dev_prog && C >= 1 && C <= DRPO_PROG_MAX_ROWS,
-               "drpo_env_constraints_program: needs a device program and 1 <= C (%d) <= %d", C, (int)DRPO_PROG_MAX_ROWS);
-  DRPO_REQUIRE(S >= 1 && S <= 256 && n >= 0, "drpo_env_constraints_program: S=%d n=%lld", S, (long long)n);
-  if (n == 0) return DRPO_OK;
-  DRPO_REQUIRE(states, "drpo_env_constraints_program: null states");
-  env_program_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(dev_prog, states, n, S, C, done, violation, h);
-  DRPO_LAUNCH_CHECK("env_program");
-  return DRPO_OK;
-}
-
-// Host-only validation of a program in host memory (no device needed).
-DRPO_API int drpo_env_program_check(const drpo_env_program_t* q, int S) {
-  DRPO_REQUIRE(q, "drpo_env_program_check: null program");
-  DRPO_REQUIRE(S >= 1 && S <= 256, "drpo_env_program_check: state dim %d out of range (indices are bytes)", S);
-  DRPO_REQUIRE(q->C >= 1 && q->C <= DRPO_PROG_MAX_ROWS, "drpo_env_program_check: %d constraint rows (1..%d)", (int)q->C,
-               (int)DRPO_PROG_MAX_ROWS);
-  for (int c = 0; c < q->C; ++c) {
-    const drpo_env_program_row_t& r = q->rows[c];
-    DRPO_REQUIRE(r.kind == DRPO_PROG_AFFINE || r.kind == DRPO_PROG_BALLS, "drpo_env_program_check: row %d has unknown kind %d",
-                 c, (int)r.kind);
-    int nidx;
-    if (r.kind == DRPO_PROG_AFFINE) {
-      DRPO_REQUIRE(r.n >= 1 && r.n <= DRPO_PROG_MAX_TERMS, "drpo_env_program_check: affine row %d has %d terms (1..%d)", c,
-                   (int)r.n, (int)DRPO_PROG_MAX_TERMS);
-      nidx = r.n;
-    } else {
-      DRPO_REQUIRE(r.n >= 1 && r.n <= DRPO_PROG_MAX_CENTRES, "drpo_env_program_check: balls row %d has %d centres (1..%d)",
-                   c, (int)r.n, (int)DRPO_PROG_MAX_CENTRES);
-      DRPO_REQUIRE(r.nd == 2 || r.nd == 3, "drpo_env_program_check: balls row %d has %d dims (2 or 3)", c, (int)r.nd);
-      nidx = r.nd;
-    }
-    for (int k = 0; k < nidx; ++k)
-      DRPO_REQUIRE(r.dims[k] < S, "drpo_env_program_check: row %d reads state index %d >= state dim %d", c, (int)r.dims[k], S);
-  }
-  DRPO_REQUIRE(q->box_n <= DRPO_PROG_MAX_BOX, "drpo_env_program_check: done box has %d dims (max %d)", (int)q->box_n,
-               (int)DRPO_PROG_MAX_BOX);
-  for (int k = 0; k < q->box_n; ++k)
-    DRPO_REQUIRE(q->box_dims[k] < S, "drpo_env_program_check: done box reads state index %d >= state dim %d",
-                 (int)q->box_dims[k], S);
-  DRPO_REQUIRE(q->ball_nd == 0 || q->ball_nd == 2 || q->ball_nd == 3, "drpo_env_program_check: done ball has %d dims (2 or 3)",
-               (int)q->ball_nd);
-  for (int k = 0; k < q->ball_nd; ++k)
-    DRPO_REQUIRE(q->ball_dims[k] < S, "drpo_env_program_check: done ball reads state index %d >= state dim %d",
-                 (int)q->ball_dims[k], S);
-  DRPO_REQUIRE(q->done_on_violation <= 1, "drpo_env_program_check: done_on_violation %d", (int)q->done_on_violation);
-  DRPO_REQUIRE(q->done_on_violation || q->box_n || q->ball_nd, "drpo_env_program_check: empty done rule");
-  return DRPO_OK;
+  RolloutWs w;
+  rollout_ws(d->B, d->S, d->H, reinterpret_cast<uintptr_t>(d->workspace), w);
+  return engine == 2 ? rollout_fused(d, w, rpt, rlen, stream) : rollout_stepwise(d, w, rpt, rlen, stream);
 }
 
 __global__ void prp_kernel(int64_t* out, int64_t B, int64_t N, int hb, uint32_t k0, uint32_t k1, uint32_t k2,
@@ -1615,7 +1423,7 @@ DRPO_API int drpo_sample_without_replacement(int64_t* out, int64_t B, int64_t N,
   DRPO_REQUIRE(B >= 0 && B <= N && N < (1ll << 62), "drpo_sample_without_replacement: need 0 <= B <= N");
   if (B == 0) return DRPO_OK;
   uint32_t k[4];
-  for (int i = 0; i < 4; ++i) k[i] = (uint32_t)(seed >> (8 * i)) * 0x9E3779B9u + (uint32_t)ctr * (2 * i + 1) + i;
+  prp_keys(seed, ctr, k);
   prp_kernel<<<(unsigned)((B + 255) / 256), 256, 0, stream>>>(out, B, N, hb_for(N), k[0], k[1], k[2], k[3]);
   DRPO_LAUNCH_CHECK("prp");
   return DRPO_OK;

@@ -266,28 +266,37 @@ class _RolloutResult:
 # ---------------------------------------------------------------------------
 # constraints / normalizer
 # ---------------------------------------------------------------------------
-def env_constraints(env_params, states):
-    """Batched (done, violation, constraint_value) on the device; C==1 squeezed like torchify(np.squeeze(...))."""
+def env_constraints(env_params, states, out=None):
+    """Batched (done, violation, constraint_value) on the device; C==1 squeezed like torchify(np.squeeze(...)).
+    out: preallocated contiguous device tensors (done[n], violation[n], h[n, C]) to write instead of new
+    ones; done / violation bool or uint8."""
     L = _lib.lib()
     _lib.require_device(states)
     states = states.contiguous().float()
     n, S = states.shape
     C = env_params['con_dim']
-    done = torch.empty(n, dtype=torch.bool, device=states.device)
-    viol = torch.empty(n, dtype=torch.bool, device=states.device)
-    h = torch.empty(n, C, dtype=torch.float32, device=states.device)
+    if out is None:
+        out = (torch.empty(n, dtype=torch.bool, device=states.device),
+               torch.empty(n, dtype=torch.bool, device=states.device),
+               torch.empty(n, C, dtype=torch.float32, device=states.device))
+    done, viol, h = out
+    _lib.require_device(done, viol, h)
+    assert done.dtype in (torch.bool, torch.uint8) and viol.dtype in (torch.bool, torch.uint8) and \
+        h.dtype == torch.float32, 'env_constraints: out dtypes'
+    assert done.numel() == n and viol.numel() == n and h.numel() == n * C and \
+        done.is_contiguous() and viol.is_contiguous() and h.is_contiguous(), 'env_constraints: out shapes'
     if 'program' in env_params:
         # a user-defined env's constraint program (env id 4): checked against S on its upload
         prog = env_params['program'].device(states.device, S)
         _lib.check(L.drpo_env_constraints_program(_lib.ptr(prog), C, _lib.ptr(states), n, S, _lib.ptr(done),
                                                   _lib.ptr(viol), _lib.ptr(h), _lib.stream()),
                    'env_constraints_program')
-        return done, viol, (h[:, 0] if C == 1 else h)
-    _lib.check(L.drpo_env_constraints(env_params['env_id'], env_params['tracking_surr_start'],
-                                      env_params['tracking_n_surr'], env_params['thr0'],
-                                      env_params['thr1'], _lib.ptr(states), n, S, _lib.ptr(done),
-                                      _lib.ptr(viol), _lib.ptr(h), _lib.stream()), 'env_constraints')
-    return done, viol, (h[:, 0] if C == 1 else h)
+    else:
+        _lib.check(L.drpo_env_constraints(env_params['env_id'], env_params['tracking_surr_start'],
+                                          env_params['tracking_n_surr'], env_params['thr0'],
+                                          env_params['thr1'], _lib.ptr(states), n, S, _lib.ptr(done),
+                                          _lib.ptr(viol), _lib.ptr(h), _lib.stream()), 'env_constraints')
+    return done, viol, (h[:, 0] if C == 1 and h.dim() == 2 else h)
 
 
 def normalizer_fit(X, mean, std):

@@ -22,7 +22,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._abi import (ActorHead, BufferView, CriticHead, MlpBwd, MlpFwd, SumDesc, WgradItem)
 from .optim import ema_segment, fused_step, grad_sumsq_multi
 
@@ -620,20 +620,9 @@ class SACEngine:
                 # (src/ssac.py:389, env.check_done on the model's s')
                 done_h = np.asarray(sol.env.check_done(s2c.detach().cpu().numpy())).reshape(B)
                 dm.copy_(torch.from_numpy(done_h.astype(np.uint8)))
-            elif 'program' in ep:
-                # a user-defined env's constraint program (env id 4)
-                _lib.check(L.drpo_env_constraints_program(ep['program'].device(s2c.device, S).data_ptr(),
-                                                          ep['con_dim'], s2c.data_ptr(), B, S, dm.data_ptr(),
-                                                          self.buf('c.vm', B, dtype=torch.uint8).data_ptr(),
-                                                          self.buf('c.hm', B, ep['con_dim']).data_ptr(),
-                                                          _lib.stream()),
-                           'env_constraints_program')
             else:
-                _lib.check(L.drpo_env_constraints(ep['env_id'], ep['tracking_surr_start'], ep['tracking_n_surr'],
-                                                  ep['thr0'], ep['thr1'], s2c.data_ptr(), B, S,
-                                                  dm.data_ptr(), self.buf('c.vm', B, dtype=torch.uint8).data_ptr(),
-                                                  self.buf('c.hm', B, C).data_ptr(), _lib.stream()),
-                           'env_constraints')
+                ops.env_constraints(ep, s2c, out=(dm, self.buf('c.vm', B, dtype=torch.uint8),
+                                                  self.buf('c.hm', B, ep['con_dim'])))
         xs = self.buf('c.x', B, S + A)
         lp2 = self.buf('c.lp2', B)
         # ONE launch (jobs longest chain first: workgroups dispatch in slot order, so the

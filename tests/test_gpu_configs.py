@@ -123,12 +123,9 @@ def test_config_rollout_vs_oracle(c):
     assert torch.equal(vg[~marginal], vr[~marginal]), f'config {c} violations'
 
 
-@pytest.mark.parametrize('c', CFGS)
-def test_config_rollout_dying_rows_properties(c):
+def _dying_rows_properties(alg, env, B, H):
     """Raw random weights: rows finish at every step. The output must chain: step t+1's
     states are step t's next_states of the rows that did not finish, in order."""
-    alg, cd = _alg(c, seed=7)
-    env, B, H = cd['env'], cd['B'], cd['H']
     _fill(alg, env, 100000, 4)
     m = alg.model_ensemble
     m.state_normalizer.fit(alg.replay_buffer.get('states'))
@@ -159,6 +156,23 @@ def test_config_rollout_dying_rows_properties(c):
     assert torch.equal(dn, got['dones']) and torch.equal(vl, got['violations'])
     assert torch.equal(h, got['constraint_values'])
     assert (got['actions'].abs() <= 1).all() and torch.isfinite(got['next_states']).all()
+
+
+@pytest.mark.parametrize('c', CFGS)
+def test_config_rollout_dying_rows_properties(c):
+    alg, cd = _alg(c, seed=7)
+    _dying_rows_properties(alg, cd['env'], cd['B'], cd['H'])
+
+
+def test_rollout_dying_rows_scan_emit_small():
+    """The scan + emit + finalize tail at its smallest shape: quadrotor, E = 7, B = 4100 in
+    16-row tiles (257 tiles, the last with 4 rows), H = 32: 257 x 32 = 8224 counts, just
+    above the single-launch emit's 8192. Rows die within a few steps, so whole tiles exit
+    early and leave zeroed later counts."""
+    env, B, H = 'quadrotor', 4100, 32
+    torch.manual_seed(7)
+    alg = bench.make_alg(DEV, B, H, 7, 7, bench.ENV_JSON[env], env=env)
+    _dying_rows_properties(alg, env, B, H)
 
 
 def _sac_batch(alg, env, jsn, B, seed):

@@ -17,7 +17,9 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize('tag', ['point-robot', 'quadrotor', 'fullwidth_quad'])
 def test_rollout_matches_reference_fixture(tag):
     """fullwidth_quad: the reference's default widths (actor 256, model 200, E = 7), B = 64,
-    H = 2: the production persist kernel's LDS-resident actor and paired-heads paths."""
+    H = 2 on the per-step engine (the fixtures' compacted tape draws select engine 1); the
+    persist kernel's LDS-resident actor and paired-heads paths run the same fixture in
+    test_fused_engine_matches_reference_fixture_full_width."""
     d = load_golden(f'rollout_{tag}')
     env = str(d['meta/env'])
     alg = small_smbpo(d, env)
