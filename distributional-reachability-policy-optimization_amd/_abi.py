@@ -208,7 +208,7 @@ class CriticHead(ctypes.Structure):
                 ('discount', c_float), ('qc_td_bound', c_float), ('lmin', c_float), ('lmax', c_float),
                 ('log_alpha', P), ('r', P), ('h', P), ('d', P), ('dc', P), ('q0t', P), ('q1t', P), ('logp2', P),
                 ('mu_t', P), ('ls_t', P), ('eps3', P), ('seed', c_uint64), ('ctr', c_uint64),
-                ('q0', P), ('q1', P), ('mu', P), ('ls', P), ('dq0', P), ('dq1', P), ('dmu', P), ('dls', P),
+                ('q0', P), ('q1', P), ('mu', P), ('ls', P),
                 ('loss', P), ('loss_part', P), ('cost', c_int), ('v', P)]
 
 
@@ -248,11 +248,6 @@ PROTOTYPES.update({
                                  P]),
     'drpo_cc_dist': (c_int, [P, P, c_int64, c_int, c_float, c_float, c_float, P, c_uint64, c_uint64, P, P, P]),
     'drpo_cc_head': (c_int, [P, P, c_int64, c_int, c_int, c_float, c_float, c_float, P, P, P]),
-    'drpo_critic_head': (c_int, [POINTER(CriticHead), P]),
-    'drpo_actor_upstream': (c_int, [c_int64, c_int, c_int, c_float, c_float, c_float, P, P, P, P, P, P, P, P, P, P,
-                                    c_float, c_float, c_float, c_float, P]),
-    'drpo_squash_backward': (c_int, [c_int64, c_int, P, P, P, P, P, P, c_float, P, c_float, P, P, P]),
-    'drpo_alpha_grad': (c_int, [P, P, c_int64, P, P]),
     'drpo_multiplier_head': (c_int, [c_int64, P, P, P, c_float, c_float, c_float, c_float, c_float, P, P, P]),
     'drpo_multiplier_out': (c_int, [c_int64, P, c_float, P, P]),
 })

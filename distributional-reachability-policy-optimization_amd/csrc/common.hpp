@@ -188,32 +188,6 @@ __device__ __forceinline__ float normal_at(const float* eps, int64_t idx, uint64
   return j == 0 ? z[0] : (j == 1 ? z[1] : (j == 2 ? z[2] : z[3]));
 }
 
-// squashed-Gaussian head of one row (src/policy.py:88-97; Independent(Tanh(Normal))
-// log_prob at the cached pre-tanh u). mode 0 sample, 1 rsample, 2 mean only.
-// raw = [mu | log-std pre-activation] (2A values, any stride source).
-template <typename RawAt>
-__device__ __forceinline__ void squashed_gaussian_row(RawAt raw_at, int64_t i, int A, int mode, const float* eps,
-                                                      uint64_t seed, uint64_t ctr, uint32_t site, float* a_out,
-                                                      float* logp, float* u_out, float* e_out, float* amean) {
-  float lp = 0.f;
-  for (int d = 0; d < A; ++d) {
-    const float mu = raw_at(d);
-    const float ls = -6.f + 10.f * sigmoidf(raw_at(A + d));
-    const float sd = expf(ls) * 1.0f;
-    if (amean) amean[i * A + d] = tanhf(mu);
-    if (mode == 2) continue;
-    const float e = normal_at(eps, i * A + d, seed, ctr, site);
-    const float u = (mode == 0) ? e * sd + mu : mu + e * sd;
-    if (a_out) a_out[i * A + d] = tanhf(u);
-    if (u_out) u_out[i * A + d] = u;
-    if (e_out) e_out[i * A + d] = e;
-    const float ladj = 2.f * (0.69314718055994531f - u - softplusf(-2.f * u));
-    const float base = -((u - mu) * (u - mu)) / (2.f * (sd * sd)) - logf(sd) - 0.91893853320467274f;
-    lp += (0.f - ladj) + base;
-  }
-  if (logp && mode != 2) logp[i] = lp;
-}
-
 // ---------------------------------------------------------------------------
 // tile_dense: out[r][c] = act(sum_k in[r][k] * W[c][k] + b[c]) for a tile of RB*16
 // rows. `in` / `out` are LDS tiles with row strides ldi / ldo; columns

@@ -1,7 +1,7 @@
-// Per-row math of the safe-SAC critic losses (src/ssac.py:284-435), shared by the
-// stand-alone drpo_critic_head kernel (csrc/sac.hip) and the critic backward launch,
-// which forms its own output gradients from the forward outputs (no separate head
-// launch on the production path, csrc/mlp.hip).
+// Per-row math of the safe-SAC critic losses (src/ssac.py:284-435): the soft Bellman
+// target and the certificate loss element with its gradients. The critic backward launch
+// (csrc/mlp.hip) forms its output gradients from the forward outputs with them; the
+// constraint critic's std map (cc_std) also serves the bound formulas of sac_rows.hpp.
 #pragma once
 #include "common.hpp"
 

@@ -13,7 +13,7 @@
 // (the weight gradients dW = dZ^T Y of every layer run in csrc/wgrad.hip)
 
 #include "common.hpp"
-#include "critic_rows.hpp"
+#include "sac_rows.hpp"
 #include "ens_reduce.hpp"
 
 using namespace drpo;
@@ -27,6 +27,7 @@ constexpr int FW_MAXC = 2;            // 16 column blocks / 8 waves
 constexpr int LDH = 264;              // LDS stride for widths <= 256 (== 8 mod 64)
 constexpr int MAXL = 3;
 constexpr int MAXN = 3;
+constexpr int MJ_MAXSLOT = 16;        // (job, net) slots of a multi-job launch (grid.y)
 
 }  // namespace
 
@@ -181,6 +182,40 @@ static int check_net(const drpo_mlp_net_t& n, int din) {
   return 1;
 }
 
+// What every forward launch requires of a job (the multi launch adds its own rules):
+// 1..3 nets of 1..3 layers, widths <= 256, chained layer widths; a trunk job's heads
+// read the trunk's output.
+static int check_fwd_job(const char* who, int j, const drpo_mlp_fwd_t* a) {
+  DRPO_REQUIRE(a->nnets >= 1 && a->nnets <= MAXN && a->nbatch >= 1, "%s: bad job %d", who, j);
+  const int din0 = a->cols[0] + a->cols[1] + a->cols[2];
+  DRPO_REQUIRE(din0 >= 1 && din0 <= 256, "%s: job %d input width %d", who, j, din0);
+  int din = din0;
+  for (int h = 0; h < a->nnets; ++h) {
+    DRPO_REQUIRE(check_net(a->net[h], din), "%s: job %d bad net %d", who, j, h);
+    if (a->trunk && h == 0) din = a->net[0].L[a->net[0].nl - 1].dout;
+  }
+  return DRPO_OK;
+}
+
+// the (job, net) slots, row tiles and batch depth of a multi-job launch's grid
+struct MultiGrid {
+  int slots = 0, nbatch = 1;
+  int64_t tiles = 0;
+};
+// adds job j's ns slots to the table; false when the table is full
+static bool add_job_slots(MultiGrid& g, unsigned char (&slot_job)[MJ_MAXSLOT], unsigned char (&slot_net)[MJ_MAXSLOT],
+                          int j, int ns, int64_t rows, int nbatch) {
+  if (g.slots + ns > MJ_MAXSLOT) return false;
+  for (int h = 0; h < ns; ++h) {
+    slot_job[g.slots] = (unsigned char)j;
+    slot_net[g.slots] = (unsigned char)h;
+    ++g.slots;
+  }
+  g.tiles = max(g.tiles, (rows + FW_ROWS - 1) / FW_ROWS);
+  g.nbatch = max(g.nbatch, nbatch);
+  return true;
+}
+
 // ---------------------------------------------------------------------------
 // multi-job forward: several independent forwards in one launch
 // ---------------------------------------------------------------------------
@@ -189,9 +224,6 @@ static int check_net(const drpo_mlp_net_t& n, int din) {
 // latency chain of one 16-row tile (stage -> layer -> layer -> ...) is serial, so
 // running e.g. the actor, safe actor, twin critics and constraint critic of one
 // SAC loss in one launch puts 4 such chains on every CU at once.
-namespace {
-constexpr int MJ_MAXSLOT = 16;
-}
 struct MultiArgs {
   const drpo_mlp_fwd_t* jobs;
   unsigned char slot_job[MJ_MAXSLOT], slot_net[MJ_MAXSLOT];
@@ -227,7 +259,8 @@ __device__ __forceinline__ float* run_net_g(const drpo_mlp_net_t& __restrict__ n
 // layers run as ONE paired layer over the trunk output (2N output columns, one
 // k-loop) and both output layers as one split-K narrow pair, so the job's serial
 // chain is 4 layers instead of 6.
-__device__ __forceinline__ bool heads_pairable(const drpo_mlp_fwd_t* __restrict__ a) {
+// (host: the ccb_out check of drpo_mlp_forward_multi)
+__host__ __device__ __forceinline__ bool heads_pairable(const drpo_mlp_fwd_t* __restrict__ a) {
   if (a->nnets != 3) return false;
   const drpo_mlp_net_t& n1 = a->net[1];
   const drpo_mlp_net_t& n2 = a->net[2];
@@ -281,8 +314,8 @@ __device__ __forceinline__ void heads_pair(const drpo_mlp_fwd_t* __restrict__ a,
 }
 
 // The fused squashed-Gaussian head of a policy job (squashed_gaussian_row's arithmetic,
-// src/policy.py:88-97, src/squashed_gaussian.py): one thread per (row, action dim)
-// instead of one per row, on the hardware transcendentals of critic_rows.hpp
+// sac_rows.hpp; src/policy.py:88-97, src/squashed_gaussian.py): one thread per (row,
+// action dim) instead of one per row, on the hardware transcendentals of critic_rows.hpp
 // (~1e-6 relative), log(std) taken as the log-std itself (the
 // reference's log(exp(log_std))); the per-dim log-prob terms are summed per row in
 // dimension order through LDS (lpt). The per-row libm chain it replaces was 5.6-8 k
@@ -299,7 +332,7 @@ __device__ __forceinline__ void squash_head_tile(const float* outp, int row0, in
       const int64_t i = row0 + r, k = i * A + d;
       const float* rrow = outp + r * LDH;
       const float mu = rrow[d];
-      const float ls = -6.f + 10.f * cr_rcp(1.f + cr_exp(-rrow[A + d]));
+      const float ls = pi_log_std_hw(rrow[A + d]);
       const float sd = cr_exp(ls) * 1.0f;
       if (hd.amean) gstore(hd.amean + k, fast_tanh(mu));
       if (mode != 2) {
@@ -371,7 +404,9 @@ __device__ __forceinline__ void pair_nets(const drpo_mlp_net_t& A, const drpo_ml
   else pair_nets_nk<RB, 4>(A, B, rows, in, bA, bB, T, z, row0, nrows, red);
 }
 
-// host-side shape check of a pair job (the kernel's pair_nets assumptions)
+// host-side shape check of a pair job (the kernel's pair_nets assumptions; the kernel
+// trusts the checked `pair` flag). mlp_desc.pairable is its Python twin
+// (tests/test_mlp_desc_checks.py holds the two together).
 static int pair_ok(const drpo_mlp_fwd_t* a) {
   if (a->trunk || a->nnets != 2) return 0;
   const drpo_mlp_net_t &A = a->net[0], &B = a->net[1];
@@ -437,8 +472,11 @@ __global__ __launch_bounds__(FW_NT) __attribute__((amdgpu_waves_per_eu(RB == 1 ?
     heads_pair<RB>(a, t, T, t == bA ? bB : bA, xin, z, row0, nrows, red);
     STAMP(6);
     if (a->ccb_out) {
-      // the constraint critic's upper bound, max over C (drpo_cc_head), from the heads'
-      // outputs in LDS (mean head: xin columns 0.., log-std head: columns 16..)
+      // the constraint critic's upper bound, max over C, from the heads' outputs in LDS
+      // (mean head: xin columns 0.., log-std head: columns 16..). cc_bound_row (sac_rows.hpp)
+      // written out: through the helper this kernel gained 130 instructions
+      // (profiles/sac_refactor/README.md); tests/test_gpu_ccb.py holds the copy to
+      // drpo_cc_head, which calls the helper, bit for bit
       lds_barrier();
       if (tid < nrows) {
         const int C = a->net[1].L[1].dout;
@@ -505,25 +543,12 @@ DRPO_API int drpo_mlp_forward_multi(const drpo_mlp_fwd_t* jobs_host, const drpo_
   m.jobs = jobs_dev;
   m.seed = seed;
   m.ctr = ctr;
-  int slots = 0;
-  int64_t tiles = 0;
-  int nbatch = 1;
+  MultiGrid g;
   for (int j = 0; j < njobs; ++j) {
     const drpo_mlp_fwd_t* a = jobs_host + j;
-    DRPO_REQUIRE(a->nnets >= 1 && a->nnets <= MAXN && a->nbatch >= 1 && !a->split_heads,
-                 "drpo_mlp_forward_multi: bad job %d", j);
-    const int din0 = a->cols[0] + a->cols[1] + a->cols[2];
-    DRPO_REQUIRE(din0 >= 1 && din0 <= 256, "drpo_mlp_forward_multi: job %d input width %d", j, din0);
-    if (a->trunk) {
-      DRPO_REQUIRE(check_net(a->net[0], din0), "drpo_mlp_forward_multi: job %d bad trunk", j);
-      const int tw = a->net[0].L[a->net[0].nl - 1].dout;
-      for (int h = 1; h < a->nnets; ++h)
-        DRPO_REQUIRE(check_net(a->net[h], tw), "drpo_mlp_forward_multi: job %d bad head %d", j, h);
-      DRPO_REQUIRE(a->head.mode == 0, "drpo_mlp_forward_multi: policy head on a trunk job");
-    } else {
-      for (int h = 0; h < a->nnets; ++h)
-        DRPO_REQUIRE(check_net(a->net[h], din0), "drpo_mlp_forward_multi: job %d bad net %d", j, h);
-    }
+    if (const int e = check_fwd_job("drpo_mlp_forward_multi", j, a)) return e;
+    DRPO_REQUIRE(!a->split_heads, "drpo_mlp_forward_multi: job %d: split_heads is a single-launch mode", j);
+    DRPO_REQUIRE(!a->trunk || a->head.mode == 0, "drpo_mlp_forward_multi: policy head on a trunk job");
     if (a->head.mode != 0)
       DRPO_REQUIRE(a->head.mode <= 3 && a->head.A >= 1 && a->head.A <= 8 &&
                        2 * a->head.A == a->net[0].L[a->net[0].nl - 1].dout,
@@ -546,13 +571,9 @@ DRPO_API int drpo_mlp_forward_multi(const drpo_mlp_fwd_t* jobs_host, const drpo_
                    "drpo_mlp_forward_multi: job %d: a chain needs a policy net on the src[0] columns whose sampled "
                    "action is the src[1] block (no input save / normalizer)", j);
     }
-    if (a->ccb_out) {   // the same conditions as heads_pairable (device side)
-      const drpo_mlp_net_t &n1 = a->net[1], &n2 = a->net[2];
-      DRPO_REQUIRE(a->trunk && a->nnets == 3 && n1.nl == 2 && n2.nl == 2 && n1.L[0].din == 256 &&
-                       n2.L[0].din == 256 && n1.L[0].dout == n2.L[0].dout && n1.L[0].act == n2.L[0].act &&
-                       n1.L[1].act == n2.L[1].act && n1.L[1].dout <= 16 && n2.L[1].dout <= 16,
+    if (a->ccb_out)
+      DRPO_REQUIRE(a->trunk && heads_pairable(a),
                    "drpo_mlp_forward_multi: job %d: the constraint bound needs a trunk job with paired heads", j);
-    }
     if (a->post.nl > 0) {
       const drpo_mlp_net_t& pn = a->post;
       DRPO_REQUIRE(a->ccb_out && a->cols[0] + 1 <= 64 && check_net(pn, a->cols[0] + 1) && !a->nmean,
@@ -561,16 +582,11 @@ DRPO_API int drpo_mlp_forward_multi(const drpo_mlp_fwd_t* jobs_host, const drpo_
     } else {
       DRPO_REQUIRE(!a->post_x, "drpo_mlp_forward_multi: job %d: post_x without a post net", j);
     }
-    const int ns = (a->trunk || a->pair) ? 1 : a->nnets;
-    DRPO_REQUIRE(slots + ns <= MJ_MAXSLOT, "drpo_mlp_forward_multi: too many nets");
-    for (int h = 0; h < ns; ++h) {
-      m.slot_job[slots] = (unsigned char)j;
-      m.slot_net[slots] = (unsigned char)h;
-      ++slots;
-    }
-    tiles = max(tiles, (a->rows + FW_ROWS - 1) / FW_ROWS);
-    nbatch = max(nbatch, a->nbatch);
+    DRPO_REQUIRE(add_job_slots(g, m.slot_job, m.slot_net, j, (a->trunk || a->pair) ? 1 : a->nnets, a->rows, a->nbatch),
+                 "drpo_mlp_forward_multi: too many nets");
   }
+  const int slots = g.slots, nbatch = g.nbatch;
+  const int64_t tiles = g.tiles;
   if (tiles == 0) return DRPO_OK;
   // 32-row tiles halve the weight bytes per MFMA but allow only one 8-wave workgroup
   // per CU (LDS); measured slower at B=4096 (profiles/r01, profiles/r04/bench_stats), so
@@ -588,16 +604,11 @@ DRPO_API int drpo_mlp_forward_multi(const drpo_mlp_fwd_t* jobs_host, const drpo_
 
 DRPO_API int drpo_mlp_forward(const drpo_mlp_fwd_t* a, drpo_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  DRPO_REQUIRE(a && a->nnets >= 1 && a->nnets <= MAXN && a->nbatch >= 1, "drpo_mlp_forward: bad descriptor");
-  const int din0 = a->cols[0] + a->cols[1] + a->cols[2];
-  DRPO_REQUIRE(din0 >= 1 && din0 <= 256, "drpo_mlp_forward: input width %d", din0);
-  if (a->trunk) {
-    DRPO_REQUIRE(check_net(a->net[0], din0), "drpo_mlp_forward: bad trunk");
-    const int tw = a->net[0].L[a->net[0].nl - 1].dout;
-    for (int h = 1; h < a->nnets; ++h) DRPO_REQUIRE(check_net(a->net[h], tw), "drpo_mlp_forward: bad head %d", h);
-  } else {
-    for (int h = 0; h < a->nnets; ++h) DRPO_REQUIRE(check_net(a->net[h], din0), "drpo_mlp_forward: bad net %d", h);
-  }
+  DRPO_REQUIRE(a, "drpo_mlp_forward: null descriptor");
+  if (const int e = check_fwd_job("drpo_mlp_forward", 0, a)) return e;
+  // the single-job kernel evaluates none of these: refuse them instead of ignoring them
+  DRPO_REQUIRE(!a->head.mode && !a->head2.mode && !a->pair && !a->pre.nl && !a->post.nl && !a->post_x && !a->ccb_out,
+               "drpo_mlp_forward: head, head2, pair, pre, post, post_x and ccb_out need drpo_mlp_forward_multi");
   if (a->rows == 0) return DRPO_OK;
   DRPO_REQUIRE(!a->split_heads || (a->trunk && a->nnets >= 2), "drpo_mlp_forward: split_heads needs a trunk + heads");
   dim3 grid((unsigned)((a->rows + FW_ROWS - 1) / FW_ROWS),
@@ -695,7 +706,8 @@ __device__ __forceinline__ float* bwd_net(const drpo_mlp_bwd_net_t& __restrict__
 // two-input pair layer), and the trunk-output gradient -- the sum of the two heads'
 // hidden-layer products -- is ONE product with the concatenated K (dZ_1 | dZ_2) x
 // [W_1; W_2]: three dependent GEMM phases instead of five, and no LDS accumulation.
-__device__ __forceinline__ bool bwd_paired_heads(const drpo_mlp_bwd_t& a) {
+// (host: drpo_mlp_backward_ens checks its heads with it)
+__host__ __device__ __forceinline__ bool bwd_paired_heads(const drpo_mlp_bwd_t& a) {
   if (!a.trunk || a.split_heads || a.nnets != 3) return false;
   const drpo_mlp_bwd_net_t &h1 = a.net[1], &h2 = a.net[2];
   if (h1.nl != 2 || h2.nl != 2 || h1.dx || h2.dx) return false;
@@ -853,11 +865,13 @@ __device__ __forceinline__ void ens_upstream(EnsUpK& u, const drpo_mlp_bwd_net_t
 typedef const __attribute__((address_space(4))) drpo_actor_head_t ActorHeadK;
 
 // DRPO_UPSTREAM_ACTOR_CC / _SAFE_CC: the actor losses' gradient w.r.t. the constraint
-// critic's mean / raw log-std heads at (s, a) or (s, a_safe) (drpo_actor_upstream's
-// arithmetic, csrc/sac.hip; src/ssac.py:474-494): weight lam / B (actor) or 1 / B
-// (safe actor) on the arg-max constraint of the quantile bound mu + ratio * std; the
-// head outputs are the forward's saves (hm / hl last-layer sy). Gm / Gl (LDS) + the
-// output layers' saved dZ.
+// critic's mean / raw log-std heads at (s, a) or (s, a_safe) (src/ssac.py:474-494):
+// weight lam / B (actor) or 1 / B (safe actor) on the arg-max constraint of the quantile
+// bound mu + ratio * std (cc_bound_row), and through std to that constraint's raw
+// log-std; lam is the MLPMultiplier's transformed output (src/ssac.py:107-111) or the
+// scalar multiplier, which has no gradient where clamp(Qc, lb, ub) saturates
+// (src/ssac.py:480-484). The head outputs are the forward's saves (hm / hl last-layer
+// sy). Gm / Gl (LDS) + the output layers' saved dZ.
 __device__ __forceinline__ void actor_cc_upstream(ActorHeadK& h, int side, const drpo_mlp_bwd_net_t& hm,
                                                   const drpo_mlp_bwd_net_t* hl, float* Gm, float* Gl, int row0,
                                                   int nrows) {
@@ -871,6 +885,9 @@ __device__ __forceinline__ void actor_cc_upstream(ActorHeadK& h, int side, const
     float gm = 0.f, gs = 0.f;
     if (r < nrows && k < C) {
       const int64_t i = row0 + r;
+      // cc_bound_row (sac_rows.hpp), written out: through the helper this kernel's register
+      // allocation changed (one SGPR spill fewer, profiles/sac_refactor/README.md), and a
+      // refactor keeps every kernel's shape
       float best = 0.f, lbest = 0.f;
       int bi = 0;
       for (int c = 0; c < C; ++c) {
@@ -883,7 +900,7 @@ __device__ __forceinline__ void actor_cc_upstream(ActorHeadK& h, int side, const
       if (side == 0) {
         float lam = h.lams ? gload(h.lams + i) : h.fixed_lam;
         const float ub = h.lam_upper_bound;
-        if (h.lams && ub > 0.f) lam = ub / 2.f * (1.f + tanhf(lam / ub * 2.f));   // MLPMultiplier.forward
+        if (h.lams && ub > 0.f) lam = multiplier_lam(lam, ub);
         if (!h.lams && (best < h.clamp_lb || best > h.clamp_ub)) lam = 0.f;       // clamped scalar-lam term
         g = lam * invB;
       }
@@ -904,9 +921,12 @@ __device__ __forceinline__ void actor_cc_upstream(ActorHeadK& h, int side, const
 }
 
 // DRPO_UPSTREAM_SQUASH / _SQUASH_SAFE: the chain rule through rsample + tanh + log_prob
-// of the squashed Gaussian (drpo_squash_backward's arithmetic, csrc/sac.hip;
-// src/policy.py:89-97, src/ssac.py:458-505) to the net's raw [mu | log-std] outputs
-// (the forward's save), and the alpha-loss sum for the actor
+// of the squashed Gaussian (src/policy.py:89-97, src/ssac.py:458-505) to the net's raw
+// [mu | log-std] outputs (the forward's save): with u = mu + e * std, a = tanh(u),
+// dL/du = dA (1 - a^2) + glp d logp/du, dL/dmu = dL/du + glp (u - mu) / var,
+// dL/dstd = dL/du e + glp ((u - mu)^2 / std^3 - 1 / std), then pi_dstd_draw to the raw
+// log-std; glp = exp(log_alpha) * lp_scale is the actor's dL/d logp (0 for the safe
+// actor). The actor's tiles also leave sum(logp + target_entropy) for the alpha loss.
 __device__ __forceinline__ void squash_upstream(ActorHeadK& h, int side, const drpo_mlp_bwd_net_t& n, float* G,
                                                 int row0, int nrows) {
   const int A = h.A;
@@ -927,7 +947,7 @@ __device__ __forceinline__ void squash_upstream(ActorHeadK& h, int side, const d
       const float uu = gload(u + i * A + d), ee = gload(ep + i * A + d);
       const float dAv = dA2 ? gload(dA + i * A + d) + gload(dA2 + i * A + d) : gload(dA + i * A + d);
       const float sg = sigmoidf(rr);
-      const float sd = expf(-6.f + 10.f * sg) * 1.0f;
+      const float sd = expf(pi_log_std_of(sg)) * 1.0f;
       const float a = tanhf(uu);
       const float diff = uu - mu;
       const float var = sd * sd;
@@ -936,7 +956,7 @@ __device__ __forceinline__ void squash_upstream(ActorHeadK& h, int side, const d
         gv = du + glp * diff / var;
       } else {
         const float dsd = du * ee + glp * (diff * diff / (var * sd) - 1.f / sd);
-        gv = dsd * sd * 10.f * sg * (1.f - sg);
+        gv = pi_dstd_draw(dsd, sd, sg);
       }
       if (side == 0 && h.alpha_sum && k == 0) asum = gload(h.logp + i) + h.target_entropy;
     }
@@ -1197,7 +1217,7 @@ __global__ __launch_bounds__(FW_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 
 struct BwdMultiArgs {
   const drpo_mlp_bwd_t* jobs;
-  unsigned char slot_job[16], slot_net[16];
+  unsigned char slot_job[MJ_MAXSLOT], slot_net[MJ_MAXSLOT];
   int has_head, has_actor;
   drpo_critic_head_t head;
   drpo_actor_head_t actor;
@@ -1218,25 +1238,43 @@ __global__ __launch_bounds__(FW_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 
 static size_t bwd_lds() { return sizeof(float) * (size_t)4 * FW_ROWS * LDH; }
 
-DRPO_API int drpo_mlp_backward(const drpo_mlp_bwd_t* a, drpo_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DRPO_REQUIRE(a && a->nnets >= 1 && a->nnets <= MAXN && a->nbatch >= 1, "drpo_mlp_backward: bad descriptor");
+// split heads: each head's workgroup backs its share of the trunk gradient through the
+// trunk, so there is no trunk input gradient, and with two heads every saved trunk dZ
+// leaves as dz + dz2
+static int split_trunk_ok(const drpo_mlp_bwd_t* a) {
+  if (!a->trunk || a->nnets < 2 || a->net[0].dx) return 0;
+  for (int l = 0; l < a->net[0].nl; ++l)
+    if (a->nnets == 3 && !a->net[0].L[l].dz != !a->net[0].L[l].dz2) return 0;
+  return 1;
+}
+
+// What every backward launch requires of a job. gout is read only for a net whose output
+// gradient comes from memory (DRPO_UPSTREAM_GOUT; a trunk's comes from its heads).
+static int check_bwd(const char* who, int j, const drpo_mlp_bwd_t* a) {
+  DRPO_REQUIRE(a->nnets >= 1 && a->nnets <= MAXN && a->nbatch >= 1, "%s: bad job %d", who, j);
   for (int h = 0; h < a->nnets; ++h) {
     const drpo_mlp_bwd_net_t& n = a->net[h];
-    DRPO_REQUIRE(n.nl >= 1 && n.nl <= MAXL && n.gout || (a->trunk && h == 0 && n.nl >= 1),
-                 "drpo_mlp_backward: bad net %d", h);
+    DRPO_REQUIRE(n.nl >= 1 && n.nl <= MAXL, "%s: job %d: net %d has %d layers (1..%d)", who, j, h, n.nl, MAXL);
+    const bool reads_gout = a->upstream == DRPO_UPSTREAM_GOUT && !(a->trunk && h == 0);
+    DRPO_REQUIRE(n.gout || !reads_gout, "%s: job %d: net %d needs gout (upstream DRPO_UPSTREAM_GOUT)", who, j, h);
     for (int l = 0; l < n.nl; ++l)
       DRPO_REQUIRE(n.L[l].din >= 1 && n.L[l].din <= 256 && n.L[l].dout >= 1 && n.L[l].dout <= 256 && n.L[l].W,
-                   "drpo_mlp_backward: bad layer %d of net %d", l, h);
-    if (n.dx) DRPO_REQUIRE(n.dx_col0 >= 0 && n.dx_col0 + n.dx_cols <= n.L[0].din, "drpo_mlp_backward: dx columns");
+                   "%s: job %d: bad layer %d of net %d", who, j, l, h);
+    if (n.dx)
+      DRPO_REQUIRE(n.dx_col0 >= 0 && n.dx_col0 + n.dx_cols <= n.L[0].din, "%s: job %d: dx columns of net %d", who, j, h);
   }
-  if (a->split_heads) {
-    DRPO_REQUIRE(a->trunk && a->nnets >= 2 && a->nnets <= 3 && !a->net[0].dx,
-                 "drpo_mlp_backward: split_heads needs a trunk, 1-2 heads and no trunk input gradient");
-    for (int l = 0; l < a->net[0].nl; ++l)
-      DRPO_REQUIRE(a->nnets < 3 || !a->net[0].L[l].dz == !a->net[0].L[l].dz2,
-                   "drpo_mlp_backward: split_heads trunk layer %d needs dz2 with dz", l);
-  }
+  if (a->split_heads)
+    DRPO_REQUIRE(split_trunk_ok(a), "%s: job %d: split_heads needs a trunk with 1-2 heads, no trunk input gradient "
+                                    "and dz2 with every trunk dz", who, j);
+  return DRPO_OK;
+}
+
+DRPO_API int drpo_mlp_backward(const drpo_mlp_bwd_t* a, drpo_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  DRPO_REQUIRE(a, "drpo_mlp_backward: null descriptor");
+  if (const int e = check_bwd("drpo_mlp_backward", 0, a)) return e;
+  DRPO_REQUIRE(a->upstream == DRPO_UPSTREAM_GOUT,
+               "drpo_mlp_backward: upstream %d needs the launch that carries its head (gout only here)", a->upstream);
   if (a->rows == 0) return DRPO_OK;
   dim3 grid((unsigned)((a->rows + FW_ROWS - 1) / FW_ROWS),
             a->trunk ? (a->split_heads ? a->nnets - 1 : 1) : a->nnets, a->nbatch);
@@ -1250,27 +1288,19 @@ DRPO_API int drpo_mlp_backward_ens(const drpo_mlp_bwd_t* a, const drpo_ens_upstr
                                    drpo_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   DRPO_REQUIRE(a && up && red_in && reduce_out, "drpo_mlp_backward_ens: null argument");
+  if (const int e = check_bwd("drpo_mlp_backward_ens", 0, a)) return e;
   DRPO_REQUIRE(a->upstream == DRPO_UPSTREAM_ENS && a->trunk && a->nnets == 3 && a->nbatch == up->Z &&
                    a->rows == up->b,
                "drpo_mlp_backward_ens: the descriptor must be the ensemble trunk + two heads with upstream ENS");
-  if (a->split_heads) {   // one workgroup per (row tile, head): the trunk dZ leaves as dz + dz2
-    DRPO_REQUIRE(!a->net[0].dx, "drpo_mlp_backward_ens: split heads and a trunk input gradient");
-    for (int l = 0; l < a->net[0].nl; ++l)
-      DRPO_REQUIRE(!a->net[0].L[l].dz == !a->net[0].L[l].dz2,
-                   "drpo_mlp_backward_ens: split heads: trunk layer %d needs dz2 with dz", l);
-  }
-  const drpo_mlp_bwd_net_t &h1 = a->net[1], &h2 = a->net[2];
-  DRPO_REQUIRE(h1.nl == 2 && h2.nl == 2 && h1.L[1].dout == up->S + 1 && h2.L[1].dout == up->S + 1 &&
-                   up->S + 1 <= 64 && h1.L[1].act == ACT_NONE && h2.L[1].act == ACT_NONE &&
-                   (h1.L[0].dout == 200 || h1.L[0].dout == 256) && h1.L[0].dout == h2.L[0].dout &&
-                   h1.L[0].act == h2.L[0].act && !h1.dx && !h2.dx,
+  // the NLL upstream assumes the paired head shape, also when each head then runs in a
+  // workgroup of its own (split_heads)
+  drpo_mlp_bwd_t shape = *a;
+  shape.split_heads = 0;
+  DRPO_REQUIRE(bwd_paired_heads(shape) && a->net[1].L[1].dout == up->S + 1,
                "drpo_mlp_backward_ens: heads must be paired [H -> 200|256 -> S+1] (S+1 <= 64)");
   DRPO_REQUIRE(up->D && up->LVR && up->s && up->t && up->minlv && up->maxlv && up->part && up->b >= 1 &&
                    up->Z >= 1 && up->Z <= 256,
                "drpo_mlp_backward_ens: bad upstream");
-  for (int l = 0; l < a->net[0].nl; ++l)
-    DRPO_REQUIRE(a->net[0].L[l].din <= 256 && a->net[0].L[l].dout <= 256 && a->net[0].L[l].W,
-                 "drpo_mlp_backward_ens: bad trunk layer %d", l);
   const int nbx = (int)((up->b + FW_ROWS - 1) / FW_ROWS);
   *reduce_out = *red_in;
   reduce_out->part = up->part;
@@ -1285,18 +1315,6 @@ DRPO_API int drpo_mlp_backward_ens(const drpo_mlp_bwd_t* a, const drpo_ens_upstr
   mlp_bwd_ens_kernel<<<grid, FW_NT, bwd_lds(), stream>>>(m);
   DRPO_LAUNCH_CHECK("mlp_backward_ens");
   return DRPO_OK;
-}
-
-static int check_bwd(const drpo_mlp_bwd_t* a) {
-  if (!(a && a->nnets >= 1 && a->nnets <= MAXN && a->nbatch >= 1 && !a->split_heads)) return 0;
-  for (int h = 0; h < a->nnets; ++h) {
-    const drpo_mlp_bwd_net_t& n = a->net[h];
-    if (!(n.nl >= 1 && n.nl <= MAXL && (n.gout || (a->trunk && h == 0)))) return 0;
-    for (int l = 0; l < n.nl; ++l)
-      if (!(n.L[l].din >= 1 && n.L[l].din <= 256 && n.L[l].dout >= 1 && n.L[l].dout <= 256 && n.L[l].W)) return 0;
-    if (n.dx && !(n.dx_col0 >= 0 && n.dx_col0 + n.dx_cols <= n.L[0].din)) return 0;
-  }
-  return 1;
 }
 
 DRPO_API int drpo_mlp_backward_multi(const drpo_mlp_bwd_t* jobs_host, const drpo_mlp_bwd_t* jobs_dev, int njobs,
@@ -1335,8 +1353,13 @@ static int bwd_multi_launch(const drpo_mlp_bwd_t* jobs_host, const drpo_mlp_bwd_
     m.has_head = 1;
     m.head = *head;
   }
+  MultiGrid g;
   for (int j = 0; j < njobs; ++j) {
     const drpo_mlp_bwd_t& J = jobs_host[j];
+    if (const int e = check_bwd("drpo_mlp_backward_multi", j, &J)) return e;
+    DRPO_REQUIRE(!J.split_heads, "drpo_mlp_backward_multi: job %d: split_heads is a single-launch mode", j);
+    DRPO_REQUIRE(add_job_slots(g, m.slot_job, m.slot_net, j, J.trunk ? 1 : J.nnets, J.rows, J.nbatch),
+                 "drpo_mlp_backward_multi: too many nets");
     DRPO_REQUIRE(J.upstream >= DRPO_UPSTREAM_GOUT && J.upstream <= DRPO_UPSTREAM_SQUASH_SAFE &&
                      J.upstream != DRPO_UPSTREAM_ENS,
                  "drpo_mlp_backward_multi: job %d upstream %d", j, J.upstream);
@@ -1372,23 +1395,8 @@ static int bwd_multi_launch(const drpo_mlp_bwd_t* jobs_host, const drpo_mlp_bwd_
                        (J.nnets == 2 || (head->distributional && J.net[2].L[J.net[2].nl - 1].dout == head->C)),
                    "drpo_mlp_backward_multi: certificate-upstream job %d must be the constraint critic", j);
   }
-  int slots = 0, nbatch = 1;
-  int64_t tiles = 0;
-  for (int j = 0; j < njobs; ++j) {
-    const drpo_mlp_bwd_t* a = jobs_host + j;
-    DRPO_REQUIRE(check_bwd(a), "drpo_mlp_backward_multi: bad job %d", j);
-    const int ns = a->trunk ? 1 : a->nnets;
-    DRPO_REQUIRE(slots + ns <= 16, "drpo_mlp_backward_multi: too many nets");
-    for (int h = 0; h < ns; ++h) {
-      m.slot_job[slots] = (unsigned char)j;
-      m.slot_net[slots] = (unsigned char)h;
-      ++slots;
-    }
-    tiles = max(tiles, (a->rows + FW_ROWS - 1) / FW_ROWS);
-    nbatch = max(nbatch, a->nbatch);
-  }
-  if (tiles == 0) return DRPO_OK;
-  const dim3 grid((unsigned)tiles, slots, nbatch);
+  if (g.tiles == 0) return DRPO_OK;
+  const dim3 grid((unsigned)g.tiles, g.slots, g.nbatch);
   if (m.has_head)
     mlp_bwd_multi_kernel<UPF_CRITIC><<<grid, FW_NT, bwd_lds(), stream>>>(m);
   else if (m.has_actor)

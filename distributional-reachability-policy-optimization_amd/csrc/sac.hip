@@ -7,19 +7,17 @@
 //                         (src/policy.py:89-97, torch TanhTransform / Normal)
 //  drpo_cc_head           constraint-critic log-std soft clamp, quantile upper bound
 //                         mu + std_ratio*std and its max over C (src/ssac.py:64-92,588-600)
-//  drpo_critic_head       soft Bellman target, reachability-certificate backup
-//                         (distributional or vanilla), both critic losses and their
-//                         gradients w.r.t. the critic outputs (src/ssac.py:284-435)
-//  drpo_actor_upstream    dL/d(critic / constraint-critic outputs) of the actor and
-//                         safe-actor losses (src/ssac.py:458-505)
-//  drpo_squash_backward   chain rule through rsample + tanh + log_prob to the actor
-//                         head (mu, raw log-std), plus the alpha-loss sum
+//  drpo_cc_dist           ConstraintCritic.forward's per-constraint outputs (src/ssac.py:75-92)
 //  drpo_multiplier_head   Lagrangian multiplier loss gradient (src/ssac.py:529-568)
-//  drpo_alpha_grad        d alpha_loss / d log_alpha (src/ssac.py:498-501)
-// Losses are accumulated (already scaled) with float atomics into caller-zeroed
-// device scalars, so no host synchronisation is needed.
+//  drpo_multiplier_out    MLPMultiplier.forward output transform (src/ssac.py:107-111)
+// The critic / certificate losses, the actor losses' output gradients, the
+// squashed-Gaussian backward and the alpha gradient have no launch of their own: the
+// backward launches of mlp.hip and drpo_optim_step form them (row formulas shared with
+// these kernels: sac_rows.hpp, critic_rows.hpp).
+// drpo_multiplier_head accumulates its (already scaled) loss with a float atomic into a
+// caller-zeroed device scalar, so no host synchronisation is needed.
 #include "common.hpp"
-#include "critic_rows.hpp"
+#include "sac_rows.hpp"
 
 using namespace drpo;
 
@@ -119,7 +117,7 @@ __global__ void policy_head_kernel(const float* raw, int64_t B, int A, int mode,
   if (mode == 3) {   // distribution parameters (loc, scale) for distr()
     for (int d = 0; d < A; ++d) {
       const float mu = r[d];
-      const float sd = expf(-6.f + 10.f * sigmoidf(r[A + d])) * 1.0f;
+      const float sd = expf(pi_log_std(r[A + d])) * 1.0f;
       if (amean) amean[i * A + d] = tanhf(mu);
       if (u_out) u_out[i * A + d] = mu;
       if (e_out) e_out[i * A + d] = sd;
@@ -149,15 +147,10 @@ __global__ void cc_head_kernel(const float* mu, const float* lsraw, int64_t B, i
                                float lmax, float* ubmax, int* argmax) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
-  float best = 0.f;
-  int bi = 0;
-  for (int c = 0; c < C; ++c) {
-    float v = mu[i * C + c];
-    if (dist) v = v + ratio * cc_std(lsraw[i * C + c], lmin, lmax);
-    if (c == 0 || v > best) { best = v; bi = c; }
-  }
-  if (ubmax) ubmax[i] = best;
-  if (argmax) argmax[i] = bi;
+  const CcBound b = cc_bound_row([&](int c) { return mu[i * C + c]; }, [&](int c) { return lsraw[i * C + c]; }, C,
+                                 dist, ratio, lmin, lmax);
+  if (ubmax) ubmax[i] = b.best;
+  if (argmax) argmax[i] = b.arg;
 }
 
 DRPO_API int drpo_cc_head(const float* mu, const float* lsraw, int64_t B, int C, int distributional, float std_ratio,
@@ -201,202 +194,10 @@ DRPO_API int drpo_cc_dist(const float* mu, const float* lsraw, int64_t n, int mo
 }
 
 // ---------------------------------------------------------------------------
-// critic + certificate targets, losses, gradients (update_critic)
-// ---------------------------------------------------------------------------
-
-__global__ __launch_bounds__(256) void critic_head_kernel(drpo_critic_head_t p) {
-  __shared__ float red[8];
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  float lq = 0.f, lc = 0.f;
-  if (i < p.B) {
-    const float y = critic_target(p, i, expf(*p.log_alpha));
-    const float e0 = p.q0[i] - y, e1 = p.q1[i] - y;
-    const float invB = 1.f / (float)p.B;
-    lq = (e0 * e0 + e1 * e1) * (0.5f * invB);
-    for (int c = 0; c < p.C; ++c) {
-      float dmu, dls;
-      lc += cert_element(p, i, c, dmu, dls);
-      p.dmu[i * p.C + c] = dmu;
-      if (p.dls) p.dls[i * p.C + c] = dls;
-    }
-    // the critic gradients are stored after the certificate loop: a store ahead of
-    // the loop's loads would cost the row a second memory latency
-    p.dq0[i] = e0 * invB;
-    p.dq1[i] = e1 * invB;
-  }
-  const float s0 = block_sum(lq, red);
-  const float s1 = block_sum(lc, red);
-  if (threadIdx.x == 0) {
-    atomicAdd(&p.loss[0], s0);
-    atomicAdd(&p.loss[1], s1);
-  }
-}
-
-DRPO_API int drpo_critic_head(const drpo_critic_head_t* p, drpo_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DRPO_REQUIRE(p && p->C >= 1 && p->B >= 0, "drpo_critic_head: bad descriptor");
-  DRPO_REQUIRE(!p->cost || (p->v && !p->distributional), "drpo_critic_head: cost target needs v, not distributional");
-  if (p->B == 0) return DRPO_OK;
-  critic_head_kernel<<<(unsigned)((p->B + 63) / 64), 64, 0, stream>>>(*p);
-  DRPO_LAUNCH_CHECK("critic_head");
-  return DRPO_OK;
-}
-
-// ---------------------------------------------------------------------------
-// actor / safe-actor upstream gradients (update_actor_and_alpha)
-// ---------------------------------------------------------------------------
-// For the actor loss mean(alpha*logp - Q_k) + mean(lam * max_C ub(s,a)) and the safe
-// actor loss mean(max_C ub(s, a_safe)): gradients w.r.t. Q_k (-1/B), and w.r.t. the
-// mean / raw-log-std heads of the constraint critic at (s,a) and (s,a_safe).
-__global__ void actor_upstream_kernel(int64_t B, int C, int dist, float ratio, float lmin, float lmax,
-                                      const float* lams, const float* mu_a, const float* ls_a, const float* mu_s,
-                                      const float* ls_s, float* gq, float* gmu_a, float* gls_a, float* gmu_s,
-                                      float* gls_s, float ub, float fixed_lam, float clb, float cub) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  const float invB = 1.f / (float)B;
-  // pass 1, loads only: the arg-max constraint of each side and its raw log-std (both
-  // sides' loads are in flight together; no store sits between them)
-  int bis[2] = {0, 0};
-  float lsb[2] = {0.f, 0.f}, best_a = 0.f;
-  float lam = gmu_a ? (lams ? lams[i] : fixed_lam) : 0.f;
-  if (lams && ub > 0.f) lam = ub / 2.f * (1.f + tanhf(lam / ub * 2.f));   // MLPMultiplier.forward transform
-#pragma unroll
-  for (int side = 0; side < 2; ++side) {
-    const float* mu = side ? mu_s : mu_a;
-    const float* ls = side ? ls_s : ls_a;
-    if (!(side ? gmu_s : gmu_a)) continue;
-    float best = 0.f, lbest = 0.f;
-    int bi = 0;
-    for (int c = 0; c < C; ++c) {
-      float v = mu[i * C + c];
-      const float l = dist ? ls[i * C + c] : 0.f;
-      if (dist) v = v + ratio * cc_std(l, lmin, lmax);
-      if (c == 0 || v > best) { best = v; bi = c; lbest = l; }
-    }
-    bis[side] = bi;
-    lsb[side] = lbest;
-    if (!side) best_a = best;
-  }
-  // scalar multiplier: the certificate term is clamp(Qc, lb, ub) -- no gradient outside
-  if (!lams && (best_a < clb || best_a > cub)) lam = 0.f;
-  // pass 2, stores
-  if (gq) gq[i] = -invB;
-#pragma unroll
-  for (int side = 0; side < 2; ++side) {
-    float* gmu = side ? gmu_s : gmu_a;
-    float* gls = side ? gls_s : gls_a;
-    if (!gmu) continue;
-    const float g = side ? invB : lam * invB;
-    float gl = 0.f;
-    if (dist && g != 0.f) {
-      const float sd = cc_std(lsb[side], lmin, lmax);
-      gl = g * ratio * cc_dstd_draw(lsb[side], lmin, lmax, sd);
-    }
-    for (int c = 0; c < C; ++c) {
-      const int64_t k = i * C + c;
-      const bool hit = c == bis[side];
-      gmu[k] = hit ? g : 0.f;
-      if (gls) gls[k] = hit ? gl : 0.f;
-    }
-  }
-}
-
-DRPO_API int drpo_actor_upstream(int64_t B, int C, int distributional, float std_ratio, float log_std_min,
-                                 float log_std_max, const float* lams, const float* mu_a, const float* ls_a,
-                                 const float* mu_s, const float* ls_s, float* gq, float* gmu_a, float* gls_a,
-                                 float* gmu_s, float* gls_s, float lam_upper_bound, float fixed_lam,
-                                 float clamp_lb, float clamp_ub, drpo_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (B == 0) return DRPO_OK;
-  actor_upstream_kernel<<<(unsigned)((B + 63) / 64), 64, 0, stream>>>(
-      B, C, distributional, std_ratio, log_std_min, log_std_max, lams, mu_a, ls_a, mu_s, ls_s, gq, gmu_a, gls_a,
-      gmu_s, gls_s, lam_upper_bound, fixed_lam, clamp_lb, clamp_ub);
-  DRPO_LAUNCH_CHECK("actor_upstream");
-  return DRPO_OK;
-}
-
-// ---------------------------------------------------------------------------
-// squashed-Gaussian backward
-// ---------------------------------------------------------------------------
-// dA [B][A]: dL/d action; g_lp = dL/d log_prob (alpha/B for the actor, 0 for the safe
-// actor, read as alpha = exp(*log_alpha) * lp_scale when log_alpha != NULL).
-// Writes draw [B][2A] = dL/d(mu, raw log-std). Optionally accumulates
-// sum_i (logp_i + target_entropy) into *alpha_sum (alpha loss).
-constexpr int SQ_MAXA = 8;   // action width bound of the row-wise heads
-__global__ __launch_bounds__(256) void squash_bwd_kernel(int64_t B, int A, const float* raw, const float* u,
-                                                         const float* e, const float* dA, const float* dA2, const float* log_alpha,
-                                                         float lp_scale, const float* logp, float target_entropy,
-                                                         float* alpha_sum, float* draw) {
-  __shared__ float red[8];
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  float acc = 0.f;
-  if (i < B) {
-    // every load of the row is issued before the first store (a store between two
-    // dependent load groups costs a second memory latency per row)
-    float mu[SQ_MAXA], rr[SQ_MAXA], uu[SQ_MAXA], ee[SQ_MAXA], dAv[SQ_MAXA];
-#pragma unroll
-    for (int d = 0; d < SQ_MAXA; ++d) {
-      if (d >= A) break;
-      mu[d] = raw[i * 2 * A + d];
-      rr[d] = raw[i * 2 * A + A + d];
-      uu[d] = u[i * A + d];
-      ee[d] = e[i * A + d];
-      dAv[d] = dA2 ? dA[i * A + d] + dA2[i * A + d] : dA[i * A + d];
-    }
-    const float lpi = alpha_sum ? logp[i] : 0.f;
-    const float glp = log_alpha ? expf(*log_alpha) * lp_scale : 0.f;
-#pragma unroll
-    for (int d = 0; d < SQ_MAXA; ++d) {
-      if (d >= A) break;
-      const float sg = sigmoidf(rr[d]);
-      const float sd = expf(-6.f + 10.f * sg) * 1.0f;
-      const float a = tanhf(uu[d]);
-      const float diff = uu[d] - mu[d];
-      const float var = sd * sd;
-      const float du = dAv[d] * (1.f - a * a) + glp * (-diff / var + 2.f - 4.f * sp_grad(-2.f * uu[d]));
-      const float dmu = du + glp * diff / var;
-      const float dsd = du * ee[d] + glp * (diff * diff / (var * sd) - 1.f / sd);
-      draw[i * 2 * A + d] = dmu;
-      draw[i * 2 * A + A + d] = dsd * sd * 10.f * sg * (1.f - sg);
-    }
-    if (alpha_sum) acc = lpi + target_entropy;
-  }
-  if (alpha_sum) {
-    const float s = block_sum(acc, red);
-    if (threadIdx.x == 0) atomicAdd(alpha_sum, s);
-  }
-}
-
-DRPO_API int drpo_squash_backward(int64_t B, int A, const float* raw, const float* u, const float* e, const float* dA, const float* dA2,
-                                  const float* log_alpha, float lp_scale, const float* logp, float target_entropy,
-                                  float* alpha_sum, float* draw, drpo_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DRPO_REQUIRE(A >= 1 && A <= SQ_MAXA, "drpo_squash_backward: action width %d", A);
-  if (B == 0) return DRPO_OK;
-  squash_bwd_kernel<<<(unsigned)((B + 63) / 64), 64, 0, stream>>>(B, A, raw, u, e, dA, dA2, log_alpha, lp_scale, logp,
-                                                                     target_entropy, alpha_sum, draw);
-  DRPO_LAUNCH_CHECK("squash_backward");
-  return DRPO_OK;
-}
-
-__global__ void alpha_grad_kernel(const float* log_alpha, const float* alpha_sum, float invB, float* grad) {
-  *grad = -expf(*log_alpha) * (*alpha_sum * invB);
-}
-
-DRPO_API int drpo_alpha_grad(const float* log_alpha, const float* alpha_sum, int64_t B, float* grad,
-                             drpo_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  alpha_grad_kernel<<<1, 1, 0, stream>>>(log_alpha, alpha_sum, 1.f / (float)B, grad);
-  DRPO_LAUNCH_CHECK("alpha_grad");
-  return DRPO_OK;
-}
-
-// ---------------------------------------------------------------------------
 // multiplier head (mlp multiplier)
 // ---------------------------------------------------------------------------
 // x: multiplier MLP output [B]; sqc: max_C safe constraint value; aqc: max_C actor Qc.
-// lam = ub/2 (1 + tanh(2x/ub)); loss = -0.5 mean([sqc<=0] lam pen) + mean(([sqc>0](lam - (ub-eps)))^2)
+// lam = multiplier_lam(x, ub); loss = -0.5 mean([sqc<=0] lam pen) + mean(([sqc>0](lam - (ub-eps)))^2)
 __global__ __launch_bounds__(256) void multiplier_head_kernel(int64_t B, const float* x, const float* sqc,
                                                               const float* aqc, float thr, float plb, float pub,
                                                               float ub, float lam_eps, float* gx, float* loss) {
@@ -407,8 +208,8 @@ __global__ __launch_bounds__(256) void multiplier_head_kernel(int64_t B, const f
     // scalar multiplier: the penalty sum of -mean(softplus(m) * penalty)
     l = fminf(fmaxf(aqc[i] - thr, plb), pub);
   } else if (i < B) {
-    const float t = tanhf(x[i] / ub * 2.f);
-    const float lam = ub / 2.f * (1.f + t);
+    const float t = multiplier_tanh(x[i], ub);
+    const float lam = multiplier_lam_of(t, ub);
     const float pen = fminf(fmaxf(aqc[i] - thr, plb), pub);
     const float safe = sqc[i] <= 0.f ? 1.f : 0.f, unsafe = 1.f - safe;
     const float invB = 1.f / (float)B;
@@ -434,10 +235,10 @@ DRPO_API int drpo_multiplier_head(int64_t B, const float* x, const float* safe_q
   return DRPO_OK;
 }
 
-// lam = ub/2 (1 + tanh(2x/ub)) (MLPMultiplier.forward output transform)
+// lam = multiplier_lam(x, ub) (sac_rows.hpp)
 __global__ void multiplier_out_kernel(int64_t B, const float* x, float ub, float* lam) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < B) lam[i] = ub / 2.f * (1.f + tanhf(x[i] / ub * 2.f));
+  if (i < B) lam[i] = multiplier_lam(x[i], ub);
 }
 
 DRPO_API int drpo_multiplier_out(int64_t B, const float* x, float upper_bound, float* lam, drpo_stream_t stream_) {

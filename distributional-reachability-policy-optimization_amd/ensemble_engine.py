@@ -25,7 +25,7 @@ import torch
 from . import _lib
 from .optim import fused_step
 from .rng import DeviceNoise
-from .sac_step import ACT_ID, Net, fill_bwd, fill_fwd
+from .mlp_desc import ACT_ID, Net, fill_bwd, fill_fwd, wgrad_workspace
 from ._abi import EnsReduce, EnsUpstream, WgradItem
 
 
@@ -308,7 +308,6 @@ class EnsembleEngine:
         c = self.wg_ws.get(key)
         if c is not None and c[0] is arr:
             return c[1]
-        from .sac_step import wgrad_workspace
         ws = wgrad_workspace(self.ws, f'{key}.wgws', arr, n, self.dev)
         self.wg_ws[key] = (arr, ws)
         return ws

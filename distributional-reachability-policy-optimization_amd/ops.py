@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from ._abi import RolloutDesc
+from .mlp_desc import Net, fill_fwd, spec_layers
 
 
 def _dev(x, device, dtype=None):
@@ -337,14 +338,12 @@ def default_noise():
 
 
 def _mlp(nets, srcs, rows, trunk=False, norm=None, nbatch=1, sstride=None):
-    from .sac_step import fill_fwd
     L = _lib.lib()
     d = fill_fwd(nets, srcs, rows, trunk=trunk, norm=norm, nbatch=nbatch, sstride=sstride)
     _lib.check(L.drpo_mlp_forward(ctypes.byref(d), _lib.stream()), 'mlp_forward')
 
 
 def _net(group, prefix, spec, out_rows=None):
-    from .sac_step import Net, spec_layers
     group.ensure_packed()
     net = Net(spec_layers(group, prefix, spec))
     if out_rows is not None:

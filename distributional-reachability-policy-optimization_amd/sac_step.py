@@ -23,256 +23,21 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from ._abi import (ActorHead, BufferView, CriticHead, MlpBwd, MlpFwd, SumDesc, WgradItem)
+from ._abi import ActorHead, BufferView, CriticHead, SumDesc
+from .mlp_desc import (HEAD_MEAN, HEAD_RSAMPLE, HEAD_SAMPLE, UPSTREAM_ACTOR_CC, UPSTREAM_CERT, UPSTREAM_CRITIC,
+                       UPSTREAM_NEG_MEAN, UPSTREAM_SAFE_CC, UPSTREAM_SQUASH, UPSTREAM_SQUASH_SAFE, Net, _p,
+                       bwd_flops, fill_bwd, fill_fwd, fwd_flops, pairable, spec_layers, wgrad_flops, wgrad_items,
+                       wgrad_workspace, with_head, with_post, with_pre)
+from .mlp_desc import LaunchProfiler  # noqa: F401  (bench.py --full takes the engine's profiler class from here)
 from .optim import ema_segment, fused_step, grad_sumsq_multi
-
-ACT_ID = {None: 0, 'identity': 0, 'relu': 1, 'swish': 2, 'tanh': 3}
 
 # Philox call-site ids (production noise)
 SITE_PI_NEXT, SITE_SAFE_NEXT, SITE_PI_RS, SITE_SAFE_RS, SITE_PI_MULT = 1, 2, 5, 6, 8
 
 
-def spec_layers(group, prefix, spec, buf=None):
-    """[(P, b, din, dout, act, PT)] for an MLPSpec stored under prefix in a flat group:
-    P / PT are the layer's packed forward / transposed weight mirrors (group.pview),
-    b the bias view (of ``buf`` if given, else the group data)."""
-    out = []
-    n = spec.n_layers
-    for i in range(n):
-        act = spec.act if i < n - 1 else spec.out_act
-        key = f'{prefix}{2 * i}.weight'
-        b = group.view(f'{prefix}{2 * i}.bias', buf)
-        PT = group.pview(key, True)
-        out.append((group.pview(key)[0], b, spec.dims[i], spec.dims[i + 1], ACT_ID[act],
-                    None if PT is None else PT[0]))
-    return out
-
-
-class Net:
-    """One MLP as seen by the kernels: layer tuples + (optional) per-layer save buffers."""
-
-    def __init__(self, layers, grad_layers=None):
-        self.layers = layers              # [(P, b, din, dout, act, PT)]
-        self.grad_layers = grad_layers    # [(gW, gb)] or None
-        self.sy = [None] * len(layers)
-        self.sz = [None] * len(layers)
-        self.dz = [None] * len(layers)
-        self.dz2 = [None] * len(layers)   # split-heads trunk: the second head's dZ share
-
-    @property
-    def dout(self):
-        return self.layers[-1][3]
-
-    @property
-    def din(self):
-        return self.layers[0][2]
-
-
-def _p(t):
-    return 0 if t is None else t.data_ptr()
-
-
 def noise_tag(eps):
     """descriptor-cache suffix: recorded draws (parity) vs Philox (production)"""
     return '.p' if eps is not None else '.d'
-
-
-def fill_net(dst, net, wstride=None):
-    """drpo_mlp_net_t of a Net (layers, save buffers, per-member strides)."""
-    dst.nl = len(net.layers)
-    for l, (W, b, din, dout, act, WT) in enumerate(net.layers):
-        L = dst.L[l]
-        L.W, L.b, L.din, L.dout, L.act = W.data_ptr(), b.data_ptr(), din, dout, act
-        L.sy, L.sz = _p(net.sy[l]), _p(net.sz[l])
-        L.wstride, L.bstride = (0, 0) if wstride is None else wstride[l]
-
-
-def fill_fwd(nets, srcs, rows, trunk=False, save_x=None, norm=None, nbatch=1, wstride=None, sstride=None,
-             split_heads=False, pair=False):
-    """pair: the two nets run by one workgroup (multi-job launches; drpo_mlp_fwd_t.pair)."""
-    d = MlpFwd()
-    for k, (t, cols) in enumerate(srcs):
-        d.src[k] = _p(t)
-        d.cols[k] = cols
-        d.ld[k] = t.shape[-1] if t is not None and t.dim() > 1 else 1
-        d.sstride[k] = 0 if sstride is None else sstride[k]
-    d.nmean, d.nstd = (norm[0].data_ptr(), norm[1].data_ptr()) if norm is not None else (0, 0)
-    d.save_x = _p(save_x)
-    for j, net in enumerate(nets):
-        fill_net(d.net[j], net, None if wstride is None else wstride[j])
-    d.nnets, d.trunk, d.rows, d.nbatch = len(nets), int(trunk), rows, nbatch
-    d.split_heads = int(split_heads)
-    d.pair = int(pair)
-    return d
-
-
-def pairable(a, b):
-    """Two nets one pair job can run (csrc/mlp.hip pair_ok): 3-layer ReLU nets of one shape
-    [K <= 16 or 49..64 -> 256 -> 256 -> <= 16] (the reference's default widths)."""
-    la, lb = a.layers, b.layers
-    if len(la) != 3 or len(lb) != 3:
-        return False
-    if any(x[2:5] != y[2:5] for x, y in zip(la, lb)):
-        return False
-    (_, _, k0, n0, a0, _), (_, _, k1, n1, a1, _), (_, _, _, n2, a2, _) = la
-    return ((k0 + 15) // 16 in (1, 4) and n0 == 256 and k1 == 256 and n1 == 256 and n2 <= 16 and
-            a0 == ACT_ID['relu'] and a1 == ACT_ID['relu'] and a2 == 0)
-
-
-def with_pre(d, policy, mode, A, eps, site, logp=None):
-    """Chain (drpo_mlp_fwd_t.pre): the policy runs first in the same workgroup on the
-    src[0] columns; its sampled action (mode 1 sample / 2 rsample) is the job's src[1]
-    block, straight from LDS."""
-    fill_net(d.pre, policy)
-    h = d.pre_head
-    h.mode, h.A, h.eps, h.site, h.logp = mode, A, _p(eps), site, _p(logp)
-    return d
-
-
-def with_post(d, net, post_x=None):
-    """Post chain (drpo_mlp_fwd_t.post): `net` (the MLPMultiplier) runs after the job's
-    constraint bound (ccb_out), in the same workgroup, on [src[0] columns, bound]; its
-    layers save as any net's, post_x saves the assembled input (the multiplier update's
-    weight-gradient Y)."""
-    fill_net(d.post, net)
-    d.post_x = _p(post_x)
-    return d
-
-
-# drpo_mlp_bwd_t.upstream (include/drpo_hip.h DRPO_UPSTREAM_*)
-UPSTREAM_GOUT, UPSTREAM_CRITIC, UPSTREAM_CERT, UPSTREAM_ENS = 0, 1, 2, 3
-UPSTREAM_ACTOR_CC, UPSTREAM_SAFE_CC, UPSTREAM_NEG_MEAN, UPSTREAM_SQUASH, UPSTREAM_SQUASH_SAFE = 4, 5, 6, 7, 8
-
-
-def fill_bwd(nets, gouts, rows, trunk=False, dx=None, nbatch=1, wstride=None, split_heads=False, upstream=0):
-    """nets[0] trunk when trunk=True (gouts[0] ignored); dx: {net_index: (tensor, col0, cols, accumulate)};
-    split_heads: one workgroup per head, the second head's trunk dZ share into nets[0].dz2;
-    upstream: output gradients from the gout arrays, or formed in-kernel from the
-    launch's critic head (UPSTREAM_CRITIC / UPSTREAM_CERT)."""
-    d = MlpBwd()
-    d.upstream = upstream
-    for j, net in enumerate(nets):
-        d.net[j].nl = len(net.layers)
-        for l, (W, b, din, dout, act, WT) in enumerate(net.layers):
-            L = d.net[j].L[l]
-            assert WT is not None, 'backward needs the transposed weight mirror (trained group)'
-            L.W, L.din, L.dout, L.act = WT.data_ptr(), din, dout, act
-            L.sy, L.sz, L.dz = _p(net.sy[l]), _p(net.sz[l]), _p(net.dz[l])
-            L.dz2 = _p(net.dz2[l]) if getattr(net, 'dz2', None) else 0
-            L.wstride = 0 if wstride is None else wstride[j][l][0]
-        d.net[j].gout = _p(gouts[j])
-        if dx and j in dx:
-            t, c0, nc, accum = dx[j]
-            d.net[j].dx, d.net[j].dx_col0, d.net[j].dx_cols, d.net[j].dx_accumulate = t.data_ptr(), c0, nc, int(accum)
-    d.nnets, d.trunk, d.rows, d.nbatch = len(nets), int(trunk), rows, nbatch
-    d.split_heads = int(split_heads)
-    return d
-
-
-HEAD_SAMPLE, HEAD_RSAMPLE, HEAD_MEAN = 1, 2, 3
-
-
-def with_head(d, mode, A, eps, site, a=None, logp=None, u=None, e=None, amean=None, second=False):
-    """Attach a fused squashed-Gaussian head (drpo_policy_head_t) to a forward descriptor
-    (second: the head of a pair job's net 1, drpo_mlp_fwd_t.head2)."""
-    h = d.head2 if second else d.head
-    h.mode, h.A, h.eps, h.site = mode, A, _p(eps), site
-    h.a, h.logp, h.u, h.e, h.amean = _p(a), _p(logp), _p(u), _p(e), _p(amean)
-    return d
-
-
-def wgrad_items(entries, rows, sq=None):
-    """entries: [(net, inputs_per_layer[, segment])] -> (ctypes array of WgradItem, count,
-    {segment: partial slots used}). With sq = {segment: device tensor}, every item of a
-    segment writes the sums of squares of its finished gradient tiles into consecutive
-    slots of that segment's tensor (the clip partials of drpo_optim_step)."""
-    L = _lib.lib()
-    items, used = [], {}
-    units = [(ent[0], ent[1], ent[2] if len(ent) > 2 else None, l) for ent in entries for l in range(len(ent[0].layers))]
-    for net, ins, seg, l in units:
-        W, b, din, dout, act, WT = net.layers[l]
-        gW, gb = net.grad_layers[l]
-        it = WgradItem()
-        it.dz, it.y, it.gW, it.gb = net.dz[l].data_ptr(), ins[l].data_ptr(), gW.data_ptr(), gb.data_ptr()
-        it.dout, it.din, it.rows, it.nbatch = dout, din, rows, 1
-        if sq is not None and seg is not None:
-            it.sq, it.sq_off = sq[seg].data_ptr(), used.get(seg, 0)
-            used[seg] = it.sq_off + L.drpo_mlp_wgrad_tiles(ctypes.byref(it))
-            assert used[seg] <= sq[seg].numel(), 'clip partial buffer too small'
-        items.append(it)
-    arr = (WgradItem * len(items))(*items)
-    return arr, len(items), used
-
-
-def wgrad_workspace(cache, key, arr, n, dev):
-    """Zero-initialised workspace of one drpo_mlp_wgrad call site (the launches keep it
-    zeroed), cached by key and grown when the plan needs more."""
-    need = int(_lib.lib().drpo_mlp_wgrad_workspace_size(arr, n))
-    t = cache.get(key)
-    if t is None or t.numel() < need:
-        t = torch.zeros(max(need, 256), dtype=torch.uint8, device=dev)
-        cache[key] = t
-    return t
-
-
-def fwd_flops(d):
-    """Algorithmic FLOPs of one drpo_mlp_forward launch (2 * rows * sum din*dout), the
-    chained policy and the post-chain multiplier of a multi-job launch included."""
-    macs = 0
-    for n in [d.net[j] for j in range(d.nnets)] + [d.pre, d.post]:
-        for l in range(n.nl):
-            macs += n.L[l].din * n.L[l].dout
-    return 2 * d.rows * d.nbatch * macs
-
-
-def bwd_flops(d):
-    """Backward-data products (dY = dZ W) of one drpo_mlp_backward launch; layer 0's
-    product runs only for trunk-mode heads (it feeds the trunk) or when the input
-    gradient is requested."""
-    macs = 0
-    for j in range(d.nnets):
-        n = d.net[j]
-        for l in range(n.nl):
-            if l > 0 or n.dx or (d.trunk and j > 0):
-                macs += n.L[l].din * n.L[l].dout
-    return 2 * d.rows * d.nbatch * macs
-
-
-def wgrad_flops(arr, n):
-    # (arr, n[, used]) descriptors
-    return sum(2 * arr[i].rows * arr[i].nbatch * arr[i].dout * (arr[i].din + 1) for i in range(n))
-
-
-class LaunchProfiler:
-    """HIP events around every MLP launch of the engine (stream-ordered on the launch
-    stream), with each launch's algorithmic FLOPs; summarise() after a synchronize."""
-
-    def __init__(self):
-        self.recs = []
-
-    def begin(self, kind, key, flops):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        return (kind, key, flops, e0, e1)
-
-    def end(self, rec):
-        rec[4].record()
-        self.recs.append(rec)
-
-    def summarise(self):
-        out = {}
-        for kind, key, flops, e0, e1 in self.recs:
-            ms = e0.elapsed_time(e1)
-            for k in (kind, f'{kind}:{key}'):
-                o = out.setdefault(k, {'launches': 0, 'ms': 0.0, 'flop': 0.0})
-                o['launches'] += 1
-                o['ms'] += ms
-                o['flop'] += flops
-        for o in out.values():
-            o['avg_ms'] = o['ms'] / o['launches']
-            o['tflops'] = o['flop'] / (o['ms'] * 1e-3) / 1e12 if o['ms'] > 0 else 0.0
-        self.recs = []
-        return out
 
 
 class SACEngine:
@@ -422,82 +187,66 @@ class SACEngine:
                   sol.multiplier_group):
             g.ensure_packed()
 
-    def _run_fwd(self, key, builder):
+    def _launch(self, kind, key, build, flops, call):
+        """One launch of a cached descriptor: build() makes it on first use, call(d) issues
+        the launch and returns its status; with a profiler, HIP events and flops(d) around it."""
         d = self.desc.get(key)
         if d is None:
-            d = self.desc[key] = builder()
-        ev = self.profiler.begin('mlp_fwd', key, fwd_flops(d)) if self.profiler else None
-        _lib.check(_lib.lib().drpo_mlp_forward(ctypes.byref(d), _lib.stream()), key)
+            d = self.desc[key] = build()
+        ev = self.profiler.begin(kind, key, flops(d)) if self.profiler else None
+        _lib.check(call(d), key)
         if ev:
             self.profiler.end(ev)
+        return d
 
-    def _upload(self, structs):
-        raw = bytes(structs)
-        return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.dev)
+    def _jobs(self, jobs, flops):
+        """(host array, device copy, count, FLOPs) of a multi-job launch's descriptors:
+        built once and kept in device memory."""
+        arr = (type(jobs[0]) * len(jobs))(*jobs)
+        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.dev)
+        return arr, raw, len(jobs), sum(flops(j) for j in jobs)
+
+    def _run_fwd(self, key, builder):
+        self._launch('mlp_fwd', key, builder, fwd_flops,
+                     lambda d: _lib.lib().drpo_mlp_forward(ctypes.byref(d), _lib.stream()))
 
     def _run_multi(self, key, builder, ctr):
-        """Independent forwards (+ fused policy heads) in one launch; descriptors are
-        built once and kept in device memory."""
-        d = self.desc.get(key)
-        if d is None:
-            jobs = builder()
-            arr = (MlpFwd * len(jobs))(*jobs)
-            d = self.desc[key] = (arr, self._upload(arr), len(jobs), sum(fwd_flops(j) for j in jobs))
-        arr, dev, nj, fl = d
-        ev = self.profiler.begin('mlp_fwd', key, fl) if self.profiler else None
-        _lib.check(_lib.lib().drpo_mlp_forward_multi(arr, dev.data_ptr(), nj, self.noise.seed, ctr, _lib.stream()), key)
-        if ev:
-            self.profiler.end(ev)
+        """Independent forwards (+ fused policy heads) in one launch."""
+        self._launch('mlp_fwd', key, lambda: self._jobs(builder(), fwd_flops), lambda d: d[3],
+                     lambda d: _lib.lib().drpo_mlp_forward_multi(d[0], d[1].data_ptr(), d[2], self.noise.seed, ctr,
+                                                                 _lib.stream()))
 
     def _run_bwd_multi(self, key, builder, head=None, actor=None):
-        d = self.desc.get(key)
-        if d is None:
-            jobs = builder()
-            arr = (MlpBwd * len(jobs))(*jobs)
-            d = self.desc[key] = (arr, self._upload(arr), len(jobs), sum(bwd_flops(j) for j in jobs))
-        arr, dev, nj, fl = d
-        ev = self.profiler.begin('mlp_bwd', key, fl) if self.profiler else None
+        L, st = _lib.lib(), _lib.stream()
         if actor is not None:
-            _lib.check(_lib.lib().drpo_mlp_backward_multi_actor(arr, dev.data_ptr(), nj, ctypes.byref(actor),
-                                                                _lib.stream()), key)
-        elif head is None:
-            _lib.check(_lib.lib().drpo_mlp_backward_multi(arr, dev.data_ptr(), nj, _lib.stream()), key)
+            call = lambda d: L.drpo_mlp_backward_multi_actor(d[0], d[1].data_ptr(), d[2], ctypes.byref(actor), st)
+        elif head is not None:
+            call = lambda d: L.drpo_mlp_backward_multi_head(d[0], d[1].data_ptr(), d[2], ctypes.byref(head), st)
         else:
-            _lib.check(_lib.lib().drpo_mlp_backward_multi_head(arr, dev.data_ptr(), nj, ctypes.byref(head),
-                                                               _lib.stream()), key)
-        if ev:
-            self.profiler.end(ev)
+            call = lambda d: L.drpo_mlp_backward_multi(d[0], d[1].data_ptr(), d[2], st)
+        self._launch('mlp_bwd', key, lambda: self._jobs(builder(), bwd_flops), lambda d: d[3], call)
 
     def _run_bwd(self, key, builder):
-        d = self.desc.get(key)
-        if d is None:
-            d = self.desc[key] = builder()
-        ev = self.profiler.begin('mlp_bwd', key, bwd_flops(d)) if self.profiler else None
-        _lib.check(_lib.lib().drpo_mlp_backward(ctypes.byref(d), _lib.stream()), key)
-        if ev:
-            self.profiler.end(ev)
+        self._launch('mlp_bwd', key, builder, bwd_flops,
+                     lambda d: _lib.lib().drpo_mlp_backward(ctypes.byref(d), _lib.stream()))
 
     def _run_wgrad(self, key, builder, sums=None):
         """One grouped weight-gradient launch; returns the clip-partial slots per segment.
         sums: [(partials, out)] -- loss partials the launch's extra block adds up in order
         into the 0-d `out` (drpo_mlp_wgrad_sums)."""
-        d = self.desc.get(key)
-        if d is None:
+        def build():
             arr, n, used = builder()
-            ws = wgrad_workspace(self.wg_ws, key, arr, n, self.dev)
-            d = self.desc[key] = (arr, n, used, ws, (SumDesc * 4)())
-        arr, n, used, ws, sd = d
-        ev = self.profiler.begin('mlp_wgrad', key, wgrad_flops(arr, n)) if self.profiler else None
-        if sums:
+            return arr, n, used, wgrad_workspace(self.wg_ws, key, arr, n, self.dev), (SumDesc * 4)()
+
+        def call(d):
+            arr, n, _, ws, sd = d
+            L = _lib.lib()
+            if not sums:
+                return L.drpo_mlp_wgrad(arr, n, ws.data_ptr(), ws.numel(), _lib.stream())
             for q, (part, out) in enumerate(sums):
                 sd[q].part, sd[q].n, sd[q].out = part.data_ptr(), part.numel(), out.data_ptr()
-            _lib.check(_lib.lib().drpo_mlp_wgrad_sums(arr, n, sd, len(sums), ws.data_ptr(), ws.numel(),
-                                                      _lib.stream()), key)
-        else:
-            _lib.check(_lib.lib().drpo_mlp_wgrad(arr, n, ws.data_ptr(), ws.numel(), _lib.stream()), key)
-        if ev:
-            self.profiler.end(ev)
-        return used
+            return L.drpo_mlp_wgrad_sums(arr, n, sd, len(sums), ws.data_ptr(), ws.numel(), _lib.stream())
+        return self._launch('mlp_wgrad', key, build, lambda d: wgrad_flops(d[0], d[1]), call)[2]
 
     def _clip_parts(self, fused, key, segs, grads):
         """Clip partial sums per segment: from the weight-gradient launch (fused, single
@@ -517,12 +266,6 @@ class SACEngine:
             return None
         return {sg: self.buf(f'sq.{key}.{sg}', 4096) for sg in segs}
 
-    def _policy_head(self, raw, mode, eps, site, ctr, a=None, logp=None, u=None, e=None, amean=None):
-        L = _lib.lib()
-        seed = self.noise.seed
-        _lib.check(L.drpo_policy_head(raw.data_ptr(), self.B, self.A, mode, _p(eps), seed, ctr, site, _p(a), _p(logp),
-                                      _p(u), _p(e), _p(amean), _lib.stream()), 'policy_head')
-
     def _ccb_fused(self):
         """The multi-job forward can form the bound when the constraint critic's heads are
         pairable (256-wide trunk, two [256 -> H -> C <= 16] heads: the reference widths)."""
@@ -532,7 +275,7 @@ class SACEngine:
                 and l2[1][3] <= 16 and l1[0][4] == l2[0][4] and l1[1][4] == l2[1][4])
 
     def _ccb(self, d, out, dist):
-        """The constraint critic's max-C upper bound (drpo_cc_head's arithmetic) formed
+        """The constraint critic's max-C upper bound (the one drpo_cc_head computes) formed
         by the multi-job forward from the paired heads' outputs (drpo_mlp_fwd_t.ccb_*);
         other head shapes keep the drpo_cc_head launch (_cc_bound_after)."""
         if not self._ccb_fused():
@@ -592,7 +335,6 @@ class SACEngine:
         sol, n, B, S, A, C = self.sol, self.nets, self.B, self.S, self.A, self.C
         self._ensure_packed()
         self.noise = noise = noise or self.noise
-        L = _lib.lib()
         dist = sol.distributional_qc and sol.qc_under_uncertainty
         robust = sol.qc_under_uncertainty and not sol.distributional_qc and not self.cost
         qshape = (B,) if C == 1 else (B, C)
@@ -665,8 +407,6 @@ class SACEngine:
             ch.mu_t, ch.ls_t = n['cc_meant'].sy[-1].data_ptr(), n['cc_lst'].sy[-1].data_ptr()
             ch.q0, ch.q1 = n['q0'].sy[-1].data_ptr(), n['q1'].sy[-1].data_ptr()
             ch.mu, ch.ls = n['cc_mean'].sy[-1].data_ptr(), n['cc_ls'].sy[-1].data_ptr()
-            ch.dq0, ch.dq1 = self.buf('c.dq0', B).data_ptr(), self.buf('c.dq1', B).data_ptr()
-            ch.dmu, ch.dls = self.buf('c.dmu', B, C).data_ptr(), self.buf('c.dls', B, C).data_ptr()
         cc = sol.constraint_critic
         ch.distributional, ch.deterministic_backup = int(dist), int(sol.deterministic_backup)
         ch.discount, ch.qc_td_bound = sol.discount, sol.qc_td_bound
@@ -687,8 +427,8 @@ class SACEngine:
         # (src/ssac.py:284-456: compute_target, compute_cons_target, both losses)
         heads = [n['cc_trunk'], n['cc_mean']] + ([n['cc_ls']] if dist else [])
         self._run_bwd_multi('c.b' + str(int(dist)), lambda: [
-            fill_bwd(heads, [None, ws['c.dmu'], ws['c.dls']][:len(heads)], B, trunk=True, upstream=UPSTREAM_CERT),
-            fill_bwd([n['q0'], n['q1']], [ws['c.dq0'], ws['c.dq1']], B, upstream=UPSTREAM_CRITIC)], head=ch)
+            fill_bwd(heads, [None] * len(heads), B, trunk=True, upstream=UPSTREAM_CERT),
+            fill_bwd([n['q0'], n['q1']], [None, None], B, upstream=UPSTREAM_CRITIC)], head=ch)
         tsy = n['cc_trunk'].sy
         items = [(n['q0'], [xs, n['q0'].sy[0], n['q0'].sy[1]], 'c'), (n['q1'], [xs, n['q1'].sy[0], n['q1'].sy[1]], 'c'),
                  (n['cc_trunk'], [xs, tsy[0]], 'cc'), (n['cc_mean'], [tsy[-1], n['cc_mean'].sy[0]], 'cc')]
@@ -740,7 +480,6 @@ class SACEngine:
         sol, n, B, S, A, C = self.sol, self.nets, self.B, self.S, self.A, self.C
         self._ensure_packed()
         self.noise = noise = noise or self.noise
-        L = _lib.lib()
         ws = self.ws
         dist = sol.distributional_qc
         qshape = (B,) if C == 1 else (B, C)
@@ -817,22 +556,20 @@ class SACEngine:
         # the reference's order) and of the safe actor: one backward launch
         dA, dAc, dAs = self.buf('a.dA', B, A), self.buf('a.dAc', B, A), self.buf('a.dAs', B, A)
         hv, hv2 = self.nets_view['a.cc'], self.nets_view.get('a.cc2')
-        gq, gmu, gls, gmu2, gls2 = (self.buf('a.gq', B), self.buf('a.gmu', B, C), self.buf('a.gls', B, C),
-                                    self.buf('a.gmu2', B, C), self.buf('a.gls2', B, C))
+        nh = 3 if dist else 2   # trunk + mean head (+ log-std head)
         self._run_bwd_multi(f'a.b.{k}{int(dist)}', lambda: [
-            fill_bwd(hv if dist else hv[:2], [None, gmu, gls][:3 if dist else 2], B, trunk=True,
-                     dx={0: (dAc, S, A, False)}, upstream=UPSTREAM_ACTOR_CC)] + ([] if cost else [
-            fill_bwd(hv2 if dist else hv2[:2], [None, gmu2, gls2][:3 if dist else 2], B, trunk=True,
-                     dx={0: (dAs, S, A, False)}, upstream=UPSTREAM_SAFE_CC)]) + [
-            fill_bwd([self.nets_view[f'a.q{k}']], [gq], B, dx={0: (dA, S, A, False)}, upstream=UPSTREAM_NEG_MEAN)],
+            fill_bwd(hv[:nh], [None] * nh, B, trunk=True, dx={0: (dAc, S, A, False)}, upstream=UPSTREAM_ACTOR_CC)] + (
+            [] if cost else [
+                fill_bwd(hv2[:nh], [None] * nh, B, trunk=True, dx={0: (dAs, S, A, False)},
+                         upstream=UPSTREAM_SAFE_CC)]) + [
+            fill_bwd([self.nets_view[f'a.q{k}']], [None], B, dx={0: (dA, S, A, False)}, upstream=UPSTREAM_NEG_MEAN)],
             actor=ah)
-        draw, draws = self.buf('a.draw', B, 2 * A), self.buf('a.draws', B, 2 * A)
         asum = self.alpha_sum
         self._clean_grads(sol.actor.group)
         if not cost:
             self._clean_grads(sol.actor_safe.group)
-        self._run_bwd_multi('a.bpi', lambda: [fill_bwd([n['actor']], [draw], B, upstream=UPSTREAM_SQUASH)] + (
-            [] if cost else [fill_bwd([n['safe']], [draws], B, upstream=UPSTREAM_SQUASH_SAFE)]), actor=ah)
+        self._run_bwd_multi('a.bpi', lambda: [fill_bwd([n['actor']], [None], B, upstream=UPSTREAM_SQUASH)] + (
+            [] if cost else [fill_bwd([n['safe']], [None], B, upstream=UPSTREAM_SQUASH_SAFE)]), actor=ah)
         na, ns = n['actor'], n['safe']
         asegs = ('a',) if cost else ('a', 's')
         sq = self._sq('a', asegs)
@@ -890,38 +627,31 @@ class SACEngine:
         a, lp, u, e = self.buf('a.a', B, A), self.buf('a.lp', B), self.buf('a.u', B, A), self.buf('a.e', B, A)
         a_s, u_s, e_s, am = self.buf('a.as', B, A), self.buf('a.us', B, A), self.buf('a.es', B, A), \
             self.buf('a.am', B, A)
-        # One workgroup runs both policies when their shapes pair (the same input, one
-        # saved copy of it). Cost certificate: the safe actor only gives tanh(mu_safe) for the
-        # multiplier's input (src/ssac.py:473-478), or nothing without the MLP multiplier.
-        if cost:
-            return [
-                with_head(with_head(fill_fwd([n['actor'], n['safe']], [(self.bs, S), (None, 0), (None, 0)], B,
-                                             save_x=xa, pair=True), HEAD_RSAMPLE, A, e5, SITE_PI_RS, a=a, logp=lp, u=u,
-                                    e=e),
-                          HEAD_MEAN, A, None, 0, amean=am, second=True)] if mlp_mult and pairable(n['actor'], n['safe']) \
-                else [with_head(fill_fwd([n['actor']], [(self.bs, S), (None, 0), (None, 0)], B, save_x=xa), HEAD_RSAMPLE,
-                                A, e5, SITE_PI_RS, a=a, logp=lp, u=u, e=e)] + (
-                    [with_head(fill_fwd([Net(n['safe'].layers)], [(self.bs, S), (None, 0), (None, 0)], B), HEAD_MEAN, A,
-                               None, 0, amean=am)] if mlp_mult else [])
-        elif pairable(n['actor'], n['safe']):
-            return [
-                with_head(with_head(fill_fwd([n['actor'], n['safe']], [(self.bs, S), (None, 0), (None, 0)], B,
-                                             save_x=xa, pair=True), HEAD_RSAMPLE, A, e5, SITE_PI_RS, a=a, logp=lp, u=u,
-                                    e=e),
-                          HEAD_RSAMPLE, A, e6, SITE_SAFE_RS, a=a_s, u=u_s, e=e_s, amean=am, second=True)]
-        else:
-            return [
-                with_head(fill_fwd([n['actor']], [(self.bs, S), (None, 0), (None, 0)], B, save_x=xa), HEAD_RSAMPLE,
-                          A, e5, SITE_PI_RS, a=a, logp=lp, u=u, e=e),
-                with_head(fill_fwd([n['safe']], [(self.bs, S), (None, 0), (None, 0)], B), HEAD_RSAMPLE, A, e6,
-                          SITE_SAFE_RS, a=a_s, u=u_s, e=e_s, amean=am)]
+        # Cost certificate: the safe actor only gives tanh(mu_safe) for the multiplier's
+        # input (src/ssac.py:473-478), or nothing without the MLP multiplier.
+        pi = dict(mode=HEAD_RSAMPLE, eps=e5, site=SITE_PI_RS, a=a, logp=lp, u=u, e=e)
+        if not cost:
+            return self._policy_jobs(n['actor'], pi, n['safe'], dict(mode=HEAD_RSAMPLE, eps=e6, site=SITE_SAFE_RS, a=a_s,
+                                                                     u=u_s, e=e_s, amean=am), save_x=xa)
+        if not mlp_mult:
+            return self._policy_jobs(n['actor'], pi, save_x=xa)
+        # (its own job runs a no-save view; the pair job keeps the net's save buffers)
+        safe = n['safe'] if pairable(n['actor'], n['safe']) else Net(n['safe'].layers)
+        return self._policy_jobs(n['actor'], pi, safe, dict(mode=HEAD_MEAN, eps=None, site=0, amean=am), save_x=xa)
 
-    def _alpha_adam(self, grad):
-        opt = self.sol.alpha_optimizer
-        if opt.tensor is None:
-            opt.tensor = self.sol.log_alpha.view(1)
-        sc = opt.step_scalars()
-        opt.apply(grad, 0, 1, sc)
+    def _policy_jobs(self, actor, head, safe=None, head2=None, save_x=None):
+        """Forward jobs of the actor and, with `safe`, the safe actor on the batch states,
+        each with its fused squashed-Gaussian head (head / head2: with_head's keywords).
+        One workgroup runs both policies when their shapes pair (one pair job: the same
+        input, one saved copy of it); else one job each, the actor's first with save_x."""
+        src, B, A = [(self.bs, self.S), (None, 0), (None, 0)], self.B, self.A
+        if safe is None:
+            return [with_head(fill_fwd([actor], src, B, save_x=save_x), A=A, **head)]
+        if pairable(actor, safe):
+            d = fill_fwd([actor, safe], src, B, save_x=save_x, pair=True)
+            return [with_head(with_head(d, A=A, **head), A=A, second=True, **head2)]
+        return [with_head(fill_fwd([actor], src, B, save_x=save_x), A=A, **head),
+                with_head(fill_fwd([safe], src, B), A=A, **head2)]
 
     # views of nets with separately named save buffers (so passes do not clobber each other)
     def _reuse(self, net, name):
@@ -939,10 +669,6 @@ class SACEngine:
             v = [self._reuse(x, f'{name}.{i}') for i, x in enumerate(self._cc_nets())]
             self.nets_view[name] = v
         return v
-
-    def _cc_views(self, name):
-        v = self.nets_view[name]
-        return v[1].sy[-1], v[2].sy[-1]
 
     def _outs_cc(self, name):
         nets = [Net(x.layers) for x in self._cc_nets()]
@@ -965,7 +691,6 @@ class SACEngine:
         if not sol.mlp_multiplier:
             return self._scalar_mult_step(noise)
         L = _lib.lib()
-        ws = self.ws
         dist = sol.distributional_qc
         qshape = (B,) if C == 1 else (B, C)
         e7 = self._eps('e7', noise.std_normal((B, A)))
@@ -975,18 +700,8 @@ class SACEngine:
         ctr = noise.next()
         a, am = self.buf('m.a', B, A), self.buf('m.am', B, A)
         # launch 1: a ~ pi(s) (rsample) and tanh(mu_safe(s)) via fused heads
-        if pairable(n['actor'], n['safe']):
-            jobs = lambda: [
-                with_head(with_head(fill_fwd([Net(n['actor'].layers), Net(n['safe'].layers)],
-                                             [(self.bs, S), (None, 0), (None, 0)], B, pair=True),
-                                    HEAD_RSAMPLE, A, e7, SITE_PI_MULT, a=a),
-                          HEAD_MEAN, A, None, 0, amean=am, second=True)]
-        else:
-            jobs = lambda: [
-                with_head(fill_fwd([Net(n['actor'].layers)], [(self.bs, S), (None, 0), (None, 0)], B), HEAD_RSAMPLE,
-                          A, e7, SITE_PI_MULT, a=a),
-                with_head(fill_fwd([Net(n['safe'].layers)], [(self.bs, S), (None, 0), (None, 0)], B), HEAD_MEAN, A,
-                          None, 0, amean=am)]
+        jobs = lambda: self._policy_jobs(Net(n['actor'].layers), dict(mode=HEAD_RSAMPLE, eps=e7, site=SITE_PI_MULT, a=a),
+                                         Net(n['safe'].layers), dict(mode=HEAD_MEAN, eps=None, site=0, amean=am))
         self._run_multi('m.f1' + noise_tag(e7), jobs, ctr)
         # launch 2: constraint critic at (s, a) and at (s, tanh(mu_safe))
         aqc, sqc = self.buf('m.aqc', B), self.buf('m.sqc', B)
@@ -1034,7 +749,6 @@ class SACEngine:
         optimizer launch forms d/dm = -sigmoid(m) * sum / rows on the device."""
         sol, n, B, S, A, C = self.sol, self.nets, self.B, self.S, self.A, self.C
         L = _lib.lib()
-        ws = self.ws
         dist = sol.distributional_qc
         qshape = (B,) if C == 1 else (B, C)
         e7 = self._eps('e7', noise.std_normal((B, A)))
@@ -1042,9 +756,8 @@ class SACEngine:
             noise.randn_like(qshape, used=False)
         ctr = noise.next()
         a = self.buf('m.a', B, A)
-        self._run_multi('m.f1s' + noise_tag(e7), lambda: [
-            with_head(fill_fwd([Net(n['actor'].layers)], [(self.bs, S), (None, 0), (None, 0)], B), HEAD_RSAMPLE, A,
-                      e7, SITE_PI_MULT, a=a)], ctr)
+        self._run_multi('m.f1s' + noise_tag(e7), lambda: self._policy_jobs(
+            Net(n['actor'].layers), dict(mode=HEAD_RSAMPLE, eps=e7, site=SITE_PI_MULT, a=a)), ctr)
         aqc = self.buf('m.aqc', B)
         self._run_multi('m.f2s', lambda: [
             self._ccb(fill_fwd(self._outs_cc('m.cc'), [(self.bs, S), (a, A), (None, 0)], B, trunk=True), aqc,

@@ -220,7 +220,7 @@ typedef struct {
   float* ccb_out;      /* multi-job launches, trunk job with paired heads (the constraint critic,
                           src/ssac.py:46-92): per-row max over the C constraints of the quantile
                           bound mu + ccb_ratio * std(log-std raw) (ccb_dist) or of mu, formed from
-                          the heads' outputs in the launch (drpo_cc_head's arithmetic,
+                          the heads' outputs in the launch (the bound drpo_cc_head computes,
                           src/ssac.py:474-494,536-560); NULL: none */
   int ccb_dist;
   float ccb_ratio, ccb_lmin, ccb_lmax;
@@ -256,7 +256,8 @@ typedef struct {
 typedef struct {
   int nl;
   drpo_mlp_bwd_layer_t L[3];
-  const float* gout;   /* dL/d(output) [rows][dout_last] */
+  const float* gout;   /* dL/d(output) [rows][dout_last]: read (and required) only with
+                          DRPO_UPSTREAM_GOUT, and never for the trunk of a trunk job */
   float* dx;           /* optional dL/d(input) for input columns [dx_col0, dx_col0 + dx_cols) */
   int dx_col0, dx_cols, dx_accumulate;
 } drpo_mlp_bwd_net_t;
@@ -291,8 +292,8 @@ typedef struct {
 } drpo_ens_upstream_t;
 
 /* The actor update's output gradients (src/ssac.py:458-527), formed in-kernel by its
- * backward launches (drpo_mlp_backward_multi_actor): what drpo_actor_upstream and
- * drpo_squash_backward compute as separate launches. */
+ * backward launches (drpo_mlp_backward_multi_actor): dL/d(Q_k, constraint-critic heads) of
+ * the actor / safe-actor losses and the chain rule through rsample + tanh + log_prob. */
 typedef struct {
   int64_t B;
   int C, A, distributional;
@@ -354,8 +355,8 @@ typedef struct {
   float *mse, *loss, *gmin, *gmax;
 } drpo_ens_reduce_t;
 
-/* the safe-SAC critic losses of one update_critic (src/ssac.py:284-435): drpo_critic_head
- * (csrc/sac.hip) or fused into drpo_mlp_backward_multi_head */
+/* the safe-SAC critic losses of one update_critic (src/ssac.py:284-435), formed by
+ * drpo_mlp_backward_multi_head */
 typedef struct {
   int64_t B;
   int C;
@@ -371,17 +372,17 @@ typedef struct {
   uint64_t seed, ctr;
   const float *q0, *q1;
   const float *mu, *ls;
-  float *dq0, *dq1, *dmu, *dls;
-  float* loss; /* [2] accumulated: critic loss, constraint-critic loss */
-  float* loss_part;   /* drpo_mlp_backward_multi_head only: per-workgroup loss partials instead of
-                         atomics into loss: [3][row tiles] = twin 0, twin 1, certificate (summed by
-                         a drpo_mlp_wgrad_sums reduction) */
+  float* loss; /* [2]: critic loss, constraint-critic loss (the sums of loss_part) */
+  float* loss_part;   /* per-workgroup loss partials, no atomics: [3][row tiles] = twin 0, twin 1,
+                         certificate (summed into loss by a drpo_mlp_wgrad_sums reduction) */
   /* constrained_fcn='cost' (src/ssac.py:306-310): certificate target = violation + discount *
      (1 - done) * mu_t, MSE loss (distributional must be 0); v = the batch's violation flags */
   int cost;
   const uint8_t* v;
 } drpo_critic_head_t;
 
+/* one job; head, head2, pair, pre, post, post_x and ccb_out are refused (the multi launch
+ * runs them) */
 int drpo_mlp_forward(const drpo_mlp_fwd_t* desc /* host */, drpo_stream_t stream);
 /* Up to 8 independent forward jobs (different inputs / nets, e.g. every forward of
  * one SAC loss that does not depend on another) in ONE launch, each with an
@@ -389,17 +390,19 @@ int drpo_mlp_forward(const drpo_mlp_fwd_t* desc /* host */, drpo_stream_t stream
  * (read by the kernel; static across calls), jobs_host: for the grid. */
 int drpo_mlp_forward_multi(const drpo_mlp_fwd_t* jobs_host, const drpo_mlp_fwd_t* jobs_dev, int njobs, uint64_t seed,
                            uint64_t ctr, drpo_stream_t stream);
+/* one job, upstream DRPO_UPSTREAM_GOUT */
 int drpo_mlp_backward(const drpo_mlp_bwd_t* desc /* host */, drpo_stream_t stream);
 /* independent backward-data jobs in one launch (descriptors in device memory) */
 int drpo_mlp_backward_multi(const drpo_mlp_bwd_t* jobs_host, const drpo_mlp_bwd_t* jobs_dev, int njobs,
                             drpo_stream_t stream);
 /* the same with the critic losses fused in (update_critic, src/ssac.py:284-456): jobs with
  * upstream = DRPO_UPSTREAM_CRITIC / _CERT form their output gradients from `head` (the
- * forward outputs, targets and batch of drpo_critic_head_t; its dq0 / dq1 / dmu / dls are
- * not written, loss[0] / loss[1] are accumulated) -- no separate head launch */
+ * forward outputs, targets and batch of drpo_critic_head_t), leaving the loss partials in
+ * head->loss_part -- no separate head launch */
 int drpo_mlp_backward_multi_head(const drpo_mlp_bwd_t* jobs_host, const drpo_mlp_bwd_t* jobs_dev, int njobs,
                                  const drpo_critic_head_t* head /* host */, drpo_stream_t stream);
-/* the actor update's backward launches with actor_upstream / squash_backward fused in */
+/* the actor update's backward launches: jobs with upstream >= DRPO_UPSTREAM_ACTOR_CC form
+ * their output gradients from `head` */
 int drpo_mlp_backward_multi_actor(const drpo_mlp_bwd_t* jobs_host, const drpo_mlp_bwd_t* jobs_dev, int njobs,
                                   const drpo_actor_head_t* head /* host */, drpo_stream_t stream);
 /* the model fit's backward with the NLL loss fused in: desc->upstream = DRPO_UPSTREAM_ENS,
@@ -512,30 +515,10 @@ int drpo_cc_dist(const float* mu, const float* lsraw, int64_t n, int mode, float
 int drpo_cc_head(const float* mu, const float* lsraw, int64_t B, int C, int distributional, float std_ratio,
                  float log_std_min, float log_std_max, float* ubmax, int* argmax, drpo_stream_t stream);
 
-
-/* compute_target + compute_cons_target + critic / constraint-critic losses and
- * their output gradients (src/ssac.py:284-435) */
-int drpo_critic_head(const drpo_critic_head_t* p /* host */, drpo_stream_t stream);
-
-/* dL/d outputs of the critic and constraint critic for actor_loss (src/ssac.py:458-505) */
-int drpo_actor_upstream(int64_t B, int C, int distributional, float std_ratio, float log_std_min, float log_std_max,
-                        const float* lams, const float* mu_a, const float* ls_a, const float* mu_s, const float* ls_s,
-                        float* gq, float* gmu_a, float* gls_a, float* gmu_s, float* gls_s,
-                        float lam_upper_bound /* > 0: lams holds the MLPMultiplier's raw output x and
-                                                 lam = ub/2 (1 + tanh(2x/ub)) (src/ssac.py:107-111) is
-                                                 applied here; 0: lams holds lam */,
-                        float fixed_lam, float clamp_lb, float clamp_ub /* lams == NULL (scalar-multiplier
-                                                 solver, mlp_multiplier = False): lam = fixed_lam and the
-                                                 certificate term is clamp(Qc, lb, ub) (src/ssac.py:481-484) */,
-                        drpo_stream_t stream);
-
-/* chain rule through rsample/tanh/log_prob to the actor head; alpha-loss sum */
-int drpo_squash_backward(int64_t B, int A, const float* raw, const float* u, const float* e, const float* dA,
-                         const float* dA2 /* optional second dL/da term, summed: dA + dA2 */, const float* log_alpha, float lp_scale, const float* logp, float target_entropy,
-                         float* alpha_sum, float* draw, drpo_stream_t stream);
-
-/* d alpha_loss / d log_alpha (src/ssac.py:498-501) */
-int drpo_alpha_grad(const float* log_alpha, const float* alpha_sum, int64_t B, float* grad, drpo_stream_t stream);
+/* The critic / certificate losses, the actor losses' output gradients and the
+ * squashed-Gaussian backward have no launch of their own: drpo_mlp_backward_multi_head and
+ * drpo_mlp_backward_multi_actor form them in the backward launch; the alpha gradient is a
+ * drpo_optim_step segment (grad_from_sum). */
 
 /* multiplier loss gradient w.r.t. the MLPMultiplier output (src/ssac.py:529-568). x == NULL
  * (scalar multiplier, src/ssac.py:564-566): *loss accumulates sum_i clamp(actor_qc_i -
@@ -628,8 +611,8 @@ typedef struct {
   const drpo_pack_map_t* map; /* optional (device): packed mirrors to refresh */
   const float* grad_from_sum; /* optional (device scalar): the gradient of element i is
                                  -exp(p_i) * (*grad_from_sum / grad_sum_rows) instead of g[i]:
-                                 d alpha_loss / d log_alpha from the alpha-loss sum of
-                                 drpo_squash_backward (src/ssac.py:498-501), so the SAC
+                                 d alpha_loss / d log_alpha from the alpha-loss sum of the
+                                 DRPO_UPSTREAM_SQUASH backward (src/ssac.py:498-501), so the SAC
                                  temperature needs no separate gradient launch */
   int64_t grad_sum_rows;
   int grad_from_sum_kind;     /* 0: -exp(p_i) * sum / rows (the SAC temperature, alpha loss);

@@ -18,7 +18,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     import bench
-    from drpo_amd.sac_step import LaunchProfiler
+    from drpo_amd.mlp_desc import LaunchProfiler
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--batch', type=int, default=4096)
