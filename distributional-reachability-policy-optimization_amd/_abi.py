@@ -116,17 +116,12 @@ PROTOTYPES = {
     'drpo_optim_step': (c_int, [POINTER(OptimSeg), c_int, P]),
     'drpo_grad_sumsq_multi': (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(c_void_p), c_int, P]),
     'drpo_pack_weights': (c_int, [POINTER(PackItem), c_int, P]),
-    'drpo_ens_gather': (c_int, [P, P, P, P, c_int64, P, c_int64, c_int64, P, c_uint64, c_uint64, c_int, c_int, P, P,
-                                P, P]),
     'drpo_ens_gather_steps': (c_int, [P, P, P, P, c_int64, P, c_int64, c_int64, c_int64, P, c_uint64, c_uint64,
                                       c_int, c_int, P, P, P, P]),
     'drpo_ens_head': (c_int, [P, P, P, c_int64, c_int64, c_int, c_int, P, P, P, P, c_uint64, c_uint64, P, P, P, P,
                               P]),
     'drpo_ens_loss_workspace_size': (c_size_t, [c_int64, c_int, c_int]),
-    'drpo_ens_loss': (c_int, [P, P, P, c_int64, P, c_int64, c_int64, c_int, c_int, P, P, c_float, P, P, P, P, P, P,
-                              P, P, P]),
-    'drpo_ens_loss_partials': (c_int, [P, P, P, c_int64, P, c_int64, c_int64, c_int, c_int, P, P, c_float, P, P, P,
-                                       P, P, P, P, P, POINTER(EnsReduce), P]),
+    'drpo_ens_loss': (c_int, [POINTER(EnsUpstream), POINTER(EnsReduce), P, P, POINTER(EnsReduce), P]),
 }
 
 

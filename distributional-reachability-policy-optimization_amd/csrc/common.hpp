@@ -121,6 +121,10 @@ __device__ __forceinline__ float fast_softplus(float x) {   // max(x, 0) + log1p
   const float y = __builtin_amdgcn_exp2f(-1.44269504088896341f * fabsf(x));
   return fmaxf(x, 0.f) + 0.69314718055994531f * __builtin_amdgcn_logf(1.f + y);
 }
+// torch softplus backward (the sigmoid, threshold 20) on v_exp_f32 + v_rcp_f32: the flavour of
+// the SAC heads (critic_rows.hpp) and of the fused fit kernels' NLL (ens_nll.hpp, which also
+// has the libm flavour, sp_grad_exact)
+__device__ __forceinline__ float sp_grad(float x) { return x > 20.f ? 1.f : __builtin_amdgcn_rcpf(1.f + fast_exp(-x)); }
 __device__ __forceinline__ float fast_tanh(float x) {        // 1 - 2 / (exp(2x) + 1), saturating
   return 1.f - 2.f * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(2.88539008177792682f * x) + 1.f);
 }

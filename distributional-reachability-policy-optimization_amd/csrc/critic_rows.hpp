@@ -23,7 +23,7 @@ __device__ __forceinline__ float cr_softplus(float x) {   // torch softplus (bet
   return fmaxf(x, 0.f) + l1p;
 }
 
-__device__ __forceinline__ float sp_grad(float x) { return x > 20.f ? 1.f : cr_rcp(1.f + cr_exp(-x)); }
+// (the softplus derivative of these forms is sp_grad, common.hpp: cr_rcp(1 + cr_exp(-x)))
 
 __device__ __forceinline__ float cc_std(float l, float lmin, float lmax) {
   float ls = lmax - cr_softplus(lmax - l);

@@ -1,8 +1,8 @@
 // Row-wise kernels around the fused ensemble MLP (mlp.hip) for the dynamics
 // ensemble API and its fit (src/dynamics.py:112-253):
 //
-//  drpo_ens_gather  fit / holdout minibatch: chronological replay indices (recorded
-//                   or Philox) -> raw states, actions and targets [s', r]
+//  drpo_ens_gather_steps  fit / holdout minibatches: chronological replay indices
+//                   (recorded or Philox) -> raw states, actions and targets [s', r]
 //                   (src/dynamics.py:156-166,175-177; SampleBuffer.get order,
 //                   src/sampling.py:87-92)
 //  drpo_ens_head    Gaussian head: mu = diff + [s, 0], the soft log-var clamp, and
@@ -13,23 +13,11 @@
 //                   (src/dynamics.py:143-153,236-253)
 // All are HBM/latency-bound epilogues; the GEMM work is in mlp.hip.
 #include "common.hpp"
-#include "ens_reduce.hpp"
+#include "ens_nll.hpp"
 
 using namespace drpo;
 
 namespace {
-
-// torch softplus backward: x > 20 ? 1 : e^x / (e^x + 1)
-__device__ __forceinline__ float sp_grad(float x) {
-  if (x > 20.f) return 1.f;
-  const float z = expf(x);
-  return z / (z + 1.f);
-}
-
-__device__ __forceinline__ float lv_clamp(float raw, float lo, float hi) {
-  const float l1 = hi - softplusf(hi - raw);
-  return lo + softplusf(l1 - lo);
-}
 
 __device__ __forceinline__ int64_t chrono_to_phys(int64_t j, int64_t ptr, int64_t cap) {
   // SampleBuffer._get1: when wrapped, chronological order starts at ptr % cap
@@ -91,24 +79,16 @@ DRPO_API int drpo_ens_gather_steps(const float* states, const float* actions, co
   hipStream_t stream = (hipStream_t)stream_;
   DRPO_REQUIRE(states && actions && next_states && rewards && cap >= 1 && rows >= 0 && steps >= 0 && S >= 1 &&
                    A >= 1,
-               "drpo_ens_gather: bad arguments");
-  DRPO_REQUIRE(ptr_dev || ptr >= 1, "drpo_ens_gather: empty buffer");
+               "drpo_ens_gather_steps: bad arguments");
+  DRPO_REQUIRE(ptr_dev || ptr >= 1, "drpo_ens_gather_steps: empty buffer");
   const int64_t elems = steps * rows * (2 * S + A + 1);
   if (elems == 0) return DRPO_OK;
-  DRPO_REQUIRE((elems + 255) / 256 <= 0x7fffffff, "drpo_ens_gather: %lld elements", (long long)elems);
+  DRPO_REQUIRE((elems + 255) / 256 <= 0x7fffffff, "drpo_ens_gather_steps: %lld elements", (long long)elems);
   ens_gather_kernel<<<(unsigned)((elems + 255) / 256), 256, 0, stream>>>(states, actions, next_states, rewards, ptr,
                                                                          ptr_dev, cap, rows, steps, idx, seed, ctr,
                                                                          S, A, xs, xa, xt);
   DRPO_LAUNCH_CHECK("ens_gather");
   return DRPO_OK;
-}
-
-DRPO_API int drpo_ens_gather(const float* states, const float* actions, const float* next_states,
-                             const float* rewards, int64_t ptr, const int64_t* ptr_dev, int64_t cap, int64_t rows,
-                             const int64_t* idx, uint64_t seed, uint64_t ctr, int S, int A, float* xs, float* xa,
-                             float* xt, drpo_stream_t stream) {
-  return drpo_ens_gather_steps(states, actions, next_states, rewards, ptr, ptr_dev, cap, rows, 1, idx, seed, ctr, S,
-                               A, xs, xa, xt, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -201,6 +181,9 @@ __global__ __launch_bounds__(256) void ens_loss_kernel(const float* __restrict__
     const float hi = maxlv[k], lo = minlv[k];
     for (int64_t row = r0 + rl; row < r1; row += RP) {
       const int64_t o = ((int64_t)z * b + row) * S1 + k;
+      // nll_element (ens_nll.hpp) with sp_grad_exact for sp_grad, written out: through the helper
+      // (templated on the flavour, the gradients behind a flag) this kernel took 801 instructions
+      // and 51 VGPRs against 795 and 44 (profiles/fit_refactor)
       const float raw = LVR[o];
       const float l1 = hi - softplusf(hi - raw);
       const float l = lo + softplusf(l1 - lo);
@@ -210,7 +193,7 @@ __global__ __launch_bounds__(256) void ens_loss_kernel(const float* __restrict__
       acc += diff * diff * iv + l;
       if (grads) {
         const float dl = (1.f - diff * diff * iv) * g;
-        const float s1 = sp_grad(l1 - lo), s2 = sp_grad(hi - raw);
+        const float s1 = sp_grad_exact(l1 - lo), s2 = sp_grad_exact(hi - raw);
         gD[o] = -2.f * diff * iv * g;
         gLVR[o] = dl * s1 * s2;
         cmin += dl * (1.f - s1);
@@ -218,9 +201,7 @@ __global__ __launch_bounds__(256) void ens_loss_kernel(const float* __restrict__
       }
     }
   }
-  float* part_mse = part;
-  float* part_min = part_mse + (size_t)Z * nbx;
-  float* part_max = part_min + (size_t)Z * nbx * S1;
+  const EnsPartials<float> P(part, Z, nbx, S1);
   float v = acc * inv_n;
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
   if ((tid & 63) == 0) red[tid >> 6] = v;
@@ -228,63 +209,47 @@ __global__ __launch_bounds__(256) void ens_loss_kernel(const float* __restrict__
   rmax[tid] = cmax;
   __syncthreads();
   const size_t pb = (size_t)z * nbx + bx;
-  if (tid == 0) part_mse[pb] = red[0] + red[1] + red[2] + red[3];
+  if (tid == 0) P.mse[pb] = red[0] + red[1] + red[2] + red[3];
   if (grads && tid < S1) {
     float a0 = 0.f, a1 = 0.f;
     for (int q = 0; q < RP; ++q) {
       a0 += rmin[q * KP + tid];
       a1 += rmax[q * KP + tid];
     }
-    part_min[pb * S1 + tid] = a0;
-    part_max[pb * S1 + tid] = a1;
+    P.min[pb * S1 + tid] = a0;
+    P.max[pb * S1 + tid] = a1;
   }
 }
 
 // per-member NLL, total loss, bound gradients from the block partials
-// (ens_reduce.hpp; also run as the last block of a drpo_mlp_wgrad_reduce launch)
+// (ens_nll.hpp; also run as the last block of a drpo_mlp_wgrad_reduce launch)
 __global__ __launch_bounds__(256) void ens_loss_reduce_kernel(drpo_ens_reduce_t r) {
   ens_loss_reduce_block(r, (const drpo_wgrad_adam_t*)nullptr);
 }
 
-// rows per loss workgroup: one row per thread (256 / KP rows of KP column lanes)
-static int loss_rows(int S1);
-
-static int loss_kp(int S1) {
-  int kp = 16;
-  while (kp < S1) kp <<= 1;
-  return kp;
-}
-
-static int loss_rows(int S1) { return 256 / loss_kp(S1); }
-
 DRPO_API size_t drpo_ens_loss_workspace_size(int64_t b, int S, int Z) {
   const int rows = loss_rows(S + 1);
-  const size_t nbx = (size_t)((b + rows - 1) / rows);
-  return sizeof(float) * (size_t)Z * nbx * (1 + 2 * (size_t)(S + 1));
+  return EnsPartials<float>::bytes(Z, (size_t)((b + rows - 1) / rows), S + 1);
 }
 
-static int ens_loss_launch(const float* D, const float* LVR, const float* s, int64_t s_zstride, const float* t,
-                           int64_t t_zstride, int64_t b, int S, int Z, const float* minlv, const float* maxlv,
-                           float weight, const float* gscale, float* mse, float* loss, float* gD, float* gLVR,
-                           float* gmin, float* gmax, void* workspace, drpo_ens_reduce_t* reduce_out,
-                           drpo_stream_t stream_) {
+DRPO_API int drpo_ens_loss(const drpo_ens_upstream_t* up, const drpo_ens_reduce_t* red_in, float* gD, float* gLVR,
+                           drpo_ens_reduce_t* reduce_out, drpo_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  DRPO_REQUIRE(D && LVR && s && t && minlv && maxlv && mse && workspace && b >= 1 && S >= 1 &&
-                   S + 1 <= LOSS_MAXS1 && Z >= 1,
-               "drpo_ens_loss: bad arguments");
-  DRPO_REQUIRE(!gD == !gLVR && !gD == !gmin && !gD == !gmax, "drpo_ens_loss: gradient outputs all or none");
-  DRPO_REQUIRE(Z <= 256, "drpo_ens_loss: at most 256 members");
-  const int rows = loss_rows(S + 1);
-  const int64_t nbx64 = (b + rows - 1) / rows;
-  DRPO_REQUIRE(nbx64 <= (1 << 30), "drpo_ens_loss: too many rows");
-  const int nbx = (int)nbx64;
-  ens_loss_kernel<<<dim3((unsigned)nbx, Z), 256, 0, stream>>>(D, LVR, s, s_zstride, t, t_zstride, b, S, Z,
-                                                             loss_kp(S + 1), minlv, maxlv, gscale, gD, gLVR,
-                                                             (float*)workspace);
+  if (const int e = ens_upstream_check("drpo_ens_loss", up)) return e;
+  DRPO_REQUIRE(red_in, "drpo_ens_loss: null red_in");
+  DRPO_REQUIRE(!gD == !gLVR && !gD == !red_in->gmin && !gD == !red_in->gmax,
+               "drpo_ens_loss: gradient outputs (gD, gLVR, gmin, gmax) all or none");
+  const int S1 = up->S + 1, rows = loss_rows(S1);
+  const int nbx = (int)((up->b + rows - 1) / rows);
+  const drpo_ens_reduce_t r = ens_reduce_from(*up, *red_in, nbx);
+  if (const int e = ens_reduce_check("drpo_ens_loss", &r)) return e;
+  ens_loss_kernel<<<dim3((unsigned)nbx, up->Z), 256, 0, stream>>>(up->D, up->LVR, up->s, up->s_zstride, up->t,
+                                                                  up->t_zstride, up->b, up->S, up->Z, loss_kp(S1),
+                                                                  up->minlv, up->maxlv, up->gscale, gD, gLVR,
+                                                                  up->part);
   DRPO_LAUNCH_CHECK("ens_loss");
-  const drpo_ens_reduce_t r{(const float*)workspace, nbx, Z, S + 1, minlv, maxlv, weight, gscale, mse, loss, gmin, gmax};
   if (reduce_out) {
-    *reduce_out = r;   // deferred: the caller runs it (drpo_mlp_wgrad_reduce)
+    *reduce_out = r;   // deferred: the caller runs it (drpo_mlp_wgrad_reduce, drpo_ens_loss_reduce)
     return DRPO_OK;
   }
   ens_loss_reduce_kernel<<<1, 256, 0, stream>>>(r);
@@ -292,28 +257,8 @@ static int ens_loss_launch(const float* D, const float* LVR, const float* s, int
   return DRPO_OK;
 }
 
-DRPO_API int drpo_ens_loss(const float* D, const float* LVR, const float* s, int64_t s_zstride, const float* t,
-                           int64_t t_zstride, int64_t b, int S, int Z, const float* minlv, const float* maxlv,
-                           float weight, const float* gscale, float* mse, float* loss, float* gD, float* gLVR,
-                           float* gmin, float* gmax, void* workspace, drpo_stream_t stream) {
-  return ens_loss_launch(D, LVR, s, s_zstride, t, t_zstride, b, S, Z, minlv, maxlv, weight, gscale, mse, loss, gD,
-                         gLVR, gmin, gmax, workspace, nullptr, stream);
-}
-
-DRPO_API int drpo_ens_loss_partials(const float* D, const float* LVR, const float* s, int64_t s_zstride,
-                                    const float* t, int64_t t_zstride, int64_t b, int S, int Z, const float* minlv,
-                                    const float* maxlv, float weight, const float* gscale, float* mse, float* loss,
-                                    float* gD, float* gLVR, float* gmin, float* gmax, void* workspace,
-                                    drpo_ens_reduce_t* reduce_out, drpo_stream_t stream) {
-  DRPO_REQUIRE(reduce_out, "drpo_ens_loss_partials: reduce_out is required");
-  return ens_loss_launch(D, LVR, s, s_zstride, t, t_zstride, b, S, Z, minlv, maxlv, weight, gscale, mse, loss, gD,
-                         gLVR, gmin, gmax, workspace, reduce_out, stream);
-}
-
 DRPO_API int drpo_ens_loss_reduce(const drpo_ens_reduce_t* red, drpo_stream_t stream) {
-  DRPO_REQUIRE(red && red->part && red->mse && red->Z >= 1 && red->Z <= 256 && red->S1 >= 1 &&
-                   red->S1 <= LOSS_MAXS1 && red->nbx >= 1 && red->minlv && red->maxlv,
-               "drpo_ens_loss_reduce: bad reduction");
+  if (const int e = ens_reduce_check("drpo_ens_loss_reduce", red)) return e;
   ens_loss_reduce_kernel<<<1, 256, 0, (hipStream_t)stream>>>(*red);
   DRPO_LAUNCH_CHECK("ens_loss_reduce");
   return DRPO_OK;

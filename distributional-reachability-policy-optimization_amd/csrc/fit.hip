@@ -20,14 +20,14 @@
 // and the log-var outputs): one 200x200 layer more per workgroup than the two launches,
 // in one phase with the output layers (SIMD-balanced 7/6/6/7 blocks).
 #include "common.hpp"
-#include "critic_rows.hpp"
+#include "ens_nll.hpp"
 
 using namespace drpo;
 
 namespace {
 constexpr int FF_NW = 8;
 constexpr int FF_NT = FF_NW * 64;
-constexpr int FF_ROWS = 16;
+constexpr int FF_ROWS = ENS_TILE_ROWS;
 constexpr int FF_LDH = 264;   // == 8 (mod 64): conflict-free A-fragment reads
 }  // namespace
 
@@ -385,6 +385,8 @@ __device__ __forceinline__ void fit_fb_body(FitK& k, float* smem) {
         const int64_t o = ((int64_t)z * b + row0 + nr) * S1 + nk;
         const float D = narrow_pair_sum<FF_NW, 1>(red, 0, nr, nk) + n_bd;
         const float raw = narrow_pair_sum<FF_NW, 1>(red, 1, nr, nk) + n_bl;
+        // nll_element (ens_nll.hpp), written out: through the helper the compiler contracts
+        // these products differently and the gradients move in the last bit (profiles/fit_refactor)
         const float hi = n_hi, lo = n_lo;
         const float l1v = hi - softplusf(hi - raw);
         const float l = lo + softplusf(l1v - lo);
@@ -410,26 +412,8 @@ __device__ __forceinline__ void fit_fb_body(FitK& k, float* smem) {
     if ((tid & 63) == 0) s_mse[tid >> 6] = v;
     lds_barrier();
     FSTAMP(5);
-    if (h == 0) {
-      float* part_mse = U.part;
-      float* part_min = part_mse + (size_t)U.Z * nbx;
-      float* part_max = part_min + (size_t)U.Z * nbx * S1;
-      const size_t pb = (size_t)z * nbx + bx;
-      if (tid == 0) {
-        float t = 0.f;
-        for (int w = 0; w < FF_NW; ++w) t += s_mse[w];
-        part_mse[pb] = t;
-      }
-      if (tid < S1) {
-        float a0 = 0.f, a1 = 0.f;
-        for (int r = 0; r < FF_ROWS; ++r) {
-          a0 += T2[r * FF_LDH + tid];
-          a1 += T2[r * FF_LDH + 64 + tid];
-        }
-        part_min[pb * S1 + tid] = a0;
-        part_max[pb * S1 + tid] = a1;
-      }
-    }
+    ens_tile_partials<FF_NW>(EnsPartials<float>(U.part, U.Z, (int)nbx, S1), (size_t)z * nbx + bx, S1, s_mse, T2,
+                             T2 + 64, FF_LDH, h == 0);
   }
   // ---- backward: head h's hidden dZ, its trunk-L2 share, its trunk-L1 share ------------
   auto& tb = Bd.net[0].L[1];
@@ -479,6 +463,7 @@ static_assert(sizeof(FitFbArgs) <= 4096, "fused fit kernarg");
 DRPO_API int drpo_ens_fit_fb(const drpo_mlp_fwd_t* f, const drpo_mlp_bwd_t* bd, const drpo_ens_upstream_t* up,
                              const drpo_ens_reduce_t* red_in, drpo_ens_reduce_t* reduce_out, drpo_stream_t stream) {
   DRPO_REQUIRE(f && bd && up && red_in && reduce_out, "drpo_ens_fit_fb: null argument");
+  if (const int e = ens_upstream_check("drpo_ens_fit_fb", up, /*heads=*/false)) return e;
   const drpo_mlp_net_t &tr = f->net[0], &h1 = f->net[1], &h2 = f->net[2];
   const int S1 = up->S + 1;
   const int din0 = f->cols[0] + f->cols[1];
@@ -498,17 +483,10 @@ DRPO_API int drpo_ens_fit_fb(const drpo_mlp_fwd_t* f, const drpo_mlp_bwd_t* bd, 
   ok = ok && bd->net[0].L[0].dz && bd->net[0].L[0].dz2 && bd->net[0].L[1].dz && bd->net[0].L[1].dz2;
   DRPO_REQUIRE(ok, "drpo_ens_fit_fb: needs the ensemble trunk [S+A <= 64 -> H -> H] and two heads [H -> H -> S+1 <= 16] "
                    "(swish, H = 200 | 256) with the split-heads trunk dZ (dz | dz2)");
-  DRPO_REQUIRE(up->s && up->t && up->minlv && up->maxlv && up->part && up->b >= 1 && up->Z >= 1 && up->Z <= 256,
-               "drpo_ens_fit_fb: bad upstream");
-  const int nbx = (int)((up->b + FF_ROWS - 1) / FF_ROWS);
-  *reduce_out = *red_in;
-  reduce_out->part = up->part;
-  reduce_out->nbx = nbx;
-  reduce_out->Z = up->Z;
-  reduce_out->S1 = S1;
-  reduce_out->minlv = up->minlv;
-  reduce_out->maxlv = up->maxlv;
-  reduce_out->gscale = up->gscale;
+  const int nbx = ens_tile_nbx(up->b);
+  const drpo_ens_reduce_t r = ens_reduce_from(*up, *red_in, nbx);
+  if (const int e = ens_reduce_check("drpo_ens_fit_fb", &r)) return e;
+  *reduce_out = r;
   FitFbArgs a{*f, *bd, *up};
   const size_t lds = sizeof(float) * ((size_t)8 * FF_ROWS * FF_LDH + FF_NW * 256);
   fit_fb_kernel<<<dim3((unsigned)nbx, 2, (unsigned)up->Z), FF_NT, lds, (hipStream_t)stream>>>(a);

@@ -14,7 +14,7 @@
 
 #include "common.hpp"
 #include "sac_rows.hpp"
-#include "ens_reduce.hpp"
+#include "ens_nll.hpp"
 
 using namespace drpo;
 
@@ -810,19 +810,9 @@ __device__ __forceinline__ void ens_upstream(EnsUpK& u, const drpo_mlp_bwd_net_t
       const int64_t row = row0 + r;
       const int64_t o = ((int64_t)z * b + row) * S1 + k;
       const float hi = gload(u.maxlv + k), lo = gload(u.minlv + k);
-      const float raw = gload(u.LVR + o);
-      const float l1 = hi - softplusf(hi - raw);
-      const float l = lo + softplusf(l1 - lo);
-      const float m = gload(u.D + o) + (k < S ? gload(u.s + (int64_t)z * u.s_zstride + row * S + k) : 0.f);
-      const float diff = gload(u.t + (int64_t)z * u.t_zstride + row * S1 + k) - m;
-      const float iv = expf(-l);
-      acc += diff * diff * iv + l;
-      const float dl = (1.f - diff * diff * iv) * g;
-      const float s1 = sp_grad(l1 - lo), s2 = sp_grad(hi - raw);
-      gd = -2.f * diff * iv * g;
-      gl = dl * s1 * s2;
-      cmn = dl * (1.f - s1);
-      cmx = dl * s1 * (1.f - s2);
+      acc += nll_element(gload(u.D + o), gload(u.LVR + o),
+                         k < S ? gload(u.s + (int64_t)z * u.s_zstride + row * S + k) : 0.f,
+                         gload(u.t + (int64_t)z * u.t_zstride + row * S1 + k), lo, hi, g, gd, gl, cmn, cmx);
       if (split < 0 && hd.L[1].dz) gstore(hd.L[1].dz + o, gd);
       if (split < 0 && hl.L[1].dz) gstore(hl.L[1].dz + o, gl);
     }
@@ -839,26 +829,10 @@ __device__ __forceinline__ void ens_upstream(EnsUpK& u, const drpo_mlp_bwd_net_t
   if ((tid & 63) == 0) s_red[tid >> 6] = v;
   lds_barrier();
   STAMPW(7);
-  const int nbx = (int)((b + FW_ROWS - 1) / FW_ROWS);
-  float* part_mse = u.part;
-  float* part_min = part_mse + (size_t)u.Z * nbx;
-  float* part_max = part_min + (size_t)u.Z * nbx * S1;
-  const size_t pb = (size_t)z * nbx + bx;
-  if (split > 0) return;
-  if (tid == 0) {
-    float t = 0.f;
-    for (int w = 0; w < FW_NW; ++w) t += s_red[w];
-    part_mse[pb] = t;
-  }
-  if (tid < S1) {
-    float a0 = 0.f, a1 = 0.f;
-    for (int r = 0; r < FW_ROWS; ++r) {
-      a0 += Cm[r * LDH + tid];
-      a1 += Cx[r * LDH + tid];
-    }
-    part_min[pb * S1 + tid] = a0;
-    part_max[pb * S1 + tid] = a1;
-  }
+  static_assert(FW_ROWS == ENS_TILE_ROWS, "the NLL upstream writes one partial block per 16-row tile");
+  const int nbx = ens_tile_nbx(b);
+  ens_tile_partials<FW_NW>(EnsPartials<float>(u.part, u.Z, nbx, S1), (size_t)z * nbx + bx, S1, s_red, Cm, Cx, LDH,
+                           split <= 0);
 }
 
 // the actor update's head (drpo_mlp_backward_multi_actor), read in place from kernarg
@@ -1288,6 +1262,7 @@ DRPO_API int drpo_mlp_backward_ens(const drpo_mlp_bwd_t* a, const drpo_ens_upstr
                                    drpo_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   DRPO_REQUIRE(a && up && red_in && reduce_out, "drpo_mlp_backward_ens: null argument");
+  if (const int e = ens_upstream_check("drpo_mlp_backward_ens", up)) return e;
   if (const int e = check_bwd("drpo_mlp_backward_ens", 0, a)) return e;
   DRPO_REQUIRE(a->upstream == DRPO_UPSTREAM_ENS && a->trunk && a->nnets == 3 && a->nbatch == up->Z &&
                    a->rows == up->b,
@@ -1298,18 +1273,10 @@ DRPO_API int drpo_mlp_backward_ens(const drpo_mlp_bwd_t* a, const drpo_ens_upstr
   shape.split_heads = 0;
   DRPO_REQUIRE(bwd_paired_heads(shape) && a->net[1].L[1].dout == up->S + 1,
                "drpo_mlp_backward_ens: heads must be paired [H -> 200|256 -> S+1] (S+1 <= 64)");
-  DRPO_REQUIRE(up->D && up->LVR && up->s && up->t && up->minlv && up->maxlv && up->part && up->b >= 1 &&
-                   up->Z >= 1 && up->Z <= 256,
-               "drpo_mlp_backward_ens: bad upstream");
-  const int nbx = (int)((up->b + FW_ROWS - 1) / FW_ROWS);
-  *reduce_out = *red_in;
-  reduce_out->part = up->part;
-  reduce_out->nbx = nbx;
-  reduce_out->Z = up->Z;
-  reduce_out->S1 = up->S + 1;
-  reduce_out->minlv = up->minlv;
-  reduce_out->maxlv = up->maxlv;
-  reduce_out->gscale = up->gscale;
+  const int nbx = ens_tile_nbx(up->b);
+  const drpo_ens_reduce_t r = ens_reduce_from(*up, *red_in, nbx);
+  if (const int e = ens_reduce_check("drpo_mlp_backward_ens", &r)) return e;
+  *reduce_out = r;
   BwdEnsArgs m{*a, *up};
   dim3 grid((unsigned)nbx, a->split_heads ? 2 : 1, a->nbatch);
   mlp_bwd_ens_kernel<<<grid, FW_NT, bwd_lds(), stream>>>(m);

@@ -7,12 +7,33 @@ small row-wise kernels (csrc/ensemble.hip):
 
   forward     drpo_mlp_forward (trunk + diff head + log-var head in one launch)
               -> drpo_ens_head (residual mean, soft log-var clamp [, sample])
-  fit step    drpo_ens_gather -> forward (saving activations) -> drpo_ens_loss
-              (NLL + bound term + output grads) -> drpo_mlp_backward (heads into
-              the shared trunk) -> drpo_mlp_wgrad (all 6 layers x E members, one
-              launch) -> drpo_adam over the whole group
-  holdout     gather -> forward with member stride 0 (the reference's
+  holdout     drpo_ens_gather_steps -> forward with member stride 0 (the reference's
               .repeat(E, 1) without the copy) -> drpo_ens_loss (no grads)
+  fit         drpo_ens_gather_steps once per chunk of steps (every step's minibatch in one
+              launch), then per step FitPlan.compute and FitPlan.apply
+
+FitPlan.compute -- forward, NLL and backward-data, leaving the NLL's block partials and
+their reduction as data (drpo_ens_reduce_t). The first variant whose condition holds:
+  1. drpo_ens_fit_fb, all three in one launch: the shapes of ens_fb_shapes (the reference
+     default: two trunk layers, one hidden layer per head, width 200 | 256, S+A <= 64,
+     S+1 <= 16), a split-heads grid, and the switches fit_fb_enabled and split_bwd on.
+  2. drpo_mlp_forward + drpo_mlp_backward_ens, the NLL gradients formed inside the
+     backward launch: the shapes of ens_fused_shapes (heads [H -> 200|256 -> S+1 <= 64]).
+     One workgroup per (row tile, head) at split-heads grids with split_bwd on, else
+     one per row tile with the heads paired.
+  3. drpo_mlp_forward + drpo_ens_loss (deferred reduction) + drpo_mlp_backward: any other
+     model, e.g. head_hidden_layers = 2.
+FitPlan.apply -- weight gradients of all 6 layers x members, the NLL reduction, Adam:
+  1. 'fused': drpo_mlp_wgrad_adam, one launch (Adam and the mirror refresh by the
+     workgroup that finishes a tile, the reduction and the bounds' Adam step by one extra
+     workgroup): compute variant 1 or 2, one process, switch fused_adam on.
+  2. 'fused-shard': the same launch for the rank's members of a member-sharded fit, while
+     a side stream runs drpo_ens_loss_reduce, the all-reduce of the shared log-var bounds'
+     gradients (the step's one collective) and their drpo_optim_step; the next step's
+     backward waits for it (after its forward has been launched).
+  3. 'separate': drpo_mlp_wgrad_reduce (the reduction as its last workgroup), the
+     gradients' all-reduce under batch data parallelism, drpo_optim_step over the group:
+     compute variant 3, batch data parallelism, or fused_adam off.
 
 The per-step ``loss.item()`` of the reference is deferred: losses land in a device
 array that is read once at the end of fit (same returned list of floats).
@@ -46,7 +67,8 @@ def split_heads(n, Z):
 
 
 def ens_fused_shapes(nets, S1):
-    """The shapes drpo_mlp_backward_ens accepts (csrc/mlp.hip): both heads
+    """Path selector: the shapes drpo_mlp_backward_ens accepts (it mirrors that entry point's
+    check in csrc/mlp.hip: bwd_paired_heads on the descriptor plus dout == S+1): both heads
     [H -> 200|256 -> S+1] with the same hidden width and activation and an identity
     output layer, S+1 <= 64, and every trunk layer at most 256 wide."""
     h1, h2 = nets[1].layers, nets[2].layers
@@ -61,9 +83,10 @@ def ens_fused_shapes(nets, S1):
 
 
 def ens_fb_shapes(nets, S, A):
-    """The shapes drpo_ens_fit_fb takes (csrc/fit.hip: the fit step's forward, NLL and
-    backward-data in one launch): trunk [S+A <= 64 -> H -> H], heads [H -> H -> S+1 <= 16],
-    swish hidden layers, identity outputs, H = 200 | 256 (the reference default:
+    """Path selector: the shapes drpo_ens_fit_fb takes (it mirrors the `ok` condition of that
+    entry point in csrc/fit.hip; the fit step's forward, NLL and backward-data in one launch):
+    trunk [S+A <= 64 -> H -> H], heads [H -> H -> S+1 <= 16], swish hidden layers, identity
+    outputs, H = 200 | 256 (the reference default:
     src/dynamics.py:59-61,85-86, hidden_dim=200, trunk_layers=2, head_hidden_layers=1)."""
     if len(nets) != 3 or S + A > 64 or S + 1 > 16:
         return False
@@ -78,6 +101,10 @@ def ens_fb_shapes(nets, S, A):
         if len(h) != 2 or h[0][2] != H or h[0][3] != H or h[0][4] != sw or h[1][3] != S + 1 or h[1][4] != 0:
             return False
     return True
+
+
+def _addr(t):
+    return 0 if t is None else t.data_ptr()
 
 
 class EnsembleEngine:
@@ -261,26 +288,34 @@ class EnsembleEngine:
             self.ws[key] = t
         return t
 
-    def _loss_args(self, nets, s, s_zs, t, t_zs, b, Z, grads, gscale=None, loss_out=None, tag='f', bound=True):
+    def _loss_descs(self, nets, s, s_zs, t, t_zs, b, Z, grads, gscale=None, loss_out=None, tag='f', bound=True):
+        """The NLL's two descriptors over a forward's head outputs: (up, red_in, mse, gD, gL).
+        up: what drpo_ens_loss, drpo_mlp_backward_ens and drpo_ens_fit_fb read; red_in: where
+        the reduction puts the per-member NLL, the loss and (grads) the bounds' gradients."""
         m = self.m
         S = m.state_dim
-        S1 = S + 1
         g = m.group
         mse = self.buf(f'{tag}.mse', Z)
-        D, LVR = nets[1].sy[-1], nets[2].sy[-1]
-        gD = gL = gmin = gmax = None
+        gD = gL = None
+        up, red_in = EnsUpstream(), EnsReduce()
+        up.D, up.LVR = nets[1].sy[-1].data_ptr(), nets[2].sy[-1].data_ptr()
+        up.s, up.s_zstride, up.t, up.t_zstride = s.data_ptr(), s_zs, t.data_ptr(), t_zs
+        up.b, up.S, up.Z = b, S, Z
+        up.minlv, up.maxlv = m.min_log_var.data_ptr(), m.max_log_var.data_ptr()
+        up.gscale = _addr(gscale)
+        up.part = self._loss_ws(tag, b, Z).data_ptr()
+        red_in.weight = float(m.log_var_bound_weight) if bound else 0.0
+        red_in.mse, red_in.loss = mse.data_ptr(), _addr(loss_out)
         if grads:
-            gD, gL = self.buf(f'{tag}.gD', Z * b, S1), self.buf(f'{tag}.gL', Z * b, S1)
-            gmin, gmax = g.view('min_log_var', g.grad), g.view('max_log_var', g.grad)
-        args = [_lib.ptr(D), _lib.ptr(LVR), _lib.ptr(s), s_zs, _lib.ptr(t), t_zs, b, S, Z, _lib.ptr(m.min_log_var),
-                _lib.ptr(m.max_log_var), float(m.log_var_bound_weight) if bound else 0.0, _lib.ptr(gscale),
-                _lib.ptr(mse), _lib.ptr(loss_out), _lib.ptr(gD), _lib.ptr(gL), _lib.ptr(gmin), _lib.ptr(gmax),
-                _lib.ptr(self._loss_ws(tag, b, Z))]
-        return args, mse, gD, gL
+            gD, gL = self.buf(f'{tag}.gD', Z * b, S + 1), self.buf(f'{tag}.gL', Z * b, S + 1)
+            red_in.gmin = g.view('min_log_var', g.grad).data_ptr()
+            red_in.gmax = g.view('max_log_var', g.grad).data_ptr()
+        return up, red_in, mse, gD, gL
 
     def _loss(self, nets, s, s_zs, t, t_zs, b, Z, grads, gscale=None, loss_out=None, tag='f', bound=True):
-        args, mse, gD, gL = self._loss_args(nets, s, s_zs, t, t_zs, b, Z, grads, gscale, loss_out, tag, bound)
-        _lib.check(_lib.lib().drpo_ens_loss(*args, _lib.stream()), 'ens_loss')
+        up, red_in, mse, gD, gL = self._loss_descs(nets, s, s_zs, t, t_zs, b, Z, grads, gscale, loss_out, tag, bound)
+        _lib.check(_lib.lib().drpo_ens_loss(ctypes.byref(up), ctypes.byref(red_in), _lib.ptr(gD), _lib.ptr(gL), None,
+                                            _lib.stream()), 'ens_loss')
         return mse, gD, gL
 
     def _backward_descs(self, nets, strides, save_x, gD, gL, b, Z):
@@ -348,12 +383,39 @@ class EnsembleEngine:
         return loss
 
     # ------------------------------------------------------------------ fit
+    def _gather(self, rb, rows, out, steps=1, idx=None, ctr=0, seed=0, device_ptr=False):
+        """Replay rows -> out = (states, actions, targets [s', r]) for `steps` minibatches of
+        `rows` rows in one launch: chronological indices idx (a tensor or an address, step k's
+        at idx[k*rows ..]) or, without, Philox randint with counters ctr + k. device_ptr: read
+        the buffer's fill pointer on the device when it keeps no host copy (a fit inside a
+        captured or asynchronous collection); otherwise the host value."""
+        m = self.m
+        ptr_dev = rb._pointer if device_ptr and rb._host_ptr is None else None
+        ptr_host = rb.pointer if not device_ptr else (rb._host_ptr or 0)
+        idx = _lib.ptr(idx) if torch.is_tensor(idx) else idx
+        _lib.check(_lib.lib().drpo_ens_gather_steps(
+            _lib.ptr(rb._states), _lib.ptr(rb._actions), _lib.ptr(rb._next_states), _lib.ptr(rb._rewards), ptr_host,
+            _lib.ptr(ptr_dev), rb.capacity, rows, steps, idx, seed, ctr, m.state_dim, m.action_dim, _lib.ptr(out[0]),
+            _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.stream()), 'ens_gather')
+
+    def _side_stream(self):
+        """The member-sharded fit's side stream and its two fence-free library events
+        (csrc/core.hip), created once per engine: (torch stream, ev_bwd, ev_done)."""
+        if getattr(self, '_side', None) is None:
+            evs = []
+            for _ in range(2):
+                e = ctypes.c_void_p()
+                _lib.check(_lib.lib().drpo_event_create(ctypes.byref(e)), 'event_create')
+                evs.append(e)
+            self._side = (torch.cuda.Stream(device=self.dev), evs[0], evs[1])
+        return self._side
+
     def fit(self, buffer, steps, noise=None):
         """fit(steps=) (src/dynamics.py:155-183). Under data parallelism the members are
         sharded over the ranks (distributed.MemberShard) unless dp_mode='batch', in which
         case every rank fits all members on its own draw and the gradients are averaged."""
         from .distributed import member_sharding
-        m, L = self.m, _lib.lib()
+        m = self.m
         nz = self._noise(noise)
         rb = getattr(buffer, '_module', buffer)
         _lib.require_device(m.group.data, rb._states)
@@ -370,120 +432,21 @@ class EnsembleEngine:
         E, b = m.ensemble_size, m.batch_size
         z0, Z = (sh.z0, sh.count) if sh is not None else (0, E)
         rows = Z * b
-        xs, xa, xt = self.buf('fit.s', rows, S), self.buf('fit.a', rows, A), self.buf('fit.t', rows, S1)
         losses = torch.empty(max(steps, 1), device=self.dev)
-        ptr_dev = rb._pointer if rb._host_ptr is None else None
-        ptr_host = rb._host_ptr if rb._host_ptr is not None else 0
-
-        def gather(count, out, full=None):
-            # parity mode: the reference's randint over all E*b rows, this shard's slice
-            idx = nz.randint(n, full or count) if nz.parity else None
-            if idx is not None and full:
-                idx = idx[z0 * b:z0 * b + count]
-            idx_t = None if idx is None else torch.from_numpy(np.ascontiguousarray(idx)).to(self.dev)
-            ctr = 0 if nz.parity else nz.next()
-            _lib.check(L.drpo_ens_gather(_lib.ptr(rb._states), _lib.ptr(rb._actions), _lib.ptr(rb._next_states),
-                                         _lib.ptr(rb._rewards), ptr_host, _lib.ptr(ptr_dev), rb.capacity, count,
-                                         _lib.ptr(idx_t), nz.seed, ctr, S, A, _lib.ptr(out[0]), _lib.ptr(out[1]),
-                                         _lib.ptr(out[2]), _lib.stream()), 'ens_gather')
-
-        g = m.group
-        g.grad.zero_()
-        if sh is None:   # batch DP: the gradient is sum-reduced, the optimizer applies 1/G
-            segs = [m.optimizer.segment(0, g.size, (0.0, 1.0), zero_grad=True, pack_map=g.pack_map(),
-                                        grad_scale=self.dp.scale)]
-        else:
-            ranges = self._shard_ranges(z0, Z)
-            lo, hi = g.offset('min_log_var'), g.offset('max_log_var') + S1
-            bounds_grad = g.grad[lo:hi]
-            pmap = g.pack_map()
-            segs = [m.optimizer.segment(a, c, (0.0, 1.0), zero_grad=True, pack_map=pmap) for a, c in ranges]
-        # the whole step is built once (descriptors point at fixed workspaces); per step
-        # only the minibatch indices / Philox counter, the loss slot and Adam's bias-
-        # corrected step sizes change
-        from ._abi import OptimSeg
-        seg_arr = [(OptimSeg * len(segs[k:k + 8]))(*segs[k:k + 8]) for k in range(0, len(segs), 8)]
-        fd, nets, strides, save_x = self._forward_desc(xs, xa, b, Z, b * S, b * A, tag='fit', save=True, z0=z0)
-        largs, _, gD, gL = self._loss_args(nets, xs, b * S, xt, b * S1, b, Z, True, loss_out=losses[0:1], tag='fit',
-                                           bound=sh is None or sh.rank == 0)
-        bd, wl = self._backward_descs(nets, strides, save_x, gD, gL, b, Z)
-        # the NLL loss rides in the backward launch (its output gradients formed in-kernel)
-        # and its reduction in the weight-gradient launch: forward, backward, wgrad, Adam.
-        # That needs the shapes drpo_mlp_backward_ens takes (the reference default:
-        # head_hidden_layers=1, 200-wide); other shapes keep the separate loss launch.
-        fused = ens_fused_shapes(nets, S1)
-        bd.upstream = 3 if fused else 0   # DRPO_UPSTREAM_ENS
-        # the reference default shapes at split-heads grids: forward + NLL + backward-data
-        # as ONE launch per (row tile, head) (drpo_ens_fit_fb)
-        fb = self.fit_fb_enabled and fused and bool(bd.split_heads) and ens_fb_shapes(nets, S, A)
-        self.fit_fb = fb
-        up = EnsUpstream()
-        up.D, up.LVR = nets[1].sy[-1].data_ptr(), nets[2].sy[-1].data_ptr()
-        up.s_zstride, up.t_zstride, up.b, up.S, up.Z = b * S, b * S1, b, S, Z
-        up.minlv, up.maxlv = m.min_log_var.data_ptr(), m.max_log_var.data_ptr()
-        up.part = self._loss_ws('fit', b, Z).data_ptr()
-        red_in = EnsReduce()
-        red_in.weight = float(m.log_var_bound_weight) if (sh is None or sh.rank == 0) else 0.0
-        red_in.mse = self.buf('fit.mse', Z).data_ptr()
-        red_in.gmin = g.view('min_log_var', g.grad).data_ptr()
-        red_in.gmax = g.view('max_log_var', g.grad).data_ptr()
-        red = EnsReduce()
-        full = E * b if sh is not None else rows
+        m.group.grad.zero_()
+        # The minibatches of a chunk of steps are gathered in ONE launch (the replay is
+        # not written during the fit); the step's descriptors are pointed at its slice.
+        # Chunks of <= 64 MB of gathered rows.
+        chunk = max(1, min(steps, (64 << 20) // (4 * (2 * S + A + 1) * max(rows, 1))))
+        mb = (self.buf('fit.s_all', chunk * rows, S), self.buf('fit.a_all', chunk * rows, A),
+              self.buf('fit.t_all', chunk * rows, S1))
+        plan = FitPlan(self, sh, mb, losses)
+        self.fit_fb, self.fit_path = plan.fb, plan.path    # (tests, probes)
+        # parity mode: the reference's randint over all E*b rows, this shard's slice
         idx_all = None
         if nz.parity and steps > 0:
-            draws = [np.asarray(nz.randint(n, full))[z0 * b:z0 * b + rows] for _ in range(steps)]
+            draws = [np.asarray(nz.randint(n, E * b))[z0 * b:z0 * b + rows] for _ in range(steps)]
             idx_all = torch.from_numpy(np.ascontiguousarray(np.stack(draws), dtype=np.int64)).to(self.dev)
-        stream = _lib.stream()
-        # Adam fused into the weight-gradient launch: single process, whole group, no clip
-        fuse = self.fused_adam and fused and sh is None and not self.dp.active and len(wl) == 1
-        # Member shard: the rank-local members take the same fused weight-
-        # gradient + Adam launch (their tiles of the group's pack map); only the shared
-        # log-var bounds' 2(S+1) gradients leave the step. Their reduction runs as its own
-        # one-block launch on a side stream as soon as the backward has written the NLL
-        # partials; the side stream then sum-all-reduces them (the step's ONE collective)
-        # and steps the bounds, overlapped with the members' launch on the main stream.
-        # The next step's backward (which reads the bounds and rewrites the partials)
-        # waits for it.
-        # (a member shard and batch DP exclude each other: member_sharding() is None under
-        # dp_mode='batch', and no shard path sum-reduces the member gradients)
-        assert sh is None or getattr(m, 'dp_mode', 'auto') != 'batch'
-        fuse_sh = self.fused_adam and fused and sh is not None and len(wl) == 1
-        self.fit_path = 'fused' if fuse else ('fused-shard' if fuse_sh else 'separate')   # (tests, probes)
-        if fuse or fuse_sh:
-            from ._abi import WgradAdam
-            opt = m.optimizer
-            opt._ensure_state()
-            pm = g.pack_map()
-            ad = WgradAdam()
-            ad.g, ad.p, ad.m, ad.v = g.grad.data_ptr(), g.data.data_ptr(), opt.m.data_ptr(), opt.v.data_ptr()
-            ad.beta1, ad.beta2 = opt.betas
-            ad.eps, ad.weight_decay = opt.eps, opt.weight_decay
-            ad.map, ad.map_host = pm.data_ptr(), ctypes.addressof(pm.host)
-            warr, wn = wl[0]
-            wws = self._wgrad_ws('fit0', warr, wn)
-        if fuse_sh:
-            bseg = (OptimSeg * 1)(m.optimizer.segment(lo, hi, (0.0, 1.0), zero_grad=True))
-            side = self.__dict__.setdefault('_side', torch.cuda.Stream(device=self.dev))
-            if getattr(self, '_side_evs', None) is None:   # fence-free library events (csrc/core.hip)
-                self._side_evs = []
-                for _ in range(2):
-                    e = ctypes.c_void_p()
-                    _lib.check(L.drpo_event_create(ctypes.byref(e)), 'event_create')
-                    self._side_evs.append(e)
-            ev_bwd, ev_done = self._side_evs
-            main_s = stream
-            side_s = ctypes.c_void_p(side.cuda_stream)
-            pending = False
-        gargs = [_lib.ptr(rb._states), _lib.ptr(rb._actions), _lib.ptr(rb._next_states), _lib.ptr(rb._rewards),
-                 ptr_host, _lib.ptr(ptr_dev), rb.capacity, rows]
-        loss_base = losses.data_ptr()
-        # The minibatches of a chunk of steps are gathered in ONE launch (the replay is
-        # not written during the fit); the step's forward / loss descriptors are pointed
-        # at its slice. Chunks of <= 64 MB of gathered rows.
-        W = 2 * S + A + 1
-        chunk = max(1, min(steps, (64 << 20) // (4 * W * max(rows, 1))))
-        cs, ca, ct = (self.buf('fit.s_all', chunk * rows, S), self.buf('fit.a_all', chunk * rows, A),
-                      self.buf('fit.t_all', chunk * rows, S1))
         for i in range(steps):
             k = i % chunk
             if k == 0:
@@ -494,70 +457,20 @@ class EnsembleEngine:
                     idx, ctr = None, nz.next()
                     for _ in range(nc - 1):
                         nz.next()
-                _lib.check(L.drpo_ens_gather_steps(*gargs, nc, idx, nz.seed, ctr, S, A, _lib.ptr(cs), _lib.ptr(ca),
-                                                   _lib.ptr(ct), stream), 'ens_gather')
-            fd.src[0], fd.src[1] = cs.data_ptr() + 4 * k * rows * S, ca.data_ptr() + 4 * k * rows * A
-            up.s, up.t = fd.src[0], ct.data_ptr() + 4 * k * rows * S1
-            red_in.loss = loss_base + 4 * i
-            if not fb:
-                _lib.check(L.drpo_mlp_forward(ctypes.byref(fd), stream), 'ensemble forward')
-            if fuse_sh and pending:           # the previous step's bounds are stepped
-                _lib.check(L.drpo_stream_wait_event(main_s, ev_done), 'stream_wait_event')
-            if fb:
-                _lib.check(L.drpo_ens_fit_fb(ctypes.byref(fd), ctypes.byref(bd), ctypes.byref(up),
-                                             ctypes.byref(red_in), ctypes.byref(red), stream), 'ensemble fit fwd+bwd')
-            elif fused:
-                _lib.check(L.drpo_mlp_backward_ens(ctypes.byref(bd), ctypes.byref(up), ctypes.byref(red_in),
-                                                   ctypes.byref(red), stream), 'ensemble backward')
-            else:
-                largs[2], largs[4], largs[14] = ctypes.c_void_p(up.s), ctypes.c_void_p(up.t), \
-                    ctypes.c_void_p(red_in.loss)
-                _lib.check(L.drpo_ens_loss_partials(*largs, ctypes.byref(red), stream), 'ens_loss')
-                _lib.check(L.drpo_mlp_backward(ctypes.byref(bd), stream), 'ensemble backward')
-            if fuse:
-                # weight gradients + the NLL reduction + Adam + mirror refresh: one launch
-                ad.lr_over_bc1, ad.bc2_sqrt = m.optimizer.step_scalars()
-                _lib.check(L.drpo_mlp_wgrad_adam(warr, wn, ctypes.byref(red), ctypes.byref(ad), wws.data_ptr(),
-                                                 wws.numel(), stream), 'ensemble wgrad + adam')
-                continue
-            if fuse_sh:
-                lr_bc1, bc2 = m.optimizer.step_scalars()
-                _lib.check(L.drpo_event_record(ev_bwd, main_s), 'event_record')
-                _lib.check(L.drpo_stream_wait_event(side_s, ev_bwd), 'stream_wait_event')
-                _lib.check(L.drpo_ens_loss_reduce(ctypes.byref(red), side_s), 'ens_loss_reduce')
-                with torch.cuda.stream(side):      # the collective on the side stream
-                    sh.sum_(bounds_grad)
-                bseg[0].lr_over_bc1, bseg[0].bc2_sqrt = lr_bc1, bc2
-                _lib.check(L.drpo_optim_step(bseg, 1, side_s), 'optim_step (log-var bounds)')
-                _lib.check(L.drpo_event_record(ev_done, side_s), 'event_record')
-                pending = True
-                ad.lr_over_bc1, ad.bc2_sqrt = lr_bc1, bc2
-                _lib.check(L.drpo_mlp_wgrad_adam(warr, wn, None, ctypes.byref(ad), wws.data_ptr(), wws.numel(),
-                                                 stream), 'ensemble wgrad + adam (member shard)')
-                continue
-            # the loss reduction rides as the last workgroup of the wgrad launch
-            self._wgrad('fit', wl, red, stream)
-            if sh is None:
-                self.dp.sum_(g.grad)
-            else:
-                sh.sum_(bounds_grad)      # shared log-var bounds: the sum over all members
-            # Adam + grad zeroing + packed-mirror refresh in one launch
-            lr_bc1, bc2 = m.optimizer.step_scalars()
-            for arr in seg_arr:
-                for k in range(len(arr)):
-                    arr[k].lr_over_bc1, arr[k].bc2_sqrt = lr_bc1, bc2
-                _lib.check(L.drpo_optim_step(arr, len(arr), stream), 'optim_step')
-        if fuse_sh and pending:
-            _lib.check(L.drpo_stream_wait_event(main_s, ev_done), 'stream_wait_event')
+                self._gather(rb, rows, mb, steps=nc, idx=idx, ctr=ctr, seed=nz.seed, device_ptr=True)
+            plan.compute(i, k)
+            plan.apply(i)
+        plan.finish()
         # holdout: the same rows for every member (src/dynamics.py:175-183)
         hb = m.holdout_size
         assert hb == b, 'reference asserts holdout_size == batch_size (src/dynamics.py:177)'
-        hs, ha, ht = self.buf('ho.s', hb, S), self.buf('ho.a', hb, A), self.buf('ho.t', hb, S1)
-        gather(hb, (hs, ha, ht))
+        ho = (self.buf('ho.s', hb, S), self.buf('ho.a', hb, A), self.buf('ho.t', hb, S1))
+        idx = torch.from_numpy(np.ascontiguousarray(nz.randint(n, hb))).to(self.dev) if nz.parity else None
+        self._gather(rb, hb, ho, idx=idx, ctr=0 if nz.parity else nz.next(), seed=nz.seed, device_ptr=True)
         if sh is not None:
-            sh.broadcast_(hs, ha, ht)
-        nets, _, _ = self._forward(hs, ha, hb, Z, 0, 0, tag='ho', z0=z0)
-        mse, _, _ = self._loss(nets, hs, 0, ht, 0, hb, Z, False, tag='ho')
+            sh.broadcast_(*ho)
+        nets, _, _ = self._forward(ho[0], ho[1], hb, Z, 0, 0, tag='ho', z0=z0)
+        mse, _, _ = self._loss(nets, ho[0], 0, ho[2], 0, hb, Z, False, tag='ho')
         if sh is None:
             self.dp.mean_(mse)       # identical elites on every rank
         else:
@@ -592,13 +505,6 @@ class EnsembleEngine:
                     sh.gather_members_(g.view(key))
         g.mark_dirty()
 
-    def _gather_buffer(self, rb, count, idx_t, seed, ctr, out):
-        m, L = self.m, _lib.lib()
-        _lib.check(L.drpo_ens_gather(_lib.ptr(rb._states), _lib.ptr(rb._actions), _lib.ptr(rb._next_states),
-                                     _lib.ptr(rb._rewards), rb.pointer, None, rb.capacity, count, _lib.ptr(idx_t),
-                                     seed, ctr, m.state_dim, m.action_dim, _lib.ptr(out[0]), _lib.ptr(out[1]),
-                                     _lib.ptr(out[2]), _lib.stream()), 'ens_gather')
-
     def fit_epochs(self, buffer, epochs, max_grad_norm=None, post_epoch_callback=None, post_step_callback=None,
                    progress_bar=False, verbose=False):
         """fit(epochs=) == epochal_training over E*epochs epochs of randperm minibatches of
@@ -624,7 +530,7 @@ class EnsembleEngine:
                 idx = perm[bi * tb:min(n, (bi + 1) * tb)]
                 cnt = len(idx)
                 xs, xa, xt = self.buf('ep.s', cnt, S), self.buf('ep.a', cnt, A), self.buf('ep.t', cnt, S + 1)
-                self._gather_buffer(rb, cnt, idx, 0, 0, (xs, xa, xt))
+                self._gather(rb, cnt, (xs, xa, xt), idx=idx)
                 m.group.grad.zero_()
                 ep_i = ep[bi:bi + 1].view(())
                 loss = self.compute_loss_value(xs, xa, xt, with_grads=True)
@@ -644,6 +550,139 @@ class EnsembleEngine:
             if post_epoch_callback is not None:
                 post_epoch_callback(epoch)
         return losses
+
+
+class FitPlan:
+    """One fit(steps=) call's step, built once: the descriptors point at fixed workspaces, and
+    per step only the minibatch slice (fd.src, up.s, up.t), the loss slot (red_in.loss) and
+    Adam's bias-corrected step sizes change. compute(i, k) and apply(i) issue step i's
+    launches in order; which of their three variants run is decided here (the header of
+    this file says when)."""
+
+    def __init__(self, eng, sh, mb, losses):
+        from ._abi import OptimSeg, WgradAdam
+        m, g = eng.m, eng.m.group
+        S, A, b = m.state_dim, m.action_dim, m.batch_size
+        z0, Z = (sh.z0, sh.count) if sh is not None else (0, m.ensemble_size)
+        self.eng, self.sh, self.mb, self.rows = eng, sh, mb, Z * b
+        self.loss_base = losses.data_ptr()
+        self.fd, nets, strides, save_x = eng._forward_desc(mb[0], mb[1], b, Z, b * S, b * A, tag='fit', save=True,
+                                                           z0=z0)
+        self.up, self.red_in, _, gD, gL = eng._loss_descs(nets, mb[0], b * S, mb[2], b * (S + 1), b, Z, True,
+                                                          tag='fit', bound=sh is None or sh.rank == 0)
+        self.red = EnsReduce()
+        self.gD, self.gL = _lib.ptr(gD), _lib.ptr(gL)
+        self.bd, wl = eng._backward_descs(nets, strides, save_x, gD, gL, b, Z)
+        self.refs = [ctypes.byref(x) for x in (self.fd, self.bd, self.up, self.red_in, self.red)]
+        self.L, self.stream = _lib.lib(), _lib.stream()
+        # compute: the NLL in the backward launch needs the shapes drpo_mlp_backward_ens takes,
+        # the one-launch step also a split-heads grid and the shapes of drpo_ens_fit_fb
+        self.fused = ens_fused_shapes(nets, S + 1)
+        self.bd.upstream = 3 if self.fused else 0   # DRPO_UPSTREAM_ENS : DRPO_UPSTREAM_GOUT
+        self.fb = eng.fit_fb_enabled and self.fused and bool(self.bd.split_heads) and ens_fb_shapes(nets, S, A)
+        # apply: Adam in the weight-gradient launch needs the fused NLL, no clip and no exchange
+        # of the member gradients (a member shard and batch DP exclude each other:
+        # member_sharding() is None under dp_mode='batch')
+        assert sh is None or getattr(m, 'dp_mode', 'auto') != 'batch'
+        fuse = eng.fused_adam and self.fused and len(wl) == 1 and not (sh is None and eng.dp.active)
+        self.path = 'separate' if not fuse else ('fused' if sh is None else 'fused-shard')
+        self.wl = wl
+        if fuse:
+            opt = m.optimizer
+            opt._ensure_state()
+            pm = g.pack_map()
+            ad = self.ad = WgradAdam()
+            ad.g, ad.p, ad.m, ad.v = g.grad.data_ptr(), g.data.data_ptr(), opt.m.data_ptr(), opt.v.data_ptr()
+            ad.beta1, ad.beta2 = opt.betas
+            ad.eps, ad.weight_decay = opt.eps, opt.weight_decay
+            ad.map, ad.map_host = pm.data_ptr(), ctypes.addressof(pm.host)
+            self.wws = eng._wgrad_ws('fit0', *wl[0])
+        if sh is None:   # batch DP: the gradient is sum-reduced, the optimizer applies 1/G
+            segs = [m.optimizer.segment(0, g.size, (0.0, 1.0), zero_grad=True, pack_map=g.pack_map(),
+                                        grad_scale=eng.dp.scale)]
+        else:            # the shard's members and the shared log-var bounds
+            lo, hi = g.offset('min_log_var'), g.offset('max_log_var') + S + 1
+            self.bounds_grad = g.grad[lo:hi]
+            pmap = g.pack_map()
+            segs = [m.optimizer.segment(a, c, (0.0, 1.0), zero_grad=True, pack_map=pmap)
+                    for a, c in eng._shard_ranges(z0, Z)]
+            if fuse:
+                self.bseg = (OptimSeg * 1)(m.optimizer.segment(lo, hi, (0.0, 1.0), zero_grad=True))
+                self.side, self.ev_bwd, self.ev_done = eng._side_stream()
+                self.side_s = ctypes.c_void_p(self.side.cuda_stream)
+        self.seg_arr = [(OptimSeg * len(segs[k:k + 8]))(*segs[k:k + 8]) for k in range(0, len(segs), 8)]
+        self.pending = False    # fused-shard: the previous step's bounds update is in flight
+
+    def compute(self, i, k):
+        """Step i on minibatch k of the gathered chunk: forward, NLL and backward-data, with
+        the NLL partials and self.red (their reduction, as data) left for apply()."""
+        L, stream = self.L, self.stream
+        fd, bd, up, red_in, red = self.refs
+        S, A = self.up.S, self.eng.m.action_dim
+        cs, ca, ct = self.mb
+        self.fd.src[0], self.fd.src[1] = cs.data_ptr() + 4 * k * self.rows * S, ca.data_ptr() + 4 * k * self.rows * A
+        self.up.s, self.up.t = self.fd.src[0], ct.data_ptr() + 4 * k * self.rows * (S + 1)
+        self.red_in.loss = self.loss_base + 4 * i
+        if not self.fb:
+            _lib.check(L.drpo_mlp_forward(fd, stream), 'ensemble forward')
+        if self.pending:     # the previous step's bounds are stepped (the backward reads them)
+            _lib.check(L.drpo_stream_wait_event(stream, self.ev_done), 'stream_wait_event')
+        if self.fb:
+            _lib.check(L.drpo_ens_fit_fb(fd, bd, up, red_in, red, stream), 'ensemble fit fwd+bwd')
+        elif self.fused:
+            _lib.check(L.drpo_mlp_backward_ens(bd, up, red_in, red, stream), 'ensemble backward')
+        else:
+            _lib.check(L.drpo_ens_loss(up, red_in, self.gD, self.gL, red, stream), 'ens_loss')
+            _lib.check(L.drpo_mlp_backward(bd, stream), 'ensemble backward')
+
+    def apply(self, i):
+        """Step i's weight gradients, the NLL reduction and the Adam step."""
+        L, stream = self.L, self.stream
+        eng, m, sh = self.eng, self.eng.m, self.sh
+        lr_bc1, bc2 = m.optimizer.step_scalars()
+        if self.path == 'separate':
+            # the loss reduction rides as the last workgroup of the wgrad launch
+            eng._wgrad('fit', self.wl, self.red, stream)
+            if sh is None:
+                eng.dp.sum_(m.group.grad)
+            else:
+                sh.sum_(self.bounds_grad)      # shared log-var bounds: the sum over all members
+            # Adam + grad zeroing + packed-mirror refresh in one launch
+            for arr in self.seg_arr:
+                for k in range(len(arr)):
+                    arr[k].lr_over_bc1, arr[k].bc2_sqrt = lr_bc1, bc2
+                _lib.check(L.drpo_optim_step(arr, len(arr), stream), 'optim_step')
+            return
+        (warr, wn), wws, ad = self.wl[0], self.wws, self.ad
+        ad.lr_over_bc1, ad.bc2_sqrt = lr_bc1, bc2
+        if self.path == 'fused':
+            # weight gradients + the NLL reduction + Adam + mirror refresh: one launch
+            _lib.check(L.drpo_mlp_wgrad_adam(warr, wn, self.refs[4], ctypes.byref(ad), wws.data_ptr(),
+                                             wws.numel(), stream), 'ensemble wgrad + adam')
+            return
+        # Member shard (SURVEY §8(e)): only the shared log-var bounds' 2(S+1) gradients leave
+        # the step. Their reduction runs as its own one-block launch on the side stream as soon
+        # as the backward has written the NLL partials; the side stream then sum-all-reduces
+        # them (the step's ONE collective) and steps the bounds, overlapped with the members'
+        # fused weight-gradient + Adam launch on the main stream.
+        side_s = self.side_s
+        _lib.check(L.drpo_event_record(self.ev_bwd, stream), 'event_record')
+        _lib.check(L.drpo_stream_wait_event(side_s, self.ev_bwd), 'stream_wait_event')
+        _lib.check(L.drpo_ens_loss_reduce(ctypes.byref(self.red), side_s), 'ens_loss_reduce')
+        with torch.cuda.stream(self.side):      # the collective on the side stream
+            sh.sum_(self.bounds_grad)
+        self.bseg[0].lr_over_bc1, self.bseg[0].bc2_sqrt = lr_bc1, bc2
+        _lib.check(L.drpo_optim_step(self.bseg, 1, side_s), 'optim_step (log-var bounds)')
+        _lib.check(L.drpo_event_record(self.ev_done, side_s), 'event_record')
+        self.pending = True
+        _lib.check(L.drpo_mlp_wgrad_adam(warr, wn, None, ctypes.byref(ad), wws.data_ptr(), wws.numel(), stream),
+                   'ensemble wgrad + adam (member shard)')
+
+    def finish(self):
+        """The main stream waits for the last step's bounds update (member shard)."""
+        if self.pending:
+            _lib.check(self.L.drpo_stream_wait_event(self.stream, self.ev_done), 'stream_wait_event')
+            self.pending = False
 
 
 class EnsembleLoss(torch.autograd.Function):

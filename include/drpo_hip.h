@@ -274,10 +274,11 @@ typedef struct {
   int upstream;        /* where the output gradients come from: DRPO_UPSTREAM_* */
 } drpo_mlp_bwd_t;
 
-/* The model fit's NLL loss (drpo_ens_loss's arithmetic, src/dynamics.py:136-153,236-253)
- * as the upstream of the ensemble backward launch (drpo_mlp_backward_ens): the head
- * outputs' gradients are formed in-kernel and the loss partials are left for the
- * deferred reduction (drpo_mlp_wgrad_reduce). */
+/* The model fit's NLL loss (src/dynamics.py:136-153,236-253): the inputs of drpo_ens_loss,
+ * and of the same arithmetic as the upstream of the ensemble backward launch
+ * (drpo_mlp_backward_ens, drpo_ens_fit_fb), where the head outputs' gradients are formed
+ * in-kernel and the loss partials are left for the deferred reduction
+ * (drpo_mlp_wgrad_reduce). */
 typedef struct {
   const float *D, *LVR;        /* diff / raw log-var head outputs [Z][b][S+1] */
   const float* s;              /* raw states [Z][b][S] (member stride s_zstride) */
@@ -434,7 +435,7 @@ int drpo_mlp_wgrad_tiles(const drpo_wgrad_item_t* item /* host */);
 int drpo_mlp_wgrad(const drpo_wgrad_item_t* items /* host */, int n, void* workspace, size_t workspace_bytes,
                    drpo_stream_t stream);
 /* drpo_mlp_wgrad plus one extra workgroup running a deferred ensemble-loss
- * reduction (drpo_ens_loss_partials); red may be NULL */
+ * reduction (drpo_ens_loss with reduce_out); red may be NULL */
 int drpo_mlp_wgrad_reduce(const drpo_wgrad_item_t* items /* host */, int n, const drpo_ens_reduce_t* red /* host */,
                           void* workspace, size_t workspace_bytes, drpo_stream_t stream);
 /* drpo_mlp_wgrad plus one extra workgroup adding up partial sums in a fixed order:
@@ -533,11 +534,8 @@ int drpo_multiplier_out(int64_t B, const float* x, float upper_bound, float* lam
  * BatchedGaussianEnsemble (src/dynamics.py:112-253); the MLP passes use
  * drpo_mlp_forward/backward/wgrad with nbatch = ensemble members.              */
 /* fit / holdout minibatch gather by chronological replay index (src/dynamics.py:156-166,
- * 175-177); idx NULL -> Philox randint(n) with (seed, ctr); ptr_dev overrides ptr */
-int drpo_ens_gather(const float* states, const float* actions, const float* next_states, const float* rewards,
-                    int64_t ptr, const int64_t* ptr_dev, int64_t cap, int64_t rows, const int64_t* idx, uint64_t seed,
-                    uint64_t ctr, int S, int A, float* xs, float* xa, float* xt, drpo_stream_t stream);
-/* the minibatches of `steps` consecutive fit steps in one launch: step k fills rows
+ * 175-177); idx NULL -> Philox randint(n) with (seed, ctr); ptr_dev overrides ptr.
+ * The minibatches of `steps` consecutive fit steps in one launch: step k fills rows
  * [k*rows, (k+1)*rows) of xs / xa / xt from idx[k*rows ..] (or Philox counter ctr + k) */
 int drpo_ens_gather_steps(const float* states, const float* actions, const float* next_states, const float* rewards,
                           int64_t ptr, const int64_t* ptr_dev, int64_t cap, int64_t rows, int64_t steps,
@@ -549,25 +547,19 @@ int drpo_ens_head(const float* D, const float* LVR, const float* s, int64_t s_zs
                   const float* minlv, const float* maxlv, const int* zsel, const float* eps, uint64_t seed,
                   uint64_t ctr, float* mu, float* lv, float* s2, float* r, drpo_stream_t stream);
 /* per-member NLL (_mse_loss, src/dynamics.py:236-253), total compute_loss (:143-153)
- * and, when gD != NULL, its gradients (scaled by *gscale if given; gmin/gmax are
- * accumulated into). Row blocks leave partial sums in the workspace
- * (drpo_ens_loss_workspace_size(b, S, Z) bytes; one call at a time per workspace),
- * reduced in a fixed order by a one-block launch. */
+ * and, when gD != NULL, its gradients (scaled by *up->gscale if given; gmin / gmax are
+ * accumulated into). up: the head outputs, rows, bounds and the workspace
+ * (drpo_ens_loss_workspace_size(b, S, Z) bytes; one call at a time per workspace), in
+ * which row blocks leave partial sums; red_in: mse, loss (or NULL), weight and, with
+ * gD / gLVR, gmin / gmax (its other fields are ignored). reduce_out NULL: a one-block
+ * launch reduces the partials in a fixed order now. Otherwise the reduction is described
+ * in *reduce_out and runs as the extra last workgroup of the next drpo_mlp_wgrad_reduce
+ * (the fit step's weight-gradient launch, which the reduction does not depend on: one
+ * launch fewer per fit step) or by drpo_ens_loss_reduce. */
 size_t drpo_ens_loss_workspace_size(int64_t b, int S, int Z);
-int drpo_ens_loss(const float* D, const float* LVR, const float* s, int64_t s_zstride, const float* t,
-                  int64_t t_zstride, int64_t b, int S, int Z, const float* minlv, const float* maxlv, float weight,
-                  const float* gscale, float* mse, float* loss, float* gD, float* gLVR, float* gmin, float* gmax,
-                  void* workspace, drpo_stream_t stream);
-/* drpo_ens_loss without its reduction launch: the reduction is described in
- * *reduce_out and runs as the extra last workgroup of the next
- * drpo_mlp_wgrad_reduce (the fit step's weight-gradient launch, which the
- * reduction does not depend on) -- one launch fewer per fit step. */
-int drpo_ens_loss_partials(const float* D, const float* LVR, const float* s, int64_t s_zstride, const float* t,
-                           int64_t t_zstride, int64_t b, int S, int Z, const float* minlv, const float* maxlv,
-                           float weight, const float* gscale, float* mse, float* loss, float* gD, float* gLVR,
-                           float* gmin, float* gmax, void* workspace, drpo_ens_reduce_t* reduce_out,
-                           drpo_stream_t stream);
-/* The deferred reduction of drpo_ens_loss_partials / drpo_mlp_backward_ens as its own
+int drpo_ens_loss(const drpo_ens_upstream_t* up /* host */, const drpo_ens_reduce_t* red_in /* host */, float* gD,
+                  float* gLVR, drpo_ens_reduce_t* reduce_out, drpo_stream_t stream);
+/* The deferred reduction of drpo_ens_loss / drpo_mlp_backward_ens / drpo_ens_fit_fb as its own
  * one-block launch (replaces the reduction step of BatchedGaussianEnsemble.fit,
  * src/dynamics.py:143-153,163-171): per-member NLL, the step loss and the log-var
  * bound gradients ACCUMULATED into gmin / gmax (no optimizer step). The member-

@@ -334,6 +334,88 @@ def test_fit_head_hidden_layers_2_vs_oracle():
         assert not (err > 0).any(), (k, float(np.abs(got - e).max()))
 
 
+_RAGGED = {}
+
+
+def _ragged_case(env, hhl):
+    """One model [hidden 200, E=2, batch = holdout = 20 rows] per (env, head_hidden_layers)
+    with its start state and the oracle's fit(steps=2) from it, computed once."""
+    key = (env, hhl)
+    if key not in _RAGGED:
+        torch.manual_seed(13)
+        alg = bench.make_alg(DEV, 256, 5, 2, 13, bench.ENV_JSON[env], env=env,
+                             extra={'model_cfg': {'ensemble_size': 2, 'num_elites': 2, 'batch_size': 20,
+                                                  'holdout_size': 20, 'head_hidden_layers': hhl}})
+        m = alg.model_ensemble
+        assert (m.hidden_dim, m.ensemble_size, m.batch_size, m.holdout_size) == (200, 2, 20, 20)
+        assert m.head_hidden_layers == hhl
+        _fill(alg, env, 3000, 9)
+        buf = {k: v.cpu() for k, v in alg.replay_buffer.get(as_dict=True).items()}
+        P = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
+        m.optimizer._ensure_state()
+        start = [m.group.data.clone(), m.optimizer.m.clone(), m.optimizer.v.clone(), m.optimizer.step_count]
+        _oracle_threads()
+        live = O.LiveRNG()
+        ref_losses, ref_elites = O.ens_fit(P, '', {}, buf, 2, 2, 20, 20, 2, live)
+        _RAGGED[key] = (alg, start, P, ref_losses, ref_elites, live.entries)
+    return _RAGGED[key]
+
+
+# (env, head_hidden_layers, engine switches, expected fit_fb, expected fit_path)
+RAGGED_CASES = [
+    ('cartpole', 1, {}, True, 'fused'),
+    ('cartpole', 1, {'fit_fb_enabled': False}, False, 'fused'),
+    ('cartpole', 1, {'fused_adam': False}, True, 'separate'),
+    ('cartpole', 1, {'split_bwd': False}, False, 'fused'),
+    ('cartpole', 2, {}, False, 'separate'),
+    ('tracking', 1, {}, False, 'fused'),
+    ('tracking', 1, {'split_bwd': False}, False, 'fused'),
+]
+
+
+@pytest.mark.parametrize('env,hhl,switches,fit_fb,fit_path', RAGGED_CASES,
+                         ids=[f'{e}-h{h}-' + ('-'.join(s) or 'production') for e, h, s, _, _ in RAGGED_CASES])
+def test_fit_ragged_tile_vs_oracle(env, hhl, switches, fit_fb, fit_path):
+    """fit(steps=2) at batch = holdout = 20 rows per member (one full 16-row tile plus a
+    4-row tile: the smallest shape at which the tile's partial write-out and the padded
+    NLL rows can go wrong), hidden width 200, E = 2, on tape noise against the oracle: on
+    cartpole (S + 1 <= 16) through every way the step can run (the one-launch step, forward +
+    fused-NLL backward split and paired, the separate Adam step, and the separate NLL launch
+    of head_hidden_layers = 2), and on tracking (S + 1 > 16) split and paired. Tolerances of
+    test_fit_head_hidden_layers_2_vs_oracle, every element compared."""
+    alg, start, P, ref_losses, ref_elites, entries = _ragged_case(env, hhl)
+    m = alg.model_ensemble
+    eng, g = m.engine, m.group
+    assert (m.state_dim + 1 <= 16) == (env == 'cartpole')
+    g.data.copy_(start[0])
+    m.optimizer.m.copy_(start[1])
+    m.optimizer.v.copy_(start[2])
+    m.optimizer.step_count = start[3]
+    g.mark_dirty()
+    g.ensure_packed()
+    eng.ws.clear()
+    eng.wg_ws.clear()
+    tape = drpo_amd.TapeNoise(entries)
+    try:
+        for k, v in switches.items():
+            setattr(eng, k, v)
+        losses = m.fit(alg.replay_buffer, steps=2, noise=tape)
+    finally:
+        eng.fit_fb_enabled = eng.fused_adam = eng.split_bwd = True
+    assert tape.done()
+    assert (eng.fit_fb, eng.fit_path) == (fit_fb, fit_path)
+    print('ragged fit', env, hhl, switches, 'loss rel err',
+          float(np.max(np.abs(np.asarray(losses) - ref_losses) / np.abs(ref_losses))))
+    np.testing.assert_allclose(losses, ref_losses, rtol=1e-4)
+    assert m._elite_inds == ref_elites
+    sd = m.state_dict()
+    for k in O.ens_param_keys(P, ''):
+        got, e = sd[k].cpu().numpy(), P[k].numpy()
+        err = np.abs(got - e) - (5e-5 + 2e-4 * np.abs(e))
+        print('ragged fit', k, 'max excess over tolerance', float(err.max()))
+        assert not (err > 0).any(), (k, float(np.abs(got - e).max()))
+
+
 def _flags_marginal(fns, s2, flags, n_probe=6, rel=1e-5):
     """Rows whose (done, violation) flags flip under +-rel perturbations of next_state:
     there the flag is decided by fp32 rounding, not by the kernel's arithmetic."""

@@ -48,9 +48,10 @@ def test_device_normals_decorrelated_across_counters_and_seeds():
 
 @pytest.mark.parametrize('use_idx', [False, True])
 def test_fit_gather_steps_matches_per_step_gathers(use_idx):
-    """drpo_ens_gather_steps (the fit's chunked minibatch gather) writes, for step k,
-    exactly what drpo_ens_gather writes with Philox counter ctr + k (or idx rows
-    [k*rows, (k+1)*rows)), from a wrapped circular replay (pointer past capacity)."""
+    """drpo_ens_gather_steps (the fit's chunked minibatch gather) in one launch for `steps`
+    steps writes, for step k, exactly what a launch of one step writes with Philox counter
+    ctr + k (or idx rows [k*rows, (k+1)*rows)), from a wrapped circular replay (pointer
+    past capacity)."""
     L = _lib.lib()
     dev = torch.device('cuda')
     S, A, cap, rows, steps = 5, 2, 1000, 96, 4
@@ -73,10 +74,7 @@ def test_fit_gather_steps_matches_per_step_gathers(use_idx):
     run(steps, ctr, None if idx is None else idx.data_ptr(), big)
     for k in range(steps):
         one = (torch.empty(rows, S, device=dev), torch.empty(rows, A, device=dev), torch.empty(rows, S + 1, device=dev))
-        _lib.check(L.drpo_ens_gather(bs.data_ptr(), ba.data_ptr(), bs2.data_ptr(), br.data_ptr(), 0, ptr.data_ptr(),
-                                     cap, rows, None if idx is None else idx[k * rows:].data_ptr(), seed,
-                                     0 if idx is not None else ctr + k, S, A, one[0].data_ptr(), one[1].data_ptr(),
-                                     one[2].data_ptr(), _lib.stream()))
+        run(1, 0 if idx is not None else ctr + k, None if idx is None else idx[k * rows:].data_ptr(), one)
         for a, b in zip(big, one):
             assert torch.equal(a[k * rows:(k + 1) * rows], b)
     # the draws differ between steps (distinct counters)
