@@ -175,6 +175,11 @@ class MlpBwd(ctypes.Structure):
                 ('split_heads', c_int), ('upstream', c_int)]
 
 
+class MlpFbJob(ctypes.Structure):
+    """drpo_mlp_fb_job_t"""
+    _fields_ = [('nfwd', c_int), ('fwd', c_int * 2), ('bwd', c_int)]
+
+
 class WgradItem(ctypes.Structure):
     """drpo_wgrad_item_t"""
     _fields_ = [('dz', P), ('y', P), ('gW', P), ('gb', P), ('dout', c_int), ('din', c_int), ('rows', c_int64),
@@ -226,6 +231,8 @@ PROTOTYPES.update({
     'drpo_mlp_backward_multi_actor': (c_int, [POINTER(MlpBwd), P, c_int, POINTER(ActorHead), P]),
     'drpo_mlp_backward_multi': (c_int, [POINTER(MlpBwd), P, c_int, P]),
     'drpo_mlp_backward': (c_int, [POINTER(MlpBwd), P]),
+    'drpo_mlp_fb_multi': (c_int, [POINTER(MlpFwd), P, c_int, POINTER(MlpBwd), P, c_int, POINTER(MlpFbJob), c_int,
+                                  POINTER(ActorHead), c_uint64, c_uint64, P]),
     'drpo_mlp_backward_ens': (c_int, [POINTER(MlpBwd), POINTER(EnsUpstream), POINTER(EnsReduce), POINTER(EnsReduce),
                                       P]),
     'drpo_ens_fit_fb': (c_int, [POINTER(MlpFwd), POINTER(MlpBwd), POINTER(EnsUpstream), POINTER(EnsReduce),

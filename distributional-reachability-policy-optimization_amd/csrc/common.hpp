@@ -320,7 +320,31 @@ struct GSave {
   float* gz;
   int ldg;
   int nrows;
+  // ReLU mask of the tile in LDS (fused forward + backward launches, RB = 1), one
+  // __ballot word per (16-column block, accumulator register): word [cb * 4 + r], bit
+  // `lane` = (y > 0) at row 4 * (lane >> 4) + r, column cb * 16 + (lane & 15). A ReLU layer
+  // records it; an identity layer (a backward product) applies it: dZ = dY where the bit
+  // is set, else 0.
+  unsigned long long* mk = nullptr;
 };
+
+// the epilogue's share of GSave.mk for the value y of accumulator register r of column
+// block cb (every lane of the wave calls: the block test around it is wave-uniform)
+template <int ACT>
+__device__ __forceinline__ float relu_mask(unsigned long long* mk, int cb, int r, float y) {
+  if constexpr (ACT == ACT_RELU) {
+    if (mk) {
+      const unsigned long long w = __builtin_amdgcn_ballot_w64(y > 0.f);
+      if ((threadIdx.x & 63) == 0) *(__attribute__((address_space(3))) unsigned long long*)(mk + cb * 4 + r) = w;
+    }
+  } else if constexpr (ACT == ACT_NONE) {
+    if (mk) {
+      const unsigned long long w = *(const __attribute__((address_space(3))) unsigned long long*)(mk + cb * 4 + r);
+      if (!((w >> (threadIdx.x & 63)) & 1ull)) y = 0.f;
+    }
+  }
+  return y;
+}
 
 // bias values of this lane's output columns, loaded before the k-loop so their
 // latency hides behind it (loaded after the loop they cost a full L2 round trip
@@ -379,7 +403,7 @@ __device__ __forceinline__ void dense_epilogue(const f32x4 (&acc)[RB][MAXC], con
       for (int r = 0; r < 4; ++r) {
         const int row = rb * 16 + 4 * g + r;
         const float z = acc[rb][c][r] + bv;
-        const float y = act_fn<ACT>(z);
+        const float y = relu_mask<ACT>(gs.mk, cb, r, act_fn<ACT>(z));
         if (out) out[row * ldo + col] = (col < N) ? y : 0.f;
         if (col < N && row < gs.nrows) {
           if (gs.gy) gstore(gs.gy + (size_t)row * gs.ldg + col, y);
@@ -883,7 +907,7 @@ __device__ __forceinline__ void tile_dense_pair_core(const float* in, int ldi, i
       for (int r = 0; r < 4; ++r) {
         const int row = rb * 16 + 4 * g + r;
         const float z = acc[rb][c][r] + bvs[c];
-        const float y = act_fn<ACT>(z);
+        const float y = relu_mask<ACT>(gs.mk, cbs[c], r, act_fn<ACT>(z));
         out[row * ldo + col] = (col < nn) ? y : 0.f;
         if (col < nn && row < gs.nrows) {
           if (gs.gy) gstore(gs.gy + (size_t)row * gs.ldg + col, y);
@@ -1003,7 +1027,7 @@ __device__ __forceinline__ void tile_dense_pair2_core(const float* in1, const fl
       for (int r = 0; r < 4; ++r) {
         const int row = rb * 16 + 4 * g + r;
         const float z = acc[rb][c][r] + bvs[c];
-        const float y = act_fn<ACT>(z);
+        const float y = relu_mask<ACT>(gs.mk, cbs[c], r, act_fn<ACT>(z));
         if (out) out[row * ldo + col] = (col < nn) ? y : 0.f;
         if (col < nn && row < gs.nrows) {
           if (gs.gy) gstore(gs.gy + (size_t)row * gs.ldg + col, y);

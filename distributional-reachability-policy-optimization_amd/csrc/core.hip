@@ -18,7 +18,7 @@ void drpo_set_error(const char* fmt, ...) {
 
 DRPO_API const char* drpo_last_error(void) { return g_err; }
 
-DRPO_API int drpo_version(void) { return 3; }
+DRPO_API int drpo_version(void) { return 4; }
 
 // HIP event helpers so hosts without a HIP binding (ctypes/cgo/JNI) can time
 // individual kernels on the stream they run on. The events are timing-only: created
@@ -73,6 +73,7 @@ DRPO_API int64_t drpo_abi_sizeof(const char* name) {
       {"drpo_mlp_net_t", sizeof(drpo_mlp_net_t)},           {"drpo_policy_head_t", sizeof(drpo_policy_head_t)},
       {"drpo_mlp_fwd_t", sizeof(drpo_mlp_fwd_t)},           {"drpo_mlp_bwd_layer_t", sizeof(drpo_mlp_bwd_layer_t)},
       {"drpo_mlp_bwd_net_t", sizeof(drpo_mlp_bwd_net_t)},   {"drpo_mlp_bwd_t", sizeof(drpo_mlp_bwd_t)},
+      {"drpo_mlp_fb_job_t", sizeof(drpo_mlp_fb_job_t)},   {"drpo_actor_head_t", sizeof(drpo_actor_head_t)},
       {"drpo_wgrad_item_t", sizeof(drpo_wgrad_item_t)},     {"drpo_buffer_view_t", sizeof(drpo_buffer_view_t)},
       {"drpo_critic_head_t", sizeof(drpo_critic_head_t)},   {"drpo_pack_item_t", sizeof(drpo_pack_item_t)},
       {"drpo_pack_map_t", sizeof(drpo_pack_map_t)},         {"drpo_optim_seg_t", sizeof(drpo_optim_seg_t)},

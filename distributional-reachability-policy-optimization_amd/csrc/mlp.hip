@@ -28,6 +28,9 @@ constexpr int LDH = 264;              // LDS stride for widths <= 256 (== 8 mod 
 constexpr int MAXL = 3;
 constexpr int MAXN = 3;
 constexpr int MJ_MAXSLOT = 16;        // (job, net) slots of a multi-job launch (grid.y)
+constexpr int FB_MAXJOB = 4;          // jobs of a fused forward + backward launch (grid.y)
+constexpr int FB_MKW = 64;            // words of one layer's ReLU mask (GSave.mk): 16 blocks x 4 registers
+constexpr int FB_MKSLOTS = 5;         // masks a job keeps: trunk layers 0..2, heads 3 / 4 (or a net's layers)
 
 }  // namespace
 
@@ -86,11 +89,12 @@ __device__ __forceinline__ void run_layer_act(const float* in, int ldi, const dr
 // optional global saves of the post-/pre-activation for the backward pass
 template <int RB = 1>
 __device__ __forceinline__ void run_layer(const float* in, int ldi, const drpo_mlp_layer_t& __restrict__ L, int z, int64_t rows,
-                                          int row0, int nrows, float* out, float* red, bool save = true) {
+                                          int row0, int nrows, float* out, float* red, bool save = true,
+                                          unsigned long long* mk = nullptr) {
   const float* W = L.W + (size_t)z * L.wstride;
   const float* b = L.b + (size_t)z * L.bstride;
   const size_t so = ((size_t)z * rows + row0) * L.dout;
-  GSave gs{save && L.sy ? L.sy + so : nullptr, save && L.sz ? L.sz + so : nullptr, L.dout, nrows};
+  GSave gs{save && L.sy ? L.sy + so : nullptr, save && L.sz ? L.sz + so : nullptr, L.dout, nrows, mk};
   switch (L.act) {
     case ACT_RELU: run_layer_act<ACT_RELU, RB>(in, LDH, L, W, b, out, LDH, red, gs); break;
     case ACT_SILU: run_layer_act<ACT_SILU, RB>(in, LDH, L, W, b, out, LDH, red, gs); break;
@@ -230,14 +234,16 @@ struct MultiArgs {
   uint64_t seed, ctr;
 };
 
-__device__ __forceinline__ GSave layer_save(const drpo_mlp_layer_t& L, int z, int64_t rows, int row0, int nrows) {
+__device__ __forceinline__ GSave layer_save(const drpo_mlp_layer_t& L, int z, int64_t rows, int row0, int nrows,
+                                            unsigned long long* mk = nullptr) {
   const size_t so = ((size_t)z * rows + row0) * L.dout;
-  return GSave{L.sy ? L.sy + so : nullptr, L.sz ? L.sz + so : nullptr, L.dout, nrows};
+  return GSave{L.sy ? L.sy + so : nullptr, L.sz ? L.sz + so : nullptr, L.dout, nrows, mk};
 }
 
 template <int RB>
 __device__ __forceinline__ float* run_net_g(const drpo_mlp_net_t& __restrict__ n, int64_t rows, float* in, float* bufA,
-                                            float* bufB, int z, int row0, int nrows, float* red) {
+                                            float* bufB, int z, int row0, int nrows, float* red,
+                                            unsigned long long* mk = nullptr) {
   float* cur = in;
   const int nl = n.nl;
   for (int l = 0; l < nl; ++l) {
@@ -245,7 +251,9 @@ __device__ __forceinline__ float* run_net_g(const drpo_mlp_net_t& __restrict__ n
     const drpo_mlp_layer_t& L = n.L[l];
     const GSave gs = layer_save(L, z, rows, row0, nrows);
     const bool defer = save_deferrable(gs.gy, gs.gz, L.dout);
-    run_layer<RB>(cur, LDH, L, z, rows, row0, nrows, out, red, !defer);
+    // mk (fused forward + backward launches): wide ReLU layer l records its mask in slot l
+    run_layer<RB>(cur, LDH, L, z, rows, row0, nrows, out, red, !defer,
+                  (mk && L.act == ACT_RELU && L.dout > 16) ? mk + FB_MKW * l : nullptr);
     lds_barrier();
     if (defer) save_tile_lds<FW_NT, 16 * RB>(out, LDH, gs.gy, L.dout, nrows);
     STAMP(2 + l);
@@ -271,7 +279,8 @@ __host__ __device__ __forceinline__ bool heads_pairable(const drpo_mlp_fwd_t* __
 
 template <int RB, int ACT0, int ACT1>
 __device__ __forceinline__ void heads_pair_act(const drpo_mlp_fwd_t* __restrict__ a, const float* T, float* hA,
-                                               float* hB, float* o, int z, int row0, int nrows, float* red) {
+                                               float* hB, float* o, int z, int row0, int nrows, float* red,
+                                               unsigned long long* mk) {
   const drpo_mlp_layer_t& A0 = a->net[1].L[0];
   const drpo_mlp_layer_t& B0 = a->net[2].L[0];
   const drpo_mlp_layer_t& A1 = a->net[1].L[1];
@@ -280,8 +289,8 @@ __device__ __forceinline__ void heads_pair_act(const drpo_mlp_fwd_t* __restrict_
   // run_net_g does, spilled 60 VGPRs in this paired layer, profiles/r05/defer_saves)
   tile_dense_pair<FW_NW, RB, 4, ACT0, 16, 2>(T, LDH, 256, A0.W + (size_t)z * A0.wstride, A0.b + (size_t)z * A0.bstride,
                                           A0.dout, hA, B0.W + (size_t)z * B0.wstride, B0.b + (size_t)z * B0.bstride,
-                                          B0.dout, hB, LDH, layer_save(A0, z, a->rows, row0, nrows),
-                                          layer_save(B0, z, a->rows, row0, nrows));
+                                          B0.dout, hB, LDH, layer_save(A0, z, a->rows, row0, nrows, mk ? mk + 3 * FB_MKW : nullptr),
+                                          layer_save(B0, z, a->rows, row0, nrows, mk ? mk + 4 * FB_MKW : nullptr));
   lds_barrier();
   STAMP(5);
   tile_dense_narrow_pair<FW_NW, RB, ACT1>(hA, hB, LDH, A0.dout, A1.W + (size_t)z * A1.wstride,
@@ -293,23 +302,25 @@ __device__ __forceinline__ void heads_pair_act(const drpo_mlp_fwd_t* __restrict_
 
 template <int RB, int ACT0>
 __device__ __forceinline__ void heads_pair_act0(const drpo_mlp_fwd_t* __restrict__ a, const float* T, float* hA,
-                                                float* hB, float* o, int z, int row0, int nrows, float* red) {
+                                                float* hB, float* o, int z, int row0, int nrows, float* red,
+                                                unsigned long long* mk) {
   switch (a->net[1].L[1].act) {
-    case ACT_RELU: heads_pair_act<RB, ACT0, ACT_RELU>(a, T, hA, hB, o, z, row0, nrows, red); break;
-    case ACT_SILU: heads_pair_act<RB, ACT0, ACT_SILU>(a, T, hA, hB, o, z, row0, nrows, red); break;
-    case ACT_TANH: heads_pair_act<RB, ACT0, ACT_TANH>(a, T, hA, hB, o, z, row0, nrows, red); break;
-    default: heads_pair_act<RB, ACT0, ACT_NONE>(a, T, hA, hB, o, z, row0, nrows, red); break;
+    case ACT_RELU: heads_pair_act<RB, ACT0, ACT_RELU>(a, T, hA, hB, o, z, row0, nrows, red, mk); break;
+    case ACT_SILU: heads_pair_act<RB, ACT0, ACT_SILU>(a, T, hA, hB, o, z, row0, nrows, red, mk); break;
+    case ACT_TANH: heads_pair_act<RB, ACT0, ACT_TANH>(a, T, hA, hB, o, z, row0, nrows, red, mk); break;
+    default: heads_pair_act<RB, ACT0, ACT_NONE>(a, T, hA, hB, o, z, row0, nrows, red, mk); break;
   }
 }
 
 template <int RB>
 __device__ __forceinline__ void heads_pair(const drpo_mlp_fwd_t* __restrict__ a, const float* T, float* hA, float* hB,
-                                           float* o, int z, int row0, int nrows, float* red) {
+                                           float* o, int z, int row0, int nrows, float* red,
+                                           unsigned long long* mk = nullptr) {
   switch (a->net[1].L[0].act) {
-    case ACT_RELU: heads_pair_act0<RB, ACT_RELU>(a, T, hA, hB, o, z, row0, nrows, red); break;
-    case ACT_SILU: heads_pair_act0<RB, ACT_SILU>(a, T, hA, hB, o, z, row0, nrows, red); break;
-    case ACT_TANH: heads_pair_act0<RB, ACT_TANH>(a, T, hA, hB, o, z, row0, nrows, red); break;
-    default: heads_pair_act0<RB, ACT_NONE>(a, T, hA, hB, o, z, row0, nrows, red); break;
+    case ACT_RELU: heads_pair_act0<RB, ACT_RELU>(a, T, hA, hB, o, z, row0, nrows, red, mk); break;
+    case ACT_SILU: heads_pair_act0<RB, ACT_SILU>(a, T, hA, hB, o, z, row0, nrows, red, mk); break;
+    case ACT_TANH: heads_pair_act0<RB, ACT_TANH>(a, T, hA, hB, o, z, row0, nrows, red, mk); break;
+    default: heads_pair_act0<RB, ACT_NONE>(a, T, hA, hB, o, z, row0, nrows, red, mk); break;
   }
 }
 
@@ -418,28 +429,37 @@ static int pair_ok(const drpo_mlp_fwd_t* a) {
          A.L[2].dout <= 16 && A.L[0].act == ACT_RELU && A.L[1].act == ACT_RELU && A.L[2].act == ACT_NONE;
 }
 
-template <int RB>
-__global__ __launch_bounds__(FW_NT) __attribute__((amdgpu_waves_per_eu(RB == 1 ? 4 : 2, RB == 1 ? 4 : 2))) void mlp_fwd_multi_kernel(MultiArgs m) {
+// where one forward job of a multi-job launch left its results in LDS
+struct FwdOut {
+  bool ran;       // false: the tile lies past the job's rows
+  float* out;     // the final activation (paired heads: mean columns 0.., log-std columns 16..)
+  float* post;    // the post chain's output, or nullptr
+};
+
+// One (job, net) slot of a multi-job forward for row tile bx of batch item z. mk (fused
+// forward + backward launches): the wide ReLU layers of the job's nets record their
+// masks there (GSave.mk; slots: run_net_g, heads_pair_act). FB: the job kinds of a fused
+// launch only (one net, or a trunk with paired heads; drpo_mlp_fb_multi refuses the rest).
+template <int RB, bool FB = false>
+__device__ __forceinline__ FwdOut fwd_multi_body(const drpo_mlp_fwd_t* __restrict__ a, int net, int bx, int z,
+                                                 uint64_t seed, uint64_t ctr, float* smem,
+                                                 unsigned long long* mk = nullptr) {
   constexpr int ROWS = 16 * RB;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
   float* xin = smem;
   float* bA = xin + ROWS * LDH;
   float* bB = bA + ROWS * LDH;
   float* T = bB + ROWS * LDH;
   float* red = T + ROWS * LDH;
-  const drpo_mlp_fwd_t* __restrict__ a = m.jobs + m.slot_job[blockIdx.y];
-  const int net = m.slot_net[blockIdx.y];
   const int tid = threadIdx.x;
-  const int z = blockIdx.z;
-  const int row0 = blockIdx.x * ROWS;
-  if (row0 >= a->rows || z >= a->nbatch) return;
+  const int row0 = bx * ROWS;
+  if (row0 >= a->rows || z >= a->nbatch) return FwdOut{false, nullptr, nullptr};
   const int nrows = (int)min((int64_t)ROWS, a->rows - row0);
   STAMP(0);
   const int c0 = a->cols[0], c1 = a->cols[1];
   const int din0 = c0 + c1 + a->cols[2];
   const int kpad = round_up(din0, 16);
   // chain jobs: the src[1] block (the action) comes from the pre net's head below
-  const bool chain = a->pre.nl > 0;
+  const bool chain = !FB && a->pre.nl > 0;
   const int c2 = a->cols[2];
   stage_input_tile<FW_NT>(xin, LDH, ROWS, nrows, row0, kpad, a->src[0] + (size_t)z * a->sstride[0],
                           (c1 && !chain) ? a->src[1] + (size_t)z * a->sstride[1] : nullptr,
@@ -452,24 +472,27 @@ __global__ __launch_bounds__(FW_NT) __attribute__((amdgpu_waves_per_eu(RB == 1 ?
     // columns; the weights are zero beyond its own K), its sampled action into the input
     // tile's src[1] columns
     const float* po = run_net_g<RB>(a->pre, a->rows, xin, bA, bB, z, row0, nrows, red);
-    squash_head_tile<ROWS>(po, row0, nrows, a->pre_head, m.seed, m.ctr, red, xin + c0);
+    squash_head_tile<ROWS>(po, row0, nrows, a->pre_head, seed, ctr, red, xin + c0);
     lds_barrier();
     STAMP(7);
   }
   float* outp;
   float* outp2 = nullptr;
-  if (a->pair) {
+  float* postp = nullptr;
+  float* narrow = nullptr;
+  if (!FB && a->pair) {
     pair_nets<RB>(a->net[0], a->net[1], a->rows, xin, bA, bB, T, z, row0, nrows, red);
     outp = bA;
     outp2 = bA + 16;
   } else if (!a->trunk) {
-    outp = run_net_g<RB>(a->net[net], a->rows, xin, bA, bB, z, row0, nrows, red);
-  } else if (heads_pairable(a)) {
+    outp = run_net_g<RB>(a->net[net], a->rows, xin, bA, bB, z, row0, nrows, red, mk);
+  } else if (FB || heads_pairable(a)) {
     // trunk output stays where the trunk left it; the paired heads use the two
     // other full buffers and write their narrow outputs into xin (consumed)
-    float* t = run_net_g<RB>(a->net[0], a->rows, xin, bA, bB, z, row0, nrows, red);
+    float* t = run_net_g<RB>(a->net[0], a->rows, xin, bA, bB, z, row0, nrows, red, mk);
     outp = nullptr;
-    heads_pair<RB>(a, t, T, t == bA ? bB : bA, xin, z, row0, nrows, red);
+    narrow = xin;
+    heads_pair<RB>(a, t, T, t == bA ? bB : bA, xin, z, row0, nrows, red, mk);
     STAMP(6);
     if (a->ccb_out) {
       // the constraint critic's upper bound, max over C, from the heads' outputs in LDS
@@ -510,7 +533,7 @@ __global__ __launch_bounds__(FW_NT) __attribute__((amdgpu_waves_per_eu(RB == 1 ?
           T[r * LDH + k] = v;
         }
         lds_barrier();
-        run_net_g<RB>(a->post, a->rows, T, bA, bB, z, row0, nrows, red);
+        postp = run_net_g<RB>(a->post, a->rows, T, bA, bB, z, row0, nrows, red);
       }
     }
   } else {
@@ -528,11 +551,61 @@ __global__ __launch_bounds__(FW_NT) __attribute__((amdgpu_waves_per_eu(RB == 1 ?
   // fused squashed-Gaussian heads on net 0's output (non-trunk jobs) and, for a pair
   // job, on net 1's (head2; its log-prob scratch after head's)
   const drpo_policy_head_t& hd = a->head;
-  if (hd.mode != 0 && outp && net == 0) {
-    squash_head_tile<ROWS>(outp, row0, nrows, hd, m.seed, m.ctr, red);
+  if (!FB && hd.mode != 0 && outp && net == 0) {
+    squash_head_tile<ROWS>(outp, row0, nrows, hd, seed, ctr, red);
   }
-  if (outp2 && a->head2.mode != 0) squash_head_tile<ROWS>(outp2, row0, nrows, a->head2, m.seed, m.ctr, red + ROWS * 8);
+  if (!FB && outp2 && a->head2.mode != 0) squash_head_tile<ROWS>(outp2, row0, nrows, a->head2, seed, ctr, red + ROWS * 8);
   STAMP(15);
+  return FwdOut{true, narrow ? narrow : outp, postp};
+}
+
+template <int RB>
+__global__ __launch_bounds__(FW_NT) __attribute__((amdgpu_waves_per_eu(RB == 1 ? 4 : 2, RB == 1 ? 4 : 2))) void mlp_fwd_multi_kernel(MultiArgs m) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  fwd_multi_body<RB>(m.jobs + m.slot_job[blockIdx.y], m.slot_net[blockIdx.y], blockIdx.x, blockIdx.z, m.seed, m.ctr,
+                     smem);
+}
+
+// What a multi-job forward (drpo_mlp_forward_multi, and the forwards of drpo_mlp_fb_multi)
+// requires of job j beyond check_fwd_job: the kernel trusts every flag checked here.
+static int check_fwd_multi_job(const char* who, int j, const drpo_mlp_fwd_t* a) {
+  if (const int e = check_fwd_job(who, j, a)) return e;
+  DRPO_REQUIRE(!a->split_heads, "%s: job %d: split_heads is a single-launch mode", who, j);
+  DRPO_REQUIRE(!a->trunk || a->head.mode == 0, "%s: policy head on a trunk job", who);
+  if (a->head.mode != 0)
+    DRPO_REQUIRE(a->head.mode <= 3 && a->head.A >= 1 && a->head.A <= 8 &&
+                     2 * a->head.A == a->net[0].L[a->net[0].nl - 1].dout,
+                 "%s: job %d policy head shape", who, j);
+  if (a->pair) {
+    DRPO_REQUIRE(pair_ok(a), "%s: job %d: a pair job needs two 3-layer ReLU nets of one shape "
+                             "[K <= 16 or 49..64 -> 256 -> 256 -> <= 16]", who, j);
+    if (a->head2.mode != 0)
+      DRPO_REQUIRE(a->head2.mode <= 3 && a->head2.A >= 1 && a->head2.A <= 8 &&
+                       2 * a->head2.A == a->net[1].L[2].dout,
+                   "%s: job %d second policy head shape", who, j);
+  } else {
+    DRPO_REQUIRE(a->head2.mode == 0, "%s: job %d: head2 needs a pair job", who, j);
+  }
+  if (a->pre.nl > 0) {
+    const drpo_mlp_net_t& pn = a->pre;
+    DRPO_REQUIRE(check_net(pn, a->cols[0]) && (a->pre_head.mode == 1 || a->pre_head.mode == 2) &&
+                     a->pre_head.A == a->cols[1] && a->pre_head.A >= 1 && a->pre_head.A <= 8 &&
+                     2 * a->pre_head.A == pn.L[pn.nl - 1].dout && !a->save_x && !a->nmean,
+                 "%s: job %d: a chain needs a policy net on the src[0] columns whose sampled "
+                 "action is the src[1] block (no input save / normalizer)", who, j);
+  }
+  if (a->ccb_out)
+    DRPO_REQUIRE(a->trunk && heads_pairable(a), "%s: job %d: the constraint bound needs a trunk job with paired heads",
+                 who, j);
+  if (a->post.nl > 0) {
+    const drpo_mlp_net_t& pn = a->post;
+    DRPO_REQUIRE(a->ccb_out && a->cols[0] + 1 <= 64 && check_net(pn, a->cols[0] + 1) && !a->nmean,
+                 "%s: job %d: a post chain needs the job's constraint bound (ccb_out) and a "
+                 "net on [src[0] (<= 63 columns), bound]", who, j);
+  } else {
+    DRPO_REQUIRE(!a->post_x, "%s: job %d: post_x without a post net", who, j);
+  }
+  return DRPO_OK;
 }
 
 DRPO_API int drpo_mlp_forward_multi(const drpo_mlp_fwd_t* jobs_host, const drpo_mlp_fwd_t* jobs_dev, int njobs,
@@ -546,42 +619,7 @@ DRPO_API int drpo_mlp_forward_multi(const drpo_mlp_fwd_t* jobs_host, const drpo_
   MultiGrid g;
   for (int j = 0; j < njobs; ++j) {
     const drpo_mlp_fwd_t* a = jobs_host + j;
-    if (const int e = check_fwd_job("drpo_mlp_forward_multi", j, a)) return e;
-    DRPO_REQUIRE(!a->split_heads, "drpo_mlp_forward_multi: job %d: split_heads is a single-launch mode", j);
-    DRPO_REQUIRE(!a->trunk || a->head.mode == 0, "drpo_mlp_forward_multi: policy head on a trunk job");
-    if (a->head.mode != 0)
-      DRPO_REQUIRE(a->head.mode <= 3 && a->head.A >= 1 && a->head.A <= 8 &&
-                       2 * a->head.A == a->net[0].L[a->net[0].nl - 1].dout,
-                   "drpo_mlp_forward_multi: job %d policy head shape", j);
-    if (a->pair) {
-      DRPO_REQUIRE(pair_ok(a), "drpo_mlp_forward_multi: job %d: a pair job needs two 3-layer ReLU nets of one shape "
-                               "[K <= 16 or 49..64 -> 256 -> 256 -> <= 16]", j);
-      if (a->head2.mode != 0)
-        DRPO_REQUIRE(a->head2.mode <= 3 && a->head2.A >= 1 && a->head2.A <= 8 &&
-                         2 * a->head2.A == a->net[1].L[2].dout,
-                     "drpo_mlp_forward_multi: job %d second policy head shape", j);
-    } else {
-      DRPO_REQUIRE(a->head2.mode == 0, "drpo_mlp_forward_multi: job %d: head2 needs a pair job", j);
-    }
-    if (a->pre.nl > 0) {
-      const drpo_mlp_net_t& pn = a->pre;
-      DRPO_REQUIRE(check_net(pn, a->cols[0]) && (a->pre_head.mode == 1 || a->pre_head.mode == 2) &&
-                       a->pre_head.A == a->cols[1] && a->pre_head.A >= 1 && a->pre_head.A <= 8 &&
-                       2 * a->pre_head.A == pn.L[pn.nl - 1].dout && !a->save_x && !a->nmean,
-                   "drpo_mlp_forward_multi: job %d: a chain needs a policy net on the src[0] columns whose sampled "
-                   "action is the src[1] block (no input save / normalizer)", j);
-    }
-    if (a->ccb_out)
-      DRPO_REQUIRE(a->trunk && heads_pairable(a),
-                   "drpo_mlp_forward_multi: job %d: the constraint bound needs a trunk job with paired heads", j);
-    if (a->post.nl > 0) {
-      const drpo_mlp_net_t& pn = a->post;
-      DRPO_REQUIRE(a->ccb_out && a->cols[0] + 1 <= 64 && check_net(pn, a->cols[0] + 1) && !a->nmean,
-                   "drpo_mlp_forward_multi: job %d: a post chain needs the job's constraint bound (ccb_out) and a "
-                   "net on [src[0] (<= 63 columns), bound]", j);
-    } else {
-      DRPO_REQUIRE(!a->post_x, "drpo_mlp_forward_multi: job %d: post_x without a post net", j);
-    }
+    if (const int e = check_fwd_multi_job("drpo_mlp_forward_multi", j, a)) return e;
     DRPO_REQUIRE(add_job_slots(g, m.slot_job, m.slot_net, j, (a->trunk || a->pair) ? 1 : a->nnets, a->rows, a->nbatch),
                  "drpo_mlp_forward_multi: too many nets");
   }
@@ -719,18 +757,22 @@ __host__ __device__ __forceinline__ bool bwd_paired_heads(const drpo_mlp_bwd_t& 
 
 template <int NK>
 __device__ __forceinline__ void bwd_heads_catk(const drpo_mlp_bwd_net_t& h1, const drpo_mlp_bwd_net_t& h2, const float* D1,
-                                               const float* D2, float* out, int z) {
+                                               const float* D2, float* out, int z,
+                                               const GSave& gs = GSave{nullptr, nullptr, 0, 0}) {
   tile_dense_catk<FW_NW, 1, FW_MAXC, ACT_NONE, NK>(D1, D2, LDH, h1.L[0].W + (size_t)z * h1.L[0].wstride,
                                                    h2.L[0].W + (size_t)z * h2.L[0].wstride, nullptr, h1.L[0].din, out,
-                                                   LDH);
+                                                   LDH, gs);
 }
 
 template <int NK>
 __device__ __forceinline__ void bwd_heads_out(const drpo_mlp_bwd_net_t& h1, const drpo_mlp_bwd_net_t& h2, const float* G1,
-                                              const float* G2, float* o1, float* o2, int z) {
+                                              const float* G2, float* o1, float* o2, int z,
+                                              const GSave& gs1 = GSave{nullptr, nullptr, 0, 0},
+                                              const GSave& gs2 = GSave{nullptr, nullptr, 0, 0}) {
   const int hid = h1.L[1].din;
   tile_dense_pair2<FW_NW, 1, 4, ACT_NONE, NK, 2>(G1, G2, LDH, h1.L[1].W + (size_t)z * h1.L[1].wstride, nullptr, hid, o1,
-                                              h2.L[1].W + (size_t)z * h2.L[1].wstride, nullptr, hid, o2, LDH);
+                                              h2.L[1].W + (size_t)z * h2.L[1].wstride, nullptr, hid, o2, LDH, gs1,
+                                              gs2);
 }
 
 // the critic head of a drpo_mlp_backward_multi_head launch, read in place from the
@@ -845,10 +887,13 @@ typedef const __attribute__((address_space(4))) drpo_actor_head_t ActorHeadK;
 // log-std; lam is the MLPMultiplier's transformed output (src/ssac.py:107-111) or the
 // scalar multiplier, which has no gradient where clamp(Qc, lb, ub) saturates
 // (src/ssac.py:480-484). The head outputs are the forward's saves (hm / hl last-layer
-// sy). Gm / Gl (LDS) + the output layers' saved dZ.
+// sy), or, in a fused forward + backward launch, the forward's LDS tile `lo` (mean
+// columns 0.., log-std columns 16..) and the multiplier's raw outputs `lam_lds` (one per
+// row). Gm / Gl (LDS) + the output layers' saved dZ.
 __device__ __forceinline__ void actor_cc_upstream(ActorHeadK& h, int side, const drpo_mlp_bwd_net_t& hm,
                                                   const drpo_mlp_bwd_net_t* hl, float* Gm, float* Gl, int row0,
-                                                  int nrows) {
+                                                  int nrows, const float* lo = nullptr,
+                                                  const float* lam_lds = nullptr) {
   const int C = h.C, opad = round_up(C, 16);
   const bool dist = h.distributional;
   const float* __restrict__ mu = hm.L[hm.nl - 1].sy;
@@ -865,14 +910,14 @@ __device__ __forceinline__ void actor_cc_upstream(ActorHeadK& h, int side, const
       float best = 0.f, lbest = 0.f;
       int bi = 0;
       for (int c = 0; c < C; ++c) {
-        float v = gload(mu + i * C + c);
-        const float l = dist ? gload(ls + i * C + c) : 0.f;
+        float v = lo ? lo[r * LDH + c] : gload(mu + i * C + c);
+        const float l = dist ? (lo ? lo[r * LDH + 16 + c] : gload(ls + i * C + c)) : 0.f;
         if (dist) v = v + h.std_ratio * cc_std(l, h.log_std_min, h.log_std_max);
         if (c == 0 || v > best) { best = v; bi = c; lbest = l; }
       }
       float g = invB;
       if (side == 0) {
-        float lam = h.lams ? gload(h.lams + i) : h.fixed_lam;
+        float lam = h.lams ? (lam_lds ? lam_lds[r] : gload(h.lams + i)) : h.fixed_lam;
         const float ub = h.lam_upper_bound;
         if (h.lams && ub > 0.f) lam = multiplier_lam(lam, ub);
         if (!h.lams && (best < h.clamp_lb || best > h.clamp_ub)) lam = 0.f;       // clamped scalar-lam term
@@ -1022,6 +1067,18 @@ __device__ __forceinline__ void bwd_heads_paired(const drpo_mlp_bwd_t& __restric
   STAMPW(4);
 }
 
+// the requested input-gradient columns of net n from the tile's input gradient (LDS)
+__device__ __forceinline__ void store_dx_tile(const drpo_mlp_bwd_net_t& n, const float* src, int z, int64_t rows,
+                                              int row0, int nrows) {
+  if (!n.dx) return;
+  for (int e = threadIdx.x; e < nrows * n.dx_cols; e += FW_NT) {
+    const int r = e / n.dx_cols, k = e - r * n.dx_cols;
+    float* p = n.dx + ((size_t)z * rows + row0 + r) * n.dx_cols + k;
+    const float v = src[r * LDH + n.dx_col0 + k];
+    gstore(p, n.dx_accumulate ? gload(p) + v : v);
+  }
+}
+
 // one (job, net) slot of the fused backward-data pass; `a` may live in kernarg
 // (single launch) or global memory (multi-job launch)
 template <int UPF>
@@ -1047,15 +1104,7 @@ __device__ __forceinline__ void bwd_body(const drpo_mlp_bwd_t& __restrict__ a, i
     }
     lds_barrier();
   };
-  auto store_dx = [&](const drpo_mlp_bwd_net_t& n, const float* src) {
-    if (!n.dx) return;
-    for (int e = tid; e < nrows * n.dx_cols; e += FW_NT) {
-      const int r = e / n.dx_cols, k = e - r * n.dx_cols;
-      float* p = n.dx + ((size_t)z * a.rows + row0 + r) * n.dx_cols + k;
-      const float v = src[r * LDH + n.dx_col0 + k];
-      gstore(p, n.dx_accumulate ? gload(p) + v : v);
-    }
-  };
+  auto store_dx = [&](const drpo_mlp_bwd_net_t& n, const float* src) { store_dx_tile(n, src, z, a.rows, row0, nrows); };
 
   // output gradients formed in-kernel from the launch's critic head (no head launch)
   if constexpr ((UPF & UPF_CRITIC) == 0) ch = nullptr;
@@ -1374,3 +1423,182 @@ static int bwd_multi_launch(const drpo_mlp_bwd_t* jobs_host, const drpo_mlp_bwd_
   return DRPO_OK;
 }
 
+
+// ---------------------------------------------------------------------------
+// fused forward + backward-data: one workgroup runs a tile's whole chain
+// ---------------------------------------------------------------------------
+// The actor update's pass through the frozen critics (drpo_mlp_fb_multi): the forwards of
+// a job (fwd_multi_body, the multi-job forward's own body), the output gradients from the
+// forward's outputs in LDS, then the backward products -- the products of bwd_net /
+// bwd_heads_paired in the same order, with act' applied in each product's epilogue from the
+// ReLU masks the forward's epilogues left in LDS (GSave.mk) instead of an elementwise
+// phase over saved activations. Nothing here waits on another workgroup.
+struct FbArgs {
+  const drpo_mlp_fwd_t* fwd;
+  const drpo_mlp_bwd_t* bwd;
+  drpo_mlp_fb_job_t job[FB_MAXJOB];
+  uint64_t seed, ctr;
+  drpo_actor_head_t actor;
+};
+
+// G = dL/dZ of the net's last layer (LDS) -> the gradient w.r.t. the net's input (returned
+// LDS buffer); mk: the masks of the net's layers (slot l = layer l's output)
+__device__ __forceinline__ float* bwd_net_fb(const drpo_mlp_bwd_net_t& __restrict__ net, float* G, float* bA, float* bB,
+                                             int z, unsigned long long* mk, bool need_dx0) {
+  float* cur = G;
+  for (int l = net.nl - 1; l >= 0; --l) {
+    if (l == 0 && !need_dx0) return nullptr;
+    const drpo_mlp_bwd_layer_t& L = net.L[l];
+    float* out = (cur == bA) ? bB : bA;
+    GSave gs{nullptr, nullptr, 0, 0};
+    gs.mk = l > 0 ? mk + FB_MKW * (l - 1) : nullptr;
+    // dZ_prev = (dZ W) * relu'(y_prev): transposed mirror, N = din, K = dout
+    tile_dense<FW_NW, 1, FW_MAXC, ACT_NONE>(cur, LDH, L.dout, L.W + (size_t)z * L.wstride, nullptr, L.din, out, LDH, gs);
+    lds_barrier();
+    cur = out;
+  }
+  return cur;
+}
+
+__global__ __launch_bounds__(FW_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void mlp_fb_multi_kernel(FbArgs m) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  typedef const __attribute__((address_space(4))) FbArgs* ArgsK;
+  ArgsK k = (ArgsK)__builtin_amdgcn_kernarg_segment_ptr();
+  float* X = smem;                       // the forward's input tile, then its narrow outputs
+  float* G = X + FW_ROWS * LDH;
+  float* bA = G + FW_ROWS * LDH;
+  float* bB = bA + FW_ROWS * LDH;
+  float* lamS = bB + FW_ROWS * LDH + FW_NW * 256;   // behind the forward's reduction scratch
+  unsigned long long* mk = reinterpret_cast<unsigned long long*>(lamS + FW_ROWS);
+  const int tid = threadIdx.x;
+  const int nf = k->job[blockIdx.y].nfwd;
+  const drpo_mlp_bwd_t& __restrict__ a = m.bwd[k->job[blockIdx.y].bwd];
+  const int row0 = blockIdx.x * FW_ROWS;
+  if (row0 >= a.rows) return;
+  const int nrows = (int)min((int64_t)FW_ROWS, a.rows - row0);
+  // (two calls, not a loop over the job's forwards: around a loop the register
+  // allocation of the layer cores spilled several hundred VGPRs)
+  if (nf == 2) {
+    const FwdOut f0 = fwd_multi_body<1, true>(m.fwd + k->job[blockIdx.y].fwd[0], 0, blockIdx.x, 0, m.seed, m.ctr, smem);
+    if (tid < FW_ROWS) lamS[tid] = f0.post[tid * LDH];   // the multiplier's raw output of each row
+    lds_barrier();
+  }
+  const FwdOut fo =
+      fwd_multi_body<1, true>(m.fwd + k->job[blockIdx.y].fwd[nf - 1], 0, blockIdx.x, 0, m.seed, m.ctr, smem, mk);
+  lds_barrier();
+  ActorHeadK& ah = k->actor;
+  if (!a.trunk) {
+    // -mean(Q_k) (src/ssac.py:472): dL/dQ = -1/B
+    const drpo_mlp_bwd_net_t& n = a.net[0];
+    for (int e = tid; e < FW_ROWS * 16; e += FW_NT) {
+      const int r = e >> 4, c = e & 15;
+      G[r * LDH + c] = (r < nrows && c == 0) ? -1.f / (float)ah.B : 0.f;
+    }
+    lds_barrier();
+    const float* gx = bwd_net_fb(n, G, bA, bB, 0, mk, n.dx != nullptr);
+    if (gx) store_dx_tile(n, gx, 0, a.rows, row0, nrows);
+    return;
+  }
+  // trunk + paired heads: the heads' output gradients from the forward's outputs in X
+  const drpo_mlp_bwd_net_t &h1 = a.net[1], &h2 = a.net[2];
+  actor_cc_upstream(ah, a.upstream == DRPO_UPSTREAM_SAFE_CC, h1, &h2, G, bA, row0, nrows, fo.out, nf > 1 ? lamS : nullptr);
+  lds_barrier();
+  // dZ(hidden) of both heads (X: the outputs are consumed), then the trunk-output dZ as
+  // one concatenated-K product
+  GSave g1{nullptr, nullptr, 0, 0}, g2{nullptr, nullptr, 0, 0}, gt{nullptr, nullptr, 0, 0};
+  g1.mk = mk + 3 * FB_MKW;
+  g2.mk = mk + 4 * FB_MKW;
+  gt.mk = mk + FB_MKW * (a.net[0].nl - 1);
+  bwd_heads_out<1>(h1, h2, G, bA, bB, X, 0, g1, g2);
+  lds_barrier();
+  bwd_heads_catk<16>(h1, h2, bB, X, G, 0, gt);
+  lds_barrier();
+  const float* gx = bwd_net_fb(a.net[0], G, bA, bB, 0, mk, a.net[0].dx != nullptr);
+  if (gx) store_dx_tile(a.net[0], gx, 0, a.rows, row0, nrows);
+}
+
+static size_t fb_lds() {
+  return fwd_lds() + sizeof(float) * FW_ROWS + sizeof(unsigned long long) * FB_MKSLOTS * FB_MKW;
+}
+
+// the last forward of a fused job and its backward must describe the same layers
+static int fb_same_net(const drpo_mlp_net_t& f, const drpo_mlp_bwd_net_t& b) {
+  if (f.nl != b.nl) return 0;
+  for (int l = 0; l < f.nl; ++l)
+    if (f.L[l].din != b.L[l].din || f.L[l].dout != b.L[l].dout || f.L[l].act != b.L[l].act) return 0;
+  return 1;
+}
+
+DRPO_API int drpo_mlp_fb_multi(const drpo_mlp_fwd_t* fwd_host, const drpo_mlp_fwd_t* fwd_dev, int nfwd,
+                               const drpo_mlp_bwd_t* bwd_host, const drpo_mlp_bwd_t* bwd_dev, int nbwd,
+                               const drpo_mlp_fb_job_t* jobs, int njobs, const drpo_actor_head_t* actor,
+                               uint64_t seed, uint64_t ctr, drpo_stream_t stream_) {
+  const char* who = "drpo_mlp_fb_multi";
+  DRPO_REQUIRE(fwd_host && fwd_dev && bwd_host && bwd_dev && jobs && nfwd >= 1 && nbwd >= 1 && njobs >= 1 &&
+                   njobs <= FB_MAXJOB,
+               "%s: 1..%d jobs over forward and backward descriptor arrays", who, FB_MAXJOB);
+  DRPO_REQUIRE(actor && actor->B >= 0 && actor->A >= 1 && actor->A <= 8 && actor->C >= 1 && actor->C <= 16,
+               "%s: bad actor head", who);
+  FbArgs m{};
+  m.fwd = fwd_dev;
+  m.bwd = bwd_dev;
+  m.seed = seed;
+  m.ctr = ctr;
+  m.actor = *actor;
+  for (int j = 0; j < njobs; ++j) {
+    const drpo_mlp_fb_job_t& J = jobs[j];
+    DRPO_REQUIRE(J.nfwd >= 1 && J.nfwd <= 2 && J.bwd >= 0 && J.bwd < nbwd, "%s: job %d: 1..2 forwards and a backward of "
+                 "the launch's arrays", who, j);
+    m.job[j] = J;
+    for (int i = 0; i < J.nfwd; ++i) {
+      DRPO_REQUIRE(J.fwd[i] >= 0 && J.fwd[i] < nfwd, "%s: job %d: forward index %d", who, j, J.fwd[i]);
+      const drpo_mlp_fwd_t* f = fwd_host + J.fwd[i];
+      if (const int e = check_fwd_multi_job(who, j, f)) return e;
+      DRPO_REQUIRE(!f->pair && !f->head.mode && !f->head2.mode && !f->pre.nl && f->nbatch == 1 &&
+                       (f->trunk || f->nnets == 1),
+                   "%s: job %d: forward %d: one batch item, one net or a trunk job, no pair / head / head2 / pre", who, j,
+                   i);
+      DRPO_REQUIRE(f->rows == actor->B, "%s: job %d: forward %d has %lld rows, the actor head %lld", who, j, i,
+                   (long long)f->rows, (long long)actor->B);
+      if (i < J.nfwd - 1)
+        DRPO_REQUIRE(f->post.nl > 0 && f->post.L[f->post.nl - 1].dout == 1 && actor->lams,
+                     "%s: job %d: a first forward must end in a post chain with one output (the multiplier)", who, j);
+    }
+    const drpo_mlp_fwd_t* f = fwd_host + J.fwd[J.nfwd - 1];
+    const drpo_mlp_bwd_t* b = bwd_host + J.bwd;
+    if (const int e = check_bwd(who, j, b)) return e;
+    DRPO_REQUIRE(!b->split_heads && b->nbatch == 1 && b->rows == actor->B && b->trunk == f->trunk &&
+                     b->nnets == f->nnets,
+                 "%s: job %d: the backward must describe the last forward's nets (one batch item, the actor head's rows)",
+                 who, j);
+    for (int h = 0; h < b->nnets; ++h) {
+      const drpo_mlp_bwd_net_t& n = b->net[h];
+      DRPO_REQUIRE(fb_same_net(f->net[h], n), "%s: job %d: net %d differs between the forward and the backward", who, j, h);
+      for (int l = 0; l < n.nl; ++l) {
+        DRPO_REQUIRE(!n.L[l].dz && !n.L[l].dz2, "%s: job %d: net %d layer %d: dz saves are not written here", who, j, h, l);
+        const bool hidden = l < n.nl - 1 || (b->trunk && h == 0);
+        DRPO_REQUIRE(n.L[l].act == (hidden ? ACT_RELU : ACT_NONE) && (!hidden || n.L[l].dout > 16),
+                     "%s: job %d: net %d layer %d: hidden layers are ReLU and wider than 16, outputs identity", who, j, h,
+                     l);
+      }
+    }
+    if (!b->trunk) {
+      const drpo_mlp_bwd_net_t& n0 = b->net[0];
+      DRPO_REQUIRE(b->upstream == DRPO_UPSTREAM_NEG_MEAN && n0.L[n0.nl - 1].dout == 1 && J.nfwd == 1,
+                   "%s: job %d: a single net takes the -1/B upstream on one output, after one forward", who, j);
+    } else {
+      DRPO_REQUIRE((b->upstream == DRPO_UPSTREAM_ACTOR_CC || b->upstream == DRPO_UPSTREAM_SAFE_CC) &&
+                       heads_pairable(f) && bwd_paired_heads(*b) && b->net[1].L[0].dout == 256 &&
+                       b->net[0].L[b->net[0].nl - 1].dout == 256 && b->net[1].L[1].dout == actor->C,
+                   "%s: job %d: a trunk job takes the constraint-critic upstream on paired 256-wide heads "
+                   "[256 -> 256 -> C]", who, j);
+      DRPO_REQUIRE(J.nfwd == 1 || b->upstream == DRPO_UPSTREAM_ACTOR_CC,
+                   "%s: job %d: only the actor's certificate job chains the multiplier forward in front", who, j);
+    }
+  }
+  const int64_t tiles = (actor->B + FW_ROWS - 1) / FW_ROWS;
+  if (tiles == 0) return DRPO_OK;
+  mlp_fb_multi_kernel<<<dim3((unsigned)tiles, njobs, 1), FW_NT, fb_lds(), (hipStream_t)stream_>>>(m);
+  DRPO_LAUNCH_CHECK("mlp_fb_multi");
+  return DRPO_OK;
+}

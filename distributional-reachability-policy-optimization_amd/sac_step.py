@@ -7,11 +7,17 @@ Per update_solver call (DRPO flags, actor on, multiplier on) the device runs:
   certificate on (s, a), the twin critics paired), ONE backward-data launch with the
   critic / certificate losses formed in-kernel ('c.b1'), ONE grouped weight-gradient
   launch (+ clip partials), ONE fused clip + Adam + EMA launch -> [actor] 'a.f1'
-  (actor + safe actor paired, rsample heads), 'a.f2' (critics at (s, a), (s, a_safe),
-  the certificate at tanh(mu_safe)), 'a.mult', 'a.b' (backward with the actor losses
-  formed in-kernel), 'a.bpi' (both squashed-Gaussian backwards), ONE weight-gradient
-  launch, ONE optimizer launch (+ alpha) -> [multiplier] 'm.f1', 'm.f2', 'm.mult',
-  multiplier_head, backward, weight-gradient, optimizer.
+  (actor + safe actor paired, rsample heads; with device noise it rides in 'c.f'), 'a.fb'
+  (ONE launch through the frozen critics: per 16-row tile the certificate at tanh(mu_safe)
+  -> multiplier -> certificate at (s, a) -> its backward; the certificate at (s, a_safe)
+  and its backward; Q_k(s, a) and its backward -- the actor losses formed in-kernel, the
+  ReLU masks kept on chip), 'a.bpi' (both squashed-Gaussian backwards), ONE
+  weight-gradient launch, ONE optimizer launch (+ alpha) -> [multiplier] 'm.f1', 'm.f2',
+  'm.mult', multiplier_head, backward, weight-gradient, optimizer.
+Compositions 'a.fb' does not cover (fb_actor off, cost certificate, scalar multiplier,
+unpaired heads, other activations) run 'a.f2' (critics at (s, a), (s, a_safe), the
+certificate at tanh(mu_safe)), 'a.mult' and 'a.b' (backward with the actor losses formed
+in-kernel) in its place.
 All launch descriptors point at static workspaces, so they are built once per
 batch size and the whole sequence is graph-capturable. Noise: Philox in the
 kernels (production) or the reference's recorded draws (parity TapeNoise), which
@@ -23,8 +29,8 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from ._abi import ActorHead, BufferView, CriticHead, SumDesc
-from .mlp_desc import (HEAD_MEAN, HEAD_RSAMPLE, HEAD_SAMPLE, UPSTREAM_ACTOR_CC, UPSTREAM_CERT, UPSTREAM_CRITIC,
+from ._abi import ActorHead, BufferView, CriticHead, MlpFbJob, SumDesc
+from .mlp_desc import (ACT_ID, HEAD_MEAN, HEAD_RSAMPLE, HEAD_SAMPLE, UPSTREAM_ACTOR_CC, UPSTREAM_CERT, UPSTREAM_CRITIC,
                        UPSTREAM_NEG_MEAN, UPSTREAM_SAFE_CC, UPSTREAM_SQUASH, UPSTREAM_SQUASH_SAFE, Net, _p,
                        bwd_flops, fill_bwd, fill_fwd, fwd_flops, pairable, spec_layers, wgrad_flops, wgrad_items,
                        wgrad_workspace, with_head, with_post, with_pre)
@@ -74,6 +80,10 @@ class SACEngine:
         # (False: its own launch, the reference of
         # tests/test_gpu_configs.py::test_multiplier_post_chain_matches_separate_launch)
         self.post_mult = True
+        # production dispatch: the actor update's pass through the frozen critics as ONE
+        # forward + backward launch, 'a.fb' (False: 'a.f2' + 'a.b', the reference of
+        # tests/test_gpu_sac_fb.py)
+        self.fb_actor = True
 
     # ------------------------------------------------------------------ buffers
     def buf(self, name, *shape, dtype=torch.float32):
@@ -226,6 +236,27 @@ class SACEngine:
             call = lambda d: L.drpo_mlp_backward_multi(d[0], d[1].data_ptr(), d[2], st)
         self._launch('mlp_bwd', key, lambda: self._jobs(builder(), bwd_flops), lambda d: d[3], call)
 
+    def _run_fb(self, key, builder, ctr, actor):
+        """Forward + backward-data of the builder's jobs in one launch (drpo_mlp_fb_multi).
+        builder() -> (forward descriptors, backward descriptors, [(forward indices, backward
+        index)]); the launch's FLOPs are those of its parts."""
+        def build():
+            fw, bw, jobs = builder()
+            fa, fdev, nf, _ = self._jobs(fw, fwd_flops)
+            ba, bdev, nb, _ = self._jobs(bw, bwd_flops)
+            ja = (MlpFbJob * len(jobs))()
+            flops = 0
+            for J, (fi, bi) in zip(ja, jobs):
+                J.nfwd, J.bwd = len(fi), bi
+                for q, i in enumerate(fi):
+                    J.fwd[q] = i
+                flops += sum(fwd_flops(fw[i]) for i in fi) + bwd_flops(bw[bi])
+            return fa, fdev, nf, ba, bdev, nb, ja, len(jobs), flops
+        self._launch('mlp_fb', key, build, lambda d: d[8],
+                     lambda d: _lib.lib().drpo_mlp_fb_multi(d[0], d[1].data_ptr(), d[2], d[3], d[4].data_ptr(), d[5],
+                                                            d[6], d[7], ctypes.byref(actor), self.noise.seed, ctr,
+                                                            _lib.stream()))
+
     def _run_bwd(self, key, builder):
         self._launch('mlp_bwd', key, builder, bwd_flops,
                      lambda d: _lib.lib().drpo_mlp_backward(ctypes.byref(d), _lib.stream()))
@@ -290,6 +321,23 @@ class SACEngine:
         drpo_mlp_fwd_t.post) when the shapes allow it (self.post_mult)."""
         return (self.post_mult and self._ccb_fused() and self.S + 1 <= 64 and
                 self.nets['mult'].layers[0][2] == self.S + 1)
+
+    def _fb_actor(self, dist):
+        """The actor update runs 'a.fb' (drpo_mlp_fb_multi's conditions, csrc/mlp.hip): the
+        MLP multiplier as a post chain, the distributional certificate with paired
+        256-wide heads, not the cost certificate, ReLU hidden layers wider than 16 and
+        identity outputs everywhere."""
+        sol, n = self.sol, self.nets
+        if not (self.fb_actor and sol.mlp_multiplier and dist and not self.cost and self._post_mult()):
+            return False
+        relu = ACT_ID['relu']
+        t, h1, h2 = self._cc_nets()
+
+        def hidden(layers):
+            return all(l[4] == relu and l[3] > 16 for l in layers)
+        return (n['mult'].dout == 1 and hidden(t.layers) and
+                all(hidden(h.layers[:1]) and h.layers[0][3] == 256 and h.layers[1][4] == 0 for h in (h1, h2)) and
+                all(hidden(q.layers[:-1]) and tuple(q.layers[-1][3:5]) == (1, 0) for q in (n['q0'], n['q1'])))
 
     def _cc_bound_after(self, name, out, dist):
         """drpo_cc_head over the saved head outputs of job `name` when _ccb could not fuse it."""
@@ -518,10 +566,14 @@ class SACEngine:
         # (job order = workgroup dispatch order: the multiplier's chained job, Q_k, then the
         # certificate jobs measured 86.8 us against 90.9 us for the reverse order
         # (profiles/r05/early_actor/order); m.f2 keeps its chained job first)
-        self._run_multi(f'a.f2.{k}{int(mlp_mult)}{int(post)}', lambda: ([ccm()] if mlp_mult else []) + [
-            fill_fwd([self._reuse(qk, f'a.q{k}')], [(self.bs, S), (a, A), (None, 0)], B)] + (
-            [] if cost else [fill_fwd(self._reuse_cc('a.cc2'), [(self.bs, S), (a_s, A), (None, 0)], B, trunk=True)]) + [
-            fill_fwd(self._reuse_cc('a.cc'), [(self.bs, S), (a, A), (None, 0)], B, trunk=True)], ctr)
+        # production: the forwards below run inside 'a.fb' (further down), fused with their backward
+        fb = self._fb_actor(dist)
+        if not fb:
+            self._run_multi(f'a.f2.{k}{int(mlp_mult)}{int(post)}', lambda: ([ccm()] if mlp_mult else []) + [
+                fill_fwd([self._reuse(qk, f'a.q{k}')], [(self.bs, S), (a, A), (None, 0)], B)] + (
+                [] if cost else [fill_fwd(self._reuse_cc('a.cc2'), [(self.bs, S), (a_s, A), (None, 0)], B,
+                                          trunk=True)]) + [
+                fill_fwd(self._reuse_cc('a.cc'), [(self.bs, S), (a, A), (None, 0)], B, trunk=True)], ctr)
         if mlp_mult and not post:
             # lam = multiplier(s, max_C Qc_ub(s, tanh(mu_safe)))  (no grad); the bound is formed
             # by the forward launch above
@@ -543,7 +595,7 @@ class SACEngine:
             ah.B, ah.C, ah.A, ah.distributional = B, C, A, int(dist)
             ah.std_ratio, ah.log_std_min, ah.log_std_max = float(cc.std_ratio), float(cc.log_std_min), \
                 float(cc.log_std_max)
-            ah.lams = ws['a.multx'].data_ptr() if mlp_mult else 0
+            ah.lams = self.buf('a.multx', B, n['mult'].dout).data_ptr() if mlp_mult else 0
             ah.lam_upper_bound, ah.fixed_lam = ub, float(sol.fixed_multiplier)
             ah.clamp_lb, ah.clamp_ub = float(sol.penalty_lb), float(sol.penalty_ub)
             ah.u[0], ah.e[0], ah.u[1], ah.e[1] = u.data_ptr(), e.data_ptr(), u_s.data_ptr(), e_s.data_ptr()
@@ -555,15 +607,35 @@ class SACEngine:
         # dL/da of the actor (Q_k part + certificate part, summed in the squash backward in
         # the reference's order) and of the safe actor: one backward launch
         dA, dAc, dAs = self.buf('a.dA', B, A), self.buf('a.dAc', B, A), self.buf('a.dAs', B, A)
-        hv, hv2 = self.nets_view['a.cc'], self.nets_view.get('a.cc2')
-        nh = 3 if dist else 2   # trunk + mean head (+ log-std head)
-        self._run_bwd_multi(f'a.b.{k}{int(dist)}', lambda: [
-            fill_bwd(hv[:nh], [None] * nh, B, trunk=True, dx={0: (dAc, S, A, False)}, upstream=UPSTREAM_ACTOR_CC)] + (
-            [] if cost else [
-                fill_bwd(hv2[:nh], [None] * nh, B, trunk=True, dx={0: (dAs, S, A, False)},
-                         upstream=UPSTREAM_SAFE_CC)]) + [
-            fill_bwd([self.nets_view[f'a.q{k}']], [None], B, dx={0: (dA, S, A, False)}, upstream=UPSTREAM_NEG_MEAN)],
-            actor=ah)
+        if fb:
+            # ONE launch, three jobs per 16-row tile, longest chain first (per row about 672 k,
+            # 400 k and 275 k MACs: on two workgroup slots per CU 672 k against 675 k):
+            #   Qc(s, tanh(mu_safe)) -> bound -> multiplier (lam stays in LDS) -> Qc(s, a) ->
+            #   lam / B on its bound -> backward -> a.dAc;   Qc(s, a_safe) -> 1 / B -> backward
+            #   -> a.dAs;   Q_k(s, a) -> -1 / B -> backward -> a.dA.
+            # Only the nets' outputs are saved: no hidden layer of them leaves the CU.
+            # (measured, profiles/sac_fb: this order 123.4 us, the short jobs swapped 123.5, the
+            # long chain second 125.0, last 136.4)
+            def fb_jobs():
+                cc, cc2, q = self._fb_cc('a.cc'), self._fb_cc('a.cc2'), self._fb_net(qk, f'a.q{k}')
+                fw = [ccm()] + [fill_fwd(nets, [(self.bs, S), (act, A), (None, 0)], B, trunk=len(nets) > 1)
+                                for nets, act in ((cc, a), (cc2, a_s), ([q], a))]
+                bw = [fill_bwd(cc, [None] * 3, B, trunk=True, dx={0: (dAc, S, A, False)}, upstream=UPSTREAM_ACTOR_CC),
+                      fill_bwd(cc2, [None] * 3, B, trunk=True, dx={0: (dAs, S, A, False)}, upstream=UPSTREAM_SAFE_CC),
+                      fill_bwd([q], [None], B, dx={0: (dA, S, A, False)}, upstream=UPSTREAM_NEG_MEAN)]
+                return fw, bw, [((0, 1), 0), ((2,), 1), ((3,), 2)]
+            self._run_fb(f'a.fb.{k}', fb_jobs, ctr, ah)
+        else:
+            hv, hv2 = self.nets_view['a.cc'], self.nets_view.get('a.cc2')
+            nh = 3 if dist else 2   # trunk + mean head (+ log-std head)
+            self._run_bwd_multi(f'a.b.{k}{int(dist)}', lambda: [
+                fill_bwd(hv[:nh], [None] * nh, B, trunk=True, dx={0: (dAc, S, A, False)},
+                         upstream=UPSTREAM_ACTOR_CC)] + (
+                [] if cost else [
+                    fill_bwd(hv2[:nh], [None] * nh, B, trunk=True, dx={0: (dAs, S, A, False)},
+                             upstream=UPSTREAM_SAFE_CC)]) + [
+                fill_bwd([self.nets_view[f'a.q{k}']], [None], B, dx={0: (dA, S, A, False)},
+                         upstream=UPSTREAM_NEG_MEAN)], actor=ah)
         asum = self.alpha_sum
         self._clean_grads(sol.actor.group)
         if not cost:
@@ -662,6 +734,21 @@ class SACEngine:
                 v.sy[l] = self.buf(f'{name}.sy{l}', self.B, dout)
             self.nets_view[name] = v
         return v
+
+    def _fb_net(self, net, name):
+        """A view of `net` for the fused forward + backward launch: only a narrow final
+        output is saved (in the buffer _reuse names), no hidden layer."""
+        v = self.nets_view.get('fb.' + name)
+        if v is None:
+            v = Net(net.layers, net.grad_layers)
+            last = len(net.layers) - 1
+            if net.layers[last][3] <= 16:
+                v.sy[last] = self.buf(f'{name}.sy{last}', self.B, net.dout)
+            self.nets_view['fb.' + name] = v
+        return v
+
+    def _fb_cc(self, name):
+        return [self._fb_net(x, f'{name}.{i}') for i, x in enumerate(self._cc_nets())]
 
     def _reuse_cc(self, name):
         v = self.nets_view.get(name)

@@ -406,6 +406,32 @@ int drpo_mlp_backward_multi_head(const drpo_mlp_bwd_t* jobs_host, const drpo_mlp
  * their output gradients from `head` */
 int drpo_mlp_backward_multi_actor(const drpo_mlp_bwd_t* jobs_host, const drpo_mlp_bwd_t* jobs_dev, int njobs,
                                   const drpo_actor_head_t* head /* host */, drpo_stream_t stream);
+/* One job of drpo_mlp_fb_multi: forward descriptors fwd[0 .. nfwd) (indices into the launch's
+ * forward array, run in this order) and then backward descriptor bwd (an index into its
+ * backward array), all for the same 16-row tile in one workgroup. */
+typedef struct {
+  int nfwd;            /* 1 or 2 */
+  int fwd[2];
+  int bwd;
+} drpo_mlp_fb_job_t;
+/* Forward + backward-data of up to 4 jobs in ONE launch (the actor update's pass through the
+ * frozen critics, src/ssac.py:470-494): one workgroup per (job, 16-row tile) runs the job's
+ * forwards as drpo_mlp_forward_multi would, forms the output gradients as
+ * drpo_mlp_backward_multi_actor would -- from the forward's outputs in LDS -- and runs the
+ * backward products. The ReLU masks of the last forward's hidden layers stay in LDS and
+ * are applied in the backward products' epilogues, so the hidden layers need no sy save
+ * (the backward descriptors' sy / sz are not read). Computes what the two launches compute.
+ *   - every forward: one batch item, no pair / head / head2 / pre; the first of two forwards
+ *     carries a post chain whose single output per row is the job's multiplier value lam
+ *     (instead of actor->lams)
+ *   - the last forward and the backward describe the same nets: ONE net [K -> 256.. -> 1]
+ *     with DRPO_UPSTREAM_NEG_MEAN, or a trunk with paired 256-wide heads [256 -> 256 -> C <= 16]
+ *     with DRPO_UPSTREAM_ACTOR_CC / _SAFE_CC; ReLU hidden layers, identity outputs
+ *   - no dz / dz2 saves (the nets are frozen); the input gradient dx as in the backward launch */
+int drpo_mlp_fb_multi(const drpo_mlp_fwd_t* fwd_host, const drpo_mlp_fwd_t* fwd_dev, int nfwd,
+                      const drpo_mlp_bwd_t* bwd_host, const drpo_mlp_bwd_t* bwd_dev, int nbwd,
+                      const drpo_mlp_fb_job_t* jobs /* host */, int njobs, const drpo_actor_head_t* head /* host */,
+                      uint64_t seed, uint64_t ctr, drpo_stream_t stream);
 /* the model fit's backward with the NLL loss fused in: desc->upstream = DRPO_UPSTREAM_ENS,
  * trunk + paired diff / log-var heads. reduce_out receives the deferred reduction
  * (mse / loss / gmin / gmax / weight: from `red_in`, partial layout from this launch). */
