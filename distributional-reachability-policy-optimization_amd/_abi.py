@@ -106,9 +106,6 @@ PROTOTYPES = {
     'drpo_event_elapsed_ms': (c_int, [POINTER(c_float), P, P]),
     'drpo_grad_sumsq_blocks': (c_int, [c_int64]),
     'drpo_grad_sumsq': (c_int, [P, c_int64, P, P]),
-    'drpo_adam': (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, P, c_int,
-                          c_float, P, P]),
-    'drpo_ema': (c_int, [P, P, c_int64, c_float, P]),
     'drpo_normalizer_workspace_size': (c_size_t, [c_int64, c_int]),
     'drpo_normalizer_fit': (c_int, [P, c_int64, c_int, P, P, P, P]),
     'drpo_normalize': (c_int, [P, P, P, c_float, P, c_int64, c_int, P]),

@@ -149,6 +149,58 @@ __device__ __forceinline__ void adam_step(const Opt& S, float coef, float g, flo
   p = p - S.lr_over_bc1 * (m / denom);
 }
 
+// Fixed-order sums (deterministic: no float atomics). wave_sum: the 64 lanes' values by a
+// shuffle-down tree, the total in lane 0. block_tree_sum: one value per thread of a
+// 256-thread workgroup through red[256] (LDS), the total returned to every thread; red may
+// be reused after the caller's next barrier.
+__device__ __forceinline__ float wave_sum(float v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float block_tree_sum(float v, float* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int w = WG / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// The item a workgroup belongs to, when item i owns the workgroups [a.first[i], a.first[i+1])
+// (a.first[0] == 0, unused entries INT64_MAX): the number of starts <= bid, minus one. All N
+// starts are read at once (independent scalar loads, one kernarg round trip) where a
+// search costs a dependent load per item passed.
+template <int N, typename Args>
+__device__ __forceinline__ int block_item(const Args& a, int64_t bid) {
+  int q = -1;
+#pragma unroll
+  for (int i = 0; i < N; ++i) q += bid >= a.first[i] ? 1 : 0;
+  return q;
+}
+
+// n (<= 4) consecutive floats at p <-> x[0 .. n); vec: n == 4 and p 16-byte aligned, one
+// access. Elements past n are neither read nor written.
+__device__ __forceinline__ void load_row4(const float* p, bool vec, int n, float (&x)[4]) {
+  if (vec) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+    x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; x[3] = v[3];
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (e < n) x[e] = p[e];
+  }
+}
+__device__ __forceinline__ void store_row4(float* p, bool vec, int n, const float (&x)[4]) {
+  if (vec) {
+    *reinterpret_cast<f32x4*>(p) = f32x4{x[0], x[1], x[2], x[3]};
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (e < n) p[e] = x[e];
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Philox4x32-10
 // ---------------------------------------------------------------------------
@@ -203,7 +255,7 @@ __device__ __forceinline__ float normal_at(const float* eps, int64_t idx, uint64
 // fed as 4 MFMAs where lane group g=l>>4 supplies k = k0+4g+m for MFMA m, so
 // both operands are loaded as one float4 per lane (A: ds_read_b128 from LDS).
 //
-// Weights are read from a PACKED mirror (csrc/pack.hip, drpo_pack_weights): the
+// Weights are read from a PACKED mirror (pack_layout.hpp, drpo_pack_weights): the
 // B fragment of (16-column block cb, 16-deep k-step s) is 256 contiguous floats,
 // lane l's float4 at offset 4*l, zero-padded beyond N and K:
 //     P[(cb*NKS + s)*256 + 4*l + i] = W[16*cb + (l&15)][16*s + 4*(l>>4) + i]

@@ -1,124 +1,20 @@
 // Optimizer-side kernels over flat parameter groups (one launch covers a whole
-// group or clip segment, HBM-bound):
-//   drpo_grad_sumsq  : per-block partial sums of g^2 (first pass of clip_grad_norm_)
-//   drpo_adam        : torch.optim.Adam (coupled L2 weight decay, single-tensor
-//                      formulas) with the clip coefficient min(1, max/(||g||+1e-6))
-//                      applied on the fly from the partial sums (deterministic:
-//                      every block reduces the same partials in the same order)
-//   drpo_ema         : target <- rate*p + (1-rate)*target (src/torch_util.py:223-226)
+// group or several clip segments, HBM-bound):
+//   drpo_grad_sumsq[_multi] : per-block partial sums of g^2 (first pass of clip_grad_norm_)
+//   drpo_optim_step  : torch.optim.Adam (coupled L2 weight decay, single-tensor
+//                      formulas; adam_step in common.hpp) with the clip coefficient
+//                      min(1, max/(||g||+1e-6)) applied on the fly from the partial sums
+//                      (deterministic: every block reduces the same partials in the same
+//                      order), gradient zeroing, the EMA target <- rate*p + (1-rate)*target
+//                      (src/torch_util.py:223-226) and the packed-mirror refresh
 //   drpo_normalizer_fit : column mean / unbiased std over the replay states
 //                      (src/normalization.py:14-19)
 #include <algorithm>
 
 #include "common.hpp"
+#include "pack_layout.hpp"
 
 using namespace drpo;
-
-static constexpr int SUMSQ_BLOCK_ELEMS = 2048;
-
-__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, int64_t n, float* partial) {
-  __shared__ float red[256];
-  const int64_t base = (int64_t)blockIdx.x * SUMSQ_BLOCK_ELEMS;
-  float s = 0.f;
-  for (int64_t i = base + threadIdx.x; i < min(n, base + (int64_t)SUMSQ_BLOCK_ELEMS); i += 256) {
-    const float v = g[i];
-    s = fmaf(v, v, s);
-  }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-
-DRPO_API int drpo_grad_sumsq_blocks(int64_t n) { return (int)((n + SUMSQ_BLOCK_ELEMS - 1) / SUMSQ_BLOCK_ELEMS); }
-
-DRPO_API int drpo_grad_sumsq(const float* g, int64_t n, float* partial, drpo_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DRPO_REQUIRE(n >= 0, "drpo_grad_sumsq: n < 0");
-  if (n == 0) return DRPO_OK;
-  sumsq_kernel<<<drpo_grad_sumsq_blocks(n), 256, 0, stream>>>(g, n, partial);
-  DRPO_LAUNCH_CHECK("grad_sumsq");
-  return DRPO_OK;
-}
-
-struct AdamArgs {
-  float* p;
-  const float* g;
-  float *m, *v;
-  int64_t n;
-  float lr_over_bc1;      // lr / (1 - beta1^t)
-  float bc2_sqrt;         // sqrt(1 - beta2^t)
-  float beta1, beta2, one_minus_beta1, one_minus_beta2, eps, wd;
-  const float* partial;   // clip: partial sums of squares (nullptr = no clipping)
-  int n_partial;
-  float max_norm;
-  const float* lr_scale;  // optional device scalar multiplying the step (nullptr = 1)
-};
-
-__global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
-  __shared__ float s_coef;
-  if (a.partial) {
-    if (threadIdx.x < 64) {
-      float s = 0.f;
-      for (int i = threadIdx.x; i < a.n_partial; i += 64) s += a.partial[i];
-      for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-      if (threadIdx.x == 0) {
-        const float norm = sqrtf(s);
-        const float c = a.max_norm / (norm + 1e-6f);
-        s_coef = c < 1.f ? c : 1.f;
-      }
-    }
-    __syncthreads();
-  }
-  const float coef = a.partial ? s_coef : 1.f;
-  const float step = a.lr_over_bc1 * (a.lr_scale ? *a.lr_scale : 1.f);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float p = a.p[i];
-    float g = a.g[i] * coef;
-    if (a.wd != 0.f) g = fmaf(p, a.wd, g);
-    const float m = torch_lerp(a.m[i], g, a.one_minus_beta1);
-    const float v = fmaf(a.v[i], a.beta2, a.one_minus_beta2 * g * g);
-    a.m[i] = m;
-    a.v[i] = v;
-    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    a.p[i] = p - step * (m / denom);
-  }
-}
-
-DRPO_API int drpo_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr_over_bc1, float bc2_sqrt,
-                       float beta1, float beta2, float eps, float weight_decay, const float* clip_partial,
-                       int n_partial, float max_norm, const float* lr_scale, drpo_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DRPO_REQUIRE(n >= 0 && p && g && m && v, "drpo_adam: bad arguments");
-  if (n == 0) return DRPO_OK;
-  AdamArgs a{p, g, m, v, n, lr_over_bc1, bc2_sqrt, beta1, beta2, 1.f - beta1, 1.f - beta2, eps, weight_decay,
-             clip_partial, n_partial, max_norm, lr_scale};
-  int blocks = (int)((n + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  adam_kernel<<<blocks, 256, 0, stream>>>(a);
-  DRPO_LAUNCH_CHECK("adam");
-  return DRPO_OK;
-}
-
-__global__ void ema_kernel(float* t, const float* p, int64_t n, float rate, float keep) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    t[i] = rate * p[i] + keep * t[i];
-}
-
-DRPO_API int drpo_ema(float* target, const float* source, int64_t n, float rate, drpo_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DRPO_REQUIRE(rate >= 0.f && rate <= 1.f, "drpo_ema: rate must be in [0,1]");
-  if (n == 0) return DRPO_OK;
-  int blocks = (int)((n + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  // (1 - rate) is formed in double like the Python reference, then rounded once
-  ema_kernel<<<blocks, 256, 0, stream>>>(target, source, n, rate, (float)(1.0 - (double)rate));
-  DRPO_LAUNCH_CHECK("ema");
-  return DRPO_OK;
-}
 
 // ---------------------------------------------------------------------------
 // Normalizer.fit: column mean and unbiased std over X [N][S] (double accumulation)
@@ -267,20 +163,16 @@ __device__ __forceinline__ void pack_write4(const drpo_pack_map_t* mp, int64_t i
   int z = rel / msz;
   const int w = rel - z * msz;
   int o = w / din, k = w - o * din;
-  const int ncb = (dout + 15) >> 4, nks = (din + 15) >> 4;
+  const int ncb = pack_frags(dout), nks = pack_frags(din);
   float* P = mp->P;
   float* Pt = has_t ? mp->Pt : nullptr;
   float* PT = mp->PT;
   for (int e = 0; e < n; ++e) {
-    const int64_t base = mp->poff[l] + (int64_t)z * ncb * nks * 256;
-    // forward mirror: fragment (o>>4, k>>4), lane ((k>>2)&3)*16 + (o&15), component k&3
-    const int64_t pi = base + ((int64_t)((o >> 4) * nks + (k >> 4)) << 8) + ((((k >> 2) & 3) * 16 + (o & 15)) << 2) + (k & 3);
+    const int64_t base = pack_member_base(mp->poff[l], z, ncb, nks);
+    const int64_t pi = base + pack_fwd_index(o, k, nks);
     if (P) P[pi] = pv[e];
     if (Pt) Pt[pi] = tv[e];
-    if (PT) {   // transposed mirror: fragment (k>>4, o>>4), lane ((o>>2)&3)*16 + (k&15), component o&3
-      const int64_t ti = base + ((int64_t)((k >> 4) * ncb + (o >> 4)) << 8) + ((((o >> 2) & 3) * 16 + (k & 15)) << 2) + (o & 3);
-      PT[ti] = pv[e];
-    }
+    if (PT) PT[base + pack_tr_index(o, k, ncb)] = pv[e];
     if (++k == din) {
       k = 0;
       if (++o == dout) {
@@ -289,12 +181,6 @@ __device__ __forceinline__ void pack_write4(const drpo_pack_map_t* mp, int64_t i
       }
     }
   }
-}
-
-// per-element update shared by both task kinds: g (already scaled) -> Adam on p, m, v
-__device__ __forceinline__ void adam_elem(const drpo_optim_seg_t& S, float coef, float g, float& p, float& m,
-                                          float& v) {
-  adam_step(S, coef, g, p, m, v);
 }
 
 // EMA of one target element (one explicit fma: both task kinds round alike)
@@ -333,25 +219,12 @@ __device__ __forceinline__ void opt_matrix_block(const drpo_optim_seg_t& S, cons
   float p[4] = {0.f, 0.f, 0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f}, m[4] = {0.f, 0.f, 0.f, 0.f};
   float v[4] = {0.f, 0.f, 0.f, 0.f}, t[4] = {0.f, 0.f, 0.f, 0.f};
   const bool has_t = S.ema_target != nullptr;
+  const int nc = VEC ? 4 : min(4, din - k0);   // columns of the row segment inside the matrix
   auto ld = [&](const float* src, float (&dst)[4]) {
-    if (!row) return;
-    if constexpr (VEC) {
-      const f32x4 x = *reinterpret_cast<const f32x4*>(src + i);
-      dst[0] = x[0]; dst[1] = x[1]; dst[2] = x[2]; dst[3] = x[3];
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) dst[c] = k0 + c < din ? src[i + c] : 0.f;
-    }
+    if (row) load_row4(src + i, VEC, nc, dst);
   };
   auto st = [&](float* dst, const float (&src)[4]) {
-    if (!row) return;
-    if constexpr (VEC) {
-      *reinterpret_cast<f32x4*>(dst + i) = f32x4{src[0], src[1], src[2], src[3]};
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (k0 + c < din) dst[i + c] = src[c];
-    }
+    if (row) store_row4(dst + i, VEC, nc, src);
   };
   ld(S.p, p);
   if (S.adam) {
@@ -362,7 +235,7 @@ __device__ __forceinline__ void opt_matrix_block(const drpo_optim_seg_t& S, cons
   if (has_t) ld(S.ema_target, t);
   if (S.adam) {
 #pragma unroll
-    for (int c = 0; c < 4; ++c) adam_elem(S, coef, g[c] * gscale, p[c], m[c], v[c]);
+    for (int c = 0; c < 4; ++c) adam_step(S, coef, g[c] * gscale, p[c], m[c], v[c]);
     st(S.m, m);
     st(S.v, v);
     st(S.p, p);
@@ -378,15 +251,14 @@ __device__ __forceinline__ void opt_matrix_block(const drpo_optim_seg_t& S, cons
   }
   // mirrors (device map, scalar loads). Masked elements are 0, the mirrors' padding value.
   const drpo_pack_map_t* md = S.map;
-  const int ncb = (dout + 15) >> 4, nks = (din + 15) >> 4;
-  const int64_t mb = md->poff[T.layer] + (int64_t)z * ncb * nks * 256;
+  const int ncb = pack_frags(dout), nks = pack_frags(din);
+  const int64_t mb = pack_member_base(md->poff[T.layer], z, ncb, nks);
   float* P = md->P;
   float* PT = md->PT;
   float* Pt = has_t ? md->Pt : nullptr;
-  // forward mirror: row o's columns k0..k0+3 are the 4 components of fragment
-  // (o>>4, k0>>4), lane ((k0>>2)&3)*16 + (o&15)
+  // forward mirror: row o's columns k0..k0+3 are the 4 components of one fragment lane
   if (row) {
-    const int64_t pi = mb + ((int64_t)((o >> 4) * nks + (k0 >> 4)) << 8) + ((((k0 >> 2) & 3) * 16 + (o & 15)) << 2);
+    const int64_t pi = mb + pack_fwd_index(o, k0, nks);
     if (P) *reinterpret_cast<f32x4*>(P + pi) = f32x4{p[0], p[1], p[2], p[3]};
     if (Pt) *reinterpret_cast<f32x4*>(Pt + pi) = f32x4{t[0], t[1], t[2], t[3]};
   }
@@ -403,13 +275,10 @@ __device__ __forceinline__ void opt_matrix_block(const drpo_optim_seg_t& S, cons
       for (int c = 0; c < 4; ++c)   // q[j] = got (masks: see pick4)
         q[c] = __uint_as_float(__float_as_uint(q[c]) | (gb & (0u - (unsigned)(j == (unsigned)c))));
     }
-    // transposed mirror: column k's rows o0..o0+3 are the 4 components of fragment
-    // (k>>4, o0>>4), lane ((o0>>2)&3)*16 + (k&15)
+    // transposed mirror: column k's rows o0..o0+3 are the 4 components of one fragment lane
     const int k = k0 + rr;
-    if (live && k < din) {
-      const int64_t ti = mb + ((int64_t)((k >> 4) * ncb + (o0 >> 4)) << 8) + ((((o0 >> 2) & 3) * 16 + (k & 15)) << 2);
-      *reinterpret_cast<f32x4*>(PT + ti) = f32x4{q[0], q[1], q[2], q[3]};
-    }
+    if (live && k < din)
+      *reinterpret_cast<f32x4*>(PT + mb + pack_tr_index(o0, k, ncb)) = f32x4{q[0], q[1], q[2], q[3]};
   }
 }
 
@@ -420,11 +289,7 @@ __global__ __launch_bounds__(256) void optim_step_kernel(OptimArgs a) {
   // dependent global loads
   __shared__ __attribute__((aligned(16))) int s_map[(sizeof(drpo_pack_map_t) + 3) / 4];
   const int64_t bid = blockIdx.x;
-  // the task: the number of prefixes <= bid. All prefixes are read at once (independent
-  // scalar loads, one kernarg round trip) instead of a chain of dependent ones.
-  int lo = -1;
-#pragma unroll
-  for (int i = 0; i < OPT_MAXTASK; ++i) lo += bid >= a.first[i] ? 1 : 0;
+  const int lo = block_item<OPT_MAXTASK>(a, bid);   // the task
   const OptTask& T = a.task[lo];
   const drpo_optim_seg_t& S = a.seg[T.seg];
   const int64_t lb = bid - a.first[lo];
@@ -440,21 +305,8 @@ __global__ __launch_bounds__(256) void optim_step_kernel(OptimArgs a) {
   const bool vec = n == 4 && (i0 & 3) == 0;
   float p[4] = {0.f, 0.f, 0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f}, m[4] = {0.f, 0.f, 0.f, 0.f};
   float v[4] = {0.f, 0.f, 0.f, 0.f}, t[4] = {0.f, 0.f, 0.f, 0.f};
-  auto ld4 = [&](const float* src, float (&dst)[4]) {
-    if (vec) {
-      const f32x4 x = *reinterpret_cast<const f32x4*>(src + i0);
-      dst[0] = x[0]; dst[1] = x[1]; dst[2] = x[2]; dst[3] = x[3];
-    } else {
-      for (int e = 0; e < n; ++e) dst[e] = src[i0 + e];
-    }
-  };
-  auto st4 = [&](float* dst, const float (&src)[4]) {
-    if (vec) {
-      *reinterpret_cast<f32x4*>(dst + i0) = f32x4{src[0], src[1], src[2], src[3]};
-    } else {
-      for (int e = 0; e < n; ++e) dst[i0 + e] = src[e];
-    }
-  };
+  auto ld4 = [&](const float* src, float (&dst)[4]) { load_row4(src + i0, vec, n, dst); };
+  auto st4 = [&](float* dst, const float (&src)[4]) { store_row4(dst + i0, vec, n, src); };
   if (live) {
     ld4(S.p, p);
     if (S.adam) {
@@ -475,7 +327,7 @@ __global__ __launch_bounds__(256) void optim_step_kernel(OptimArgs a) {
   if (S.partial && threadIdx.x < 64) {
     float s = 0.f;
     for (int i = threadIdx.x; i < S.n_partial; i += 64) s += S.partial[i];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    s = wave_sum(s);
     if (threadIdx.x == 0) {
       const float c = S.max_norm / (sqrtf(s) * gscale + 1e-6f);
       s_coef = c < 1.f ? c : 1.f;
@@ -487,7 +339,7 @@ __global__ __launch_bounds__(256) void optim_step_kernel(OptimArgs a) {
     const int ns = S.grad_sum_n > 1 ? S.grad_sum_n : 1;
     float s = 0.f;
     for (int i = threadIdx.x; i < ns; i += 64) s += S.grad_from_sum[i];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    s = wave_sum(s);
     if (threadIdx.x == 0) s_gsum = s;
   }
   if (stage_map || S.partial || S.grad_from_sum) __syncthreads();
@@ -515,7 +367,7 @@ __global__ __launch_bounds__(256) void optim_step_kernel(OptimArgs a) {
   }
   if (S.adam) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) adam_elem(S, coef, g[e], p[e], m[e], v[e]);
+    for (int e = 0; e < 4; ++e) adam_step(S, coef, g[e], p[e], m[e], v[e]);
     st4(S.m, m);
     st4(S.v, v);
     st4(S.p, p);
@@ -602,9 +454,11 @@ DRPO_API int drpo_optim_step(const drpo_optim_seg_t* segs, int n, drpo_stream_t 
   return DRPO_OK;
 }
 
-// partial sums of squares for several clip segments in one launch:
-// segment k writes drpo_grad_sumsq_blocks(end-start) partials at out[k]
+// Partial sums of squares (first pass of clip_grad_norm_) for up to 8 clip segments in one
+// launch: a workgroup sums SUMSQ_BLOCK_ELEMS elements (256 strided lanes, then a fixed
+// tree); segment k writes drpo_grad_sumsq_blocks(n[k]) partials at out[k]
 namespace {
+constexpr int SUMSQ_BLOCK_ELEMS = 2048;
 constexpr int SQ_MAXSEG = 8;
 }
 struct SumsqArgs {
@@ -628,14 +482,11 @@ __global__ __launch_bounds__(256) void sumsq_multi_kernel(SumsqArgs a) {
     const float v = g[i];
     s = fmaf(v, v, s);
   }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) a.out[q][lb] = red[0];
+  s = block_tree_sum(s, red);
+  if (threadIdx.x == 0) a.out[q][lb] = s;
 }
+
+DRPO_API int drpo_grad_sumsq_blocks(int64_t n) { return (int)((n + SUMSQ_BLOCK_ELEMS - 1) / SUMSQ_BLOCK_ELEMS); }
 
 DRPO_API int drpo_grad_sumsq_multi(const float* const* g, const int64_t* n, float* const* out, int cnt,
                                    drpo_stream_t stream_) {
@@ -644,6 +495,7 @@ DRPO_API int drpo_grad_sumsq_multi(const float* const* g, const int64_t* n, floa
   SumsqArgs a{};
   int64_t tot = 0;
   for (int k = 0; k < cnt; ++k) {
+    DRPO_REQUIRE(n[k] >= 0, "drpo_grad_sumsq_multi: segment %d: n < 0", k);
     a.g[k] = g[k];
     a.n[k] = n[k];
     a.out[k] = out[k];
@@ -656,4 +508,8 @@ DRPO_API int drpo_grad_sumsq_multi(const float* const* g, const int64_t* n, floa
   sumsq_multi_kernel<<<(unsigned)tot, 256, 0, stream>>>(a);
   DRPO_LAUNCH_CHECK("grad_sumsq_multi");
   return DRPO_OK;
+}
+
+DRPO_API int drpo_grad_sumsq(const float* g, int64_t n, float* partial, drpo_stream_t stream) {
+  return drpo_grad_sumsq_multi(&g, &n, &partial, 1, stream);
 }

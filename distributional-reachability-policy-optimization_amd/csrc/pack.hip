@@ -1,14 +1,9 @@
-// Packed weight mirrors for the MFMA tile (see tile_dense in common.hpp).
-//
-// drpo_pack_weights rewrites PyTorch-layout weights W [nbatch][dout][din]
-// (nn.Linear / BatchedLinear, src/torch_util.py:190-211, src/dynamics.py:26-52)
-// into the fragment-linear layouts the kernels stream:
-//   P  (forward,  y = x W^T):  P [(cb*NKS + s)*256 + 4*l + i] = W[16cb + (l&15)][16s + 4(l>>4) + i]
-//   PT (backward, dx = dz W):  PT[(cb*NKS'+ s)*256 + 4*l + i] = W[16s + 4(l>>4) + i][16cb + (l&15)]
-// with zero padding outside [dout) x [din). One launch packs every layer of a
-// parameter group (all ensemble members); it runs after each optimizer / EMA
-// step of the group (HBM-bound: reads + writes ~2x the group bytes).
+// Packed weight mirrors for the MFMA tile (see tile_dense in common.hpp; the layout is
+// stated in pack_layout.hpp). One launch packs every layer of a parameter group (all
+// ensemble members); it runs after each optimizer / EMA step of the group that did not
+// refresh the mirrors itself (HBM-bound: reads + writes ~2x the group bytes).
 #include "common.hpp"
+#include "pack_layout.hpp"
 
 using namespace drpo;
 
@@ -28,7 +23,9 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
   int q = 0;
   while (q + 1 < a.n && t >= a.first[q + 1]) ++q;
   const drpo_pack_item_t& I = a.it[q];
-  const int ncb = (I.dout + 15) >> 4, nks = (I.din + 15) >> 4;
+  // the inverse of pack_fwd_index / pack_tr_index (pack_layout.hpp): one thread per fragment
+  // lane, which gathers its 4 components
+  const int ncb = pack_frags(I.dout), nks = pack_frags(I.din);
   const int64_t per = (int64_t)ncb * nks * 64;
   int64_t loc = t - a.first[q];
   const int z = (int)(loc / per);
@@ -61,7 +58,7 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
 }
 
 DRPO_API int64_t drpo_packed_size(int din, int dout) {
-  return (int64_t)((dout + 15) >> 4) * ((din + 15) >> 4) * 256;
+  return pack_matrix_floats(din, dout);
 }
 
 DRPO_API int drpo_pack_weights(const drpo_pack_item_t* items, int n, drpo_stream_t stream_) {

@@ -48,6 +48,7 @@
 // workgroup (the guide's price list) -- measured and rejected (profiles/r05/wgrad_setup).
 #include "common.hpp"
 #include "ens_nll.hpp"
+#include "pack_layout.hpp"
 
 using namespace drpo;
 
@@ -129,13 +130,8 @@ __device__ __forceinline__ void sums_block(WgradArgsK& a, float* red) {
     const auto& S = a.sums[q];
     float v = 0.f;
     for (int j = threadIdx.x; j < S.n; j += WG_NT) v += S.part[j];
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = WG_NT / 2; w > 0; w >>= 1) {
-      if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) *S.out = red[0];
+    v = block_tree_sum(v, red);
+    if (threadIdx.x == 0) *S.out = v;
     __syncthreads();
   }
 }
@@ -207,8 +203,9 @@ __device__ __forceinline__ int slab_index(int w, int ol, int il) {
   return (w * NA + m * NB + n) * WG_SLD + rr * 64 + 16 * G + L;
 }
 
+// the tile's sum of squares: wave shuffle trees, then the 4 wave sums in order (thread 0)
 __device__ __forceinline__ float wg_block_sum(float v, float* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  v = wave_sum(v);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   __syncthreads();
   if (lane == 0) red[w] = v;
@@ -219,15 +216,24 @@ __device__ __forceinline__ float wg_block_sum(float v, float* red) {
   return s;   // valid in thread 0
 }
 
-template <int TO, int TI, bool VA, bool VB, bool Z2>
-__device__ __forceinline__ void wgrad_unit(WgradArgsK& a, int q, int64_t u, float* lds) {
-  constexpr int MA = TO / 16, MB = TI / 16, NA = MA * MB;
-  constexpr int WA = TO == 64 ? 4 : 1, WB = TI == 64 ? 4 : 1;
-  constexpr int E = TO * TI / WG_NT;          // tile elements per thread (16, 4 or 1)
+// ---- a unit: one (member, row chunk, output tile) of an item, owned by one workgroup ----
+struct WgUnit {
+  int zb, ch;              // member, row chunk
+  int o0, i0;              // the tile's first output / input
+  int dout, din;
+  int64_t tile_local;      // the tile's index within the item (arrival counter, sq partial)
+  int64_t r0, r1;          // the chunk's rows
+  bool do_bias;            // the i-tile 0 units also sum the bias gradient ...
+  bool bias_mine;          // ... and thread t < TO finishes output o0 + t of it
+  float *gW, *gb;          // the member's gradient
+  int64_t eW, eb;          // fused Adam: their flat element offsets (p / m / v are indexed like g)
+};
+
+template <int TO, int TI>
+__device__ __forceinline__ WgUnit unit_decode(WgradArgsK& a, int q, int64_t u) {
   const auto& I = a.it[q];
   const auto& P = a.pl[q];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int g = lane >> 4, l15 = lane & 15;
+  WgUnit U;
   // 32-bit decode (an item has < 2^31 units): a 64-bit division expands to a long
   // stretch of scalar code, fetched cold by every workgroup at every dispatch
   const unsigned uu = (unsigned)u;
@@ -235,33 +241,57 @@ __device__ __forceinline__ void wgrad_unit(WgradArgsK& a, int q, int64_t u, floa
   unsigned rest = uu / (unsigned)P.nti;
   const int it_o = (int)(rest % (unsigned)P.nto);
   rest /= (unsigned)P.nto;
-  const int ch = (int)(rest % (unsigned)P.nch);
-  const int zb = (int)(rest / (unsigned)P.nch);
-  const int64_t tile_local = ((int64_t)zb * P.nto + it_o) * P.nti + it_i;
-  const int dout = I.dout, din = I.din;
-  const float* __restrict__ dz = I.dz + (size_t)zb * I.zstride;
-  const float* __restrict__ dz2 = Z2 ? I.dz2 + (size_t)zb * I.zstride : nullptr;
-  const float* __restrict__ y = I.y + (size_t)zb * I.ystride;
-  const int o0 = it_o * TO, i0 = it_i * TI;
-  const int64_t r0 = (int64_t)ch * P.chunk;
-  const int64_t r1 = min(I.rows, r0 + P.chunk);
-  const bool do_bias = it_i == 0;
+  U.ch = (int)(rest % (unsigned)P.nch);
+  U.zb = (int)(rest / (unsigned)P.nch);
+  U.tile_local = ((int64_t)U.zb * P.nto + it_o) * P.nti + it_i;
+  U.dout = I.dout;
+  U.din = I.din;
+  U.o0 = it_o * TO;
+  U.i0 = it_i * TI;
+  U.r0 = (int64_t)U.ch * P.chunk;
+  U.r1 = min(I.rows, U.r0 + P.chunk);
+  U.do_bias = it_i == 0;
+  U.bias_mine = U.do_bias && (int)threadIdx.x < TO && U.o0 + (int)threadIdx.x < U.dout;
+  U.gW = I.gW + (size_t)U.zb * I.gwstride;
+  U.gb = I.gb + (size_t)U.zb * I.gbstride;
+  U.eW = a.has_adam ? U.gW - a.adam.g : 0;
+  U.eb = a.has_adam ? U.gb - a.adam.g : 0;
+  return U;
+}
+
+// The main loop: this wave's share of the chunk's rows into acc (the partial tile, MFMA
+// accumulator layout) and bsum (the bias partial of this lane's 4 outputs). The only piece
+// that depends on how dZ and Y are loaded (VA / VB: 16-byte loads; Z2: a second dZ term).
+template <int TO, int TI, bool VA, bool VB, bool Z2>
+__device__ __forceinline__ void wgrad_accumulate(WgradArgsK& a, int q, const WgUnit& U,
+                                                 f32x4 (&acc)[TO / 16][TI / 16], f32x4& bsum) {
+  constexpr int MA = TO / 16, MB = TI / 16;
+  constexpr int WA = TO == 64 ? 4 : 1, WB = TI == 64 ? 4 : 1;
+  const auto& I = a.it[q];
+  const auto& P = a.pl[q];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, l15 = lane & 15;
+  const int dout = U.dout, din = U.din;
+  const float* __restrict__ dz = I.dz + (size_t)U.zb * I.zstride;
+  const float* __restrict__ dz2 = Z2 ? I.dz2 + (size_t)U.zb * I.zstride : nullptr;
+  const float* __restrict__ y = I.y + (size_t)U.zb * I.ystride;
+  const int64_t r1 = U.r1;
+  const bool do_bias = U.do_bias;
 
   // this lane's columns, clamped to valid addresses (masked to zero when out of range)
-  const int ca_raw = o0 + (WA == 4 ? 4 * l15 : l15);
-  const int cb_raw = i0 + (WB == 4 ? 4 * l15 : l15);
+  const int ca_raw = U.o0 + (WA == 4 ? 4 * l15 : l15);
+  const int cb_raw = U.i0 + (WB == 4 ? 4 * l15 : l15);
   const int ca = ca_raw < dout ? ca_raw : 0, cb = cb_raw < din ? cb_raw : 0;
 
-  f32x4 acc[MA][MB];
 #pragma unroll
   for (int m = 0; m < MA; ++m)
 #pragma unroll
     for (int n = 0; n < MB; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-  f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
+  bsum = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // wave k-group j covers rows r0 + 16 j + 4 wave + (0..3); lane group g takes row 4.. + g
   const int nj = P.chunk / (4 * WG_NW);      // k-groups per wave
-  const int64_t rlane = r0 + 4 * wave + g;
+  const int64_t rlane = U.r0 + 4 * wave + g;
   auto ld = [&](int j, f32x4& fa, f32x4& fb, f32x4& fa2) {
     const int64_t r = rlane + 16 * (int64_t)j;
     const int64_t rc = r < r1 ? r : r1 - 1;
@@ -301,88 +331,92 @@ __device__ __forceinline__ void wgrad_unit(WgradArgsK& a, int q, int64_t u, floa
     if (s0 == WG_D) STAMPG(5);
 #endif
   }
-
   STAMPG(1);
-  // Thread t owns tile elements t + 256 e: il = t % TI, ol = t / TI + (256 / TI) e; with
-  // P.vf (64x64 tiles) it owns 4 runs of 4 consecutive inputs instead: run f = t + 256 j
-  // is row ol = f / 16, inputs 4 (f % 16) .. + 3 -- the gradient / Adam reads and writes
-  // then go as float4s (a quarter of the memory instructions; the forward mirror's 4
-  // components are one float4 too). A slab (nch > 1) stores element e at t + 256 e in
-  // either mapping: the writer and the last arriver of a tile use the same one.
-  const bool vf = TO == 64 && TI == 64 && P.vf;
-  auto elem = [&](int e, int& ol, int& il) {
-    if (vf) {
-      const int f = tid + WG_NT * (e >> 2);
-      ol = f >> 4;
-      il = ((f & 15) << 2) + (e & 3);
-    } else {
-      const int idx = tid + WG_NT * e;
-      ol = idx / TI;
-      il = idx % TI;
-    }
-  };
-  constexpr int SL = TO * TI + TO;            // slab floats per unit (tile + bias)
-  float* gW = I.gW + (size_t)zb * I.gwstride;
-  float* gb = I.gb + (size_t)zb * I.gbstride;
-  float* red = lds + WG_NW * NA * WG_SLD + WG_NW * TO;   // 4 floats
-  // the gradient's current values: loaded by the workgroup that finishes the tile,
-  // before (and in flight with) the slab loads; every load precedes the first store.
-  // A single-chunk tile (nch == 1) is finished by its only workgroup: its loads are
-  // issued here, ahead of the partial tiles' LDS reduction, which covers their latency
-  float gv[E];
-  const bool bias_mine = do_bias && tid < TO && o0 + tid < dout;
-  float gbv = 0.f;
-  // fused Adam (drpo_mlp_wgrad_adam): the parameters and moments of the tile, loaded with
-  // the gradient's current values
+}
+
+// ---- what follows the main loop is per tile shape, and per finish width W -------------
+// Thread t owns E = TO * TI / 256 tile elements as E / W runs of W consecutive inputs of one
+// output row: run j is row (t + 256 j) / (TI / W), inputs W * ((t + 256 j) % (TI / W)) .. + W - 1.
+// W = 4 (64x64 tiles whose gradient rows are 16-byte aligned, WgradPlan.vf): the gradient /
+// Adam reads and writes and the forward mirror's 4 components of a lane go as float4s, a
+// quarter of the memory instructions. W = 1: one element per run. Element e = W j + c of a
+// thread is stored at t + 256 e of a slab (nch > 1) in either mapping: the writer and the
+// last arriver of a tile use the same one.
+template <int TI, int W>
+__device__ __forceinline__ void run_at(int j, int& ol, int& il) {
+  const int f = threadIdx.x + WG_NT * j;
+  ol = f / (TI / W);
+  il = f % (TI / W) * W;
+}
+template <int W>
+__device__ __forceinline__ void run_load(const float* p, bool in, float* x) {
+  if constexpr (W == 4) {
+    float t[4] = {0.f, 0.f, 0.f, 0.f};
+    if (in) load_row4(p, true, 4, t);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) x[c] = t[c];
+  } else {
+    x[0] = in ? *p : 0.f;
+  }
+}
+template <int W>
+__device__ __forceinline__ void run_store(float* p, const float* x) {
+  if constexpr (W == 4) {
+    const float t[4] = {x[0], x[1], x[2], x[3]};
+    store_row4(p, true, 4, t);
+  } else {
+    *p = x[0];
+  }
+}
+
+// the current values of a thread's tile elements: the gradient's terms and, for the fused
+// Adam step (drpo_mlp_wgrad_adam), the parameters and moments; b*: the bias element
+template <int E>
+struct TileCur {
+  float g[E], p[E], m[E], v[E];
+  float bg, bp, bm, bv;
+};
+
+// Loaded by the workgroup that finishes the tile, before (and in flight with) the slab
+// loads; every load precedes the first store. For W = 4, din % 4 == 0: a run is wholly
+// inside or outside the matrix.
+template <int TO, int TI, int W>
+__device__ __forceinline__ void tile_load(WgradArgsK& a, const WgUnit& U, TileCur<TO * TI / WG_NT>& c) {
+  constexpr int E = TO * TI / WG_NT;
+  const int tid = threadIdx.x;
   const bool adam = a.has_adam;
-  const int64_t eW = adam ? gW - a.adam.g : 0, eb = adam ? gb - a.adam.g : 0;   // flat element offsets
-  float ap[E], am[E], av[E], bp = 0.f, bm = 0.f, bvv = 0.f;
-  auto ld4 = [&](const float* base, int64_t k, bool in, float* dst) {
-    const f32x4 v = in ? *reinterpret_cast<const f32x4*>(base + k) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int c = 0; c < 4; ++c) dst[c] = v[c];
-  };
-  auto load_grad = [&]() {
-    if (vf) {   // din % 4 == 0: a run of 4 is wholly inside or outside the matrix
-#pragma unroll
-      for (int j = 0; j < E / 4; ++j) {
-        int ol, il;
-        elem(4 * j, ol, il);
-        const int o = o0 + ol, i = i0 + il;
-        const bool in = o < dout && i < din;
-        const int64_t k = (int64_t)o * din + i;
-        ld4(gW, k, in, gv + 4 * j);
-        if (adam) {
-          ld4(a.adam.p + eW, k, in, ap + 4 * j);
-          ld4(a.adam.m + eW, k, in, am + 4 * j);
-          ld4(a.adam.v + eW, k, in, av + 4 * j);
-        }
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < E; ++e) {
-        int ol, il;
-        elem(e, ol, il);
-        const int o = o0 + ol, i = i0 + il;
-        const bool in = o < dout && i < din;
-        const int64_t k = (int64_t)o * din + i;
-        gv[e] = in ? gW[k] : 0.f;
-        if (adam) {
-          ap[e] = in ? a.adam.p[eW + k] : 0.f;
-          am[e] = in ? a.adam.m[eW + k] : 0.f;
-          av[e] = in ? a.adam.v[eW + k] : 0.f;
-        }
-      }
+  for (int j = 0; j < E / W; ++j) {
+    int ol, il;
+    run_at<TI, W>(j, ol, il);
+    const int o = U.o0 + ol, i = U.i0 + il;
+    const bool in = o < U.dout && i < U.din;
+    const int64_t k = (int64_t)o * U.din + i;
+    run_load<W>(U.gW + k, in, c.g + W * j);
+    if (adam) {
+      run_load<W>(a.adam.p + U.eW + k, in, c.p + W * j);
+      run_load<W>(a.adam.m + U.eW + k, in, c.m + W * j);
+      run_load<W>(a.adam.v + U.eW + k, in, c.v + W * j);
     }
-    gbv = bias_mine ? gb[o0 + tid] : 0.f;
-    if (adam && bias_mine) {
-      bp = a.adam.p[eb + o0 + tid];
-      bm = a.adam.m[eb + o0 + tid];
-      bvv = a.adam.v[eb + o0 + tid];
-    }
-  };
-  if (P.nch == 1) load_grad();
-  // the 4 waves' partial tiles -> LDS slabs (conflict-free: lanes write consecutive words)
+  }
+  c.bg = U.bias_mine ? U.gb[U.o0 + tid] : 0.f;
+  c.bp = c.bm = c.bv = 0.f;
+  if (adam && U.bias_mine) {
+    c.bp = a.adam.p[U.eb + U.o0 + tid];
+    c.bm = a.adam.m[U.eb + U.o0 + tid];
+    c.bv = a.adam.v[U.eb + U.o0 + tid];
+  }
+}
+
+// The 4 waves' partial tiles and bias partials summed through LDS: pv[e] / pb = this
+// thread's elements of the unit's partial
+template <int TO, int TI, int W>
+__device__ __forceinline__ void wave_combine(const f32x4 (&acc)[TO / 16][TI / 16], f32x4 bsum, const WgUnit& U,
+                                             float* lds, float (&pv)[TO * TI / WG_NT], float& pb) {
+  constexpr int MA = TO / 16, MB = TI / 16, NA = MA * MB, E = TO * TI / WG_NT;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lane >> 4, l15 = lane & 15;
+  // partial tiles -> LDS slabs (conflict-free: lanes write consecutive words)
   float* R = lds;
 #pragma unroll
   for (int m = 0; m < MA; ++m)
@@ -392,7 +426,7 @@ __device__ __forceinline__ void wgrad_unit(WgradArgsK& a, int q, int64_t u, floa
       for (int rr = 0; rr < 4; ++rr) R[(wave * NA + m * MB + n) * WG_SLD + rr * 64 + lane] = acc[m][n][rr];
   // bias partials: sum over the 4 row lanes g of each column, then over waves (LDS)
   float* Rb = lds + WG_NW * NA * WG_SLD;      // [WG_NW][TO]
-  if (do_bias) {
+  if (U.do_bias) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       float s = bsum[c];
@@ -401,7 +435,7 @@ __device__ __forceinline__ void wgrad_unit(WgradArgsK& a, int q, int64_t u, floa
       bsum[c] = s;
     }
     if (g == 0) {
-      if constexpr (WA == 4) {
+      if constexpr (TO == 64) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) Rb[wave * TO + 4 * l15 + c] = bsum[c];
       } else {
@@ -410,219 +444,241 @@ __device__ __forceinline__ void wgrad_unit(WgradArgsK& a, int q, int64_t u, floa
     }
   }
   __syncthreads();
-  float pv[E];
 #pragma unroll
-  for (int e = 0; e < E; ++e) {
+  for (int j = 0; j < E / W; ++j) {
     int ol, il;
-    elem(e, ol, il);
-    float s = 0.f;
+    run_at<TI, W>(j, ol, il);
 #pragma unroll
-    for (int w = 0; w < WG_NW; ++w) s += R[slab_index<TO, TI>(w, ol, il)];
-    pv[e] = s;
+    for (int c = 0; c < W; ++c) {
+      float s = 0.f;
+#pragma unroll
+      for (int w = 0; w < WG_NW; ++w) s += R[slab_index<TO, TI>(w, ol, il + c)];
+      pv[W * j + c] = s;
+    }
   }
-  float pb = 0.f;
-  if (do_bias && tid < TO) {
+  pb = 0.f;
+  if (U.do_bias && tid < TO) {
 #pragma unroll
     for (int w = 0; w < WG_NW; ++w) pb += Rb[w * TO + tid];
   }
-  STAMPG(2);
-  if (P.nch > 1) {
-    float* my = a.slab + P.slab_off + (tile_local * P.nch + ch) * SL;
+}
+
+// Cross-chunk hand-off, first half (nch > 1): the unit's partial to its slab, then the
+// tile's ticket. Returns whether this workgroup arrived last, i.e. finishes the tile.
+template <int TO, int TI>
+__device__ __forceinline__ bool slab_publish(WgradArgsK& a, int q, const WgUnit& U, const float (&pv)[TO * TI / WG_NT],
+                                             float pb, float* red) {
+  constexpr int E = TO * TI / WG_NT, SL = TO * TI + TO;   // slab floats per unit (tile + bias)
+  const auto& P = a.pl[q];
+  const int tid = threadIdx.x;
+  float* my = a.slab + P.slab_off + (U.tile_local * P.nch + U.ch) * SL;
 #pragma unroll
-    for (int e = 0; e < E; ++e) st_sc1(my + tid + WG_NT * e, pv[e]);
-    if (do_bias && tid < TO) st_sc1(my + TO * TI + tid, pb);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int& s_last = *reinterpret_cast<int*>(red + 4);
-    if (tid == 0) {
-      unsigned* c = a.ctr + P.first_tile + tile_local;
-      // relaxed: see the memory-model note at the top (gfx950 ordering, not C++ acq_rel)
-      const unsigned old = __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int last = old == (unsigned)(P.nch - 1);
-      if (last) __hip_atomic_store(c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = last;
+  for (int e = 0; e < E; ++e) st_sc1(my + tid + WG_NT * e, pv[e]);
+  if (U.do_bias && tid < TO) st_sc1(my + TO * TI + tid, pb);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  int& s_last = *reinterpret_cast<int*>(red + 4);
+  if (tid == 0) {
+    unsigned* c = a.ctr + P.first_tile + U.tile_local;
+    // relaxed: see the memory-model note at the top (gfx950 ordering, not C++ acq_rel)
+    const unsigned old = __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int last = old == (unsigned)(P.nch - 1);
+    if (last) __hip_atomic_store(c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = last;
+  }
+  __syncthreads();
+  STAMPG(3);
+  return s_last;
+}
+
+// Second half, the last arriver: the tile's partials in chunk order, CG chunks' loads in
+// flight at a time (one memory round trip per group of chunks, not per chunk)
+template <int TO, int TI>
+__device__ __forceinline__ void slab_sum(WgradArgsK& a, int q, const WgUnit& U, float (&pv)[TO * TI / WG_NT],
+                                         float& pb) {
+  constexpr int E = TO * TI / WG_NT, SL = TO * TI + TO;
+  const auto& P = a.pl[q];
+  const int tid = threadIdx.x;
+  const float* base = a.slab + P.slab_off + U.tile_local * P.nch * SL;
+  const bool bias_lane = U.do_bias && tid < TO;
+#pragma unroll
+  for (int e = 0; e < E; ++e) pv[e] = 0.f;
+  pb = 0.f;
+  constexpr int CG = E >= 16 ? 4 : 8;
+  for (int c0 = 0; c0 < P.nch; c0 += CG) {
+    float t[CG][E], tb[CG];
+#pragma unroll
+    for (int u = 0; u < CG; ++u) {
+      const int c = min(c0 + u, P.nch - 1);     // clamped: a duplicate load, not added
+#pragma unroll
+      for (int e = 0; e < E; ++e) t[u][e] = ld_sc1(base + c * SL + tid + WG_NT * e);
+      tb[u] = bias_lane ? ld_sc1(base + c * SL + TO * TI + tid) : 0.f;
     }
-    __syncthreads();
-    STAMPG(3);
-    if (!s_last) return;
-    load_grad();
-    // last arriver: the tile's partials in chunk order, CG chunks' loads in flight at a
-    // time (one memory round trip per group of chunks, not per chunk)
-    const float* base = a.slab + P.slab_off + tile_local * P.nch * SL;
-    const bool bias_lane = do_bias && tid < TO;
 #pragma unroll
-    for (int e = 0; e < E; ++e) pv[e] = 0.f;
-    pb = 0.f;
-    constexpr int CG = E >= 16 ? 4 : 8;
-    for (int c0 = 0; c0 < P.nch; c0 += CG) {
-      float t[CG][E], tb[CG];
+    for (int u = 0; u < CG; ++u) {
+      if (c0 + u < P.nch) {
 #pragma unroll
-      for (int u = 0; u < CG; ++u) {
-        const int c = min(c0 + u, P.nch - 1);     // clamped: a duplicate load, not added
-#pragma unroll
-        for (int e = 0; e < E; ++e) t[u][e] = ld_sc1(base + c * SL + tid + WG_NT * e);
-        tb[u] = bias_lane ? ld_sc1(base + c * SL + TO * TI + tid) : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < CG; ++u) {
-        if (c0 + u < P.nch) {
-#pragma unroll
-          for (int e = 0; e < E; ++e) pv[e] += t[u][e];
-          pb += tb[u];
-        }
+        for (int e = 0; e < E; ++e) pv[e] += t[u][e];
+        pb += tb[u];
       }
     }
   }
-  if (adam) {
-    // the finished gradient g = current terms + this launch's sum -> Adam (the
-    // drpo_optim_step arithmetic), the tile's forward / transposed mirrors refreshed; the
-    // gradient itself is never written (nonzero input terms are cleared)
-    const drpo_pack_map_t* md = P.pk_layer >= 0 ? (const drpo_pack_map_t*)a.adam.map : nullptr;
-    const int ncb = (dout + 15) >> 4, nks = (din + 15) >> 4;
-    const int64_t mb = md ? md->poff[P.pk_layer] + (int64_t)(P.pk_z0 + zb) * ncb * nks * 256 : 0;
-    float* PM = md ? md->P : nullptr;
-    float* PTM = md ? md->PT : nullptr;
-    if (vf) {
+}
+
+// Finish of drpo_mlp_wgrad_adam: the finished gradient g = current terms + this launch's
+// sum -> Adam (the drpo_optim_step arithmetic), the tile's forward / transposed mirrors
+// refreshed (pack_layout.hpp); the gradient itself is never written (nonzero input terms
+// are cleared)
+template <int TO, int TI, int W>
+__device__ __forceinline__ void finish_adam(WgradArgsK& a, int q, const WgUnit& U, TileCur<TO * TI / WG_NT>& c,
+                                            const float (&pv)[TO * TI / WG_NT], float pb, float* lds) {
+  constexpr int E = TO * TI / WG_NT;
+  const auto& P = a.pl[q];
+  const int tid = threadIdx.x;
+  const int dout = U.dout, din = U.din;
+  const drpo_pack_map_t* md = P.pk_layer >= 0 ? (const drpo_pack_map_t*)a.adam.map : nullptr;
+  const int ncb = pack_frags(dout), nks = pack_frags(din);
+  const int64_t mb = md ? pack_member_base(md->poff[P.pk_layer], P.pk_z0 + U.zb, ncb, nks) : 0;
+  float* PM = md ? md->P : nullptr;
+  float* PTM = md ? md->PT : nullptr;
+#pragma unroll
+  for (int j = 0; j < E / W; ++j) {
+    int ol, il;
+    run_at<TI, W>(j, ol, il);
+    const int o = U.o0 + ol, i = U.i0 + il;
+    if (o >= dout || i >= din) continue;
+    const int64_t k = (int64_t)o * din + i;
+    bool nz = false;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      const int e = W * j + w;
+      adam_step(a.adam, 1.f, c.g[e] + pv[e], c.p[e], c.m[e], c.v[e]);
+      nz = nz || c.g[e] != 0.f;
+    }
+    run_store<W>(a.adam.p + U.eW + k, c.p + W * j);
+    run_store<W>(a.adam.m + U.eW + k, c.m + W * j);
+    run_store<W>(a.adam.v + U.eW + k, c.v + W * j);
+    const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+    if (nz) run_store<W>(U.gW + k, zero);
+    if (PM) run_store<W>(PM + mb + pack_fwd_index(o, i, nks), c.p + W * j);   // W = 4: one lane's float4
+    if constexpr (W == 1)
+      if (PTM) PTM[mb + pack_tr_index(o, i, ncb)] = c.p[j];
+  }
+  if constexpr (W == 4) {
+    if (PTM) {
+      // transposed mirror: a float4 there is 4 consecutive outputs of one input, so the
+      // tile goes through LDS ([64][65] floats over the partial-tile slabs) and each
+      // thread stores 4 such float4s instead of 16 scattered floats
+      float* T = lds;
+      __syncthreads();   // every thread's reads of the partial-tile slabs are done
 #pragma unroll
       for (int j = 0; j < E / 4; ++j) {
         int ol, il;
-        elem(4 * j, ol, il);
-        const int o = o0 + ol, i = i0 + il;
+        run_at<TI, 4>(j, ol, il);
+        const bool in = U.o0 + ol < dout && U.i0 + il < din;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) T[ol * 65 + il + w] = in ? c.p[4 * j + w] : 0.f;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < E / 4; ++j) {
+        const int f = tid + WG_NT * j;
+        const int il = f >> 4, ol = (f & 15) << 2;   // input il, outputs ol .. ol + 3
+        const int o = U.o0 + ol, i = U.i0 + il;
         if (o >= dout || i >= din) continue;
-        const int64_t k = (int64_t)o * din + i;
-        f32x4 p4, m4, v4;
-        bool nz = false;
+        float v[4];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          float pe = ap[4 * j + c], me = am[4 * j + c], ve = av[4 * j + c];
-          adam_step(a.adam, 1.f, gv[4 * j + c] + pv[4 * j + c], pe, me, ve);
-          p4[c] = pe;
-          m4[c] = me;
-          v4[c] = ve;
-          nz = nz || gv[4 * j + c] != 0.f;
-        }
-        *reinterpret_cast<f32x4*>(a.adam.p + eW + k) = p4;
-        *reinterpret_cast<f32x4*>(a.adam.m + eW + k) = m4;
-        *reinterpret_cast<f32x4*>(a.adam.v + eW + k) = v4;
-        if (nz) *reinterpret_cast<f32x4*>(gW + k) = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (PM)   // i .. i+3 are the 4 components of one lane of fragment (o>>4, i>>4)
-          *reinterpret_cast<f32x4*>(PM + mb + ((int64_t)((o >> 4) * nks + (i >> 4)) << 8) +
-                                    ((((i >> 2) & 3) * 16 + (o & 15)) << 2)) = p4;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) ap[4 * j + c] = p4[c];   // the new parameters (the transposed refresh)
-      }
-      if (PTM) {
-        // transposed mirror: a float4 there is 4 consecutive outputs of one input, so the
-        // tile goes through LDS ([64][65] floats over the partial-tile slabs) and each
-        // thread stores 4 such float4s instead of 16 scattered floats
-        float* T = lds;
-        __syncthreads();   // every thread's reads of the partial-tile slabs are done
-#pragma unroll
-        for (int j = 0; j < E / 4; ++j) {
-          int ol, il;
-          elem(4 * j, ol, il);
-          const bool in = o0 + ol < dout && i0 + il < din;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) T[ol * 65 + il + c] = in ? ap[4 * j + c] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < E / 4; ++j) {
-          const int f = tid + WG_NT * j;
-          const int il = f >> 4, ol = (f & 15) << 2;   // input il, outputs ol .. ol + 3
-          const int o = o0 + ol, i = i0 + il;
-          if (o >= dout || i >= din) continue;
-          f32x4 v;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) v[c] = T[(ol + c) * 65 + il];   // zero past dout: the padding
-          *reinterpret_cast<f32x4*>(PTM + mb + ((int64_t)((i >> 4) * ncb + (o >> 4)) << 8) +
-                                    ((((o >> 2) & 3) * 16 + (i & 15)) << 2)) = v;
-        }
-      }
-    } else
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      int ol, il;
-      elem(e, ol, il);
-      const int o = o0 + ol, i = i0 + il;
-      if (o < dout && i < din) {
-        const int64_t k = (int64_t)o * din + i;
-        float pe = ap[e], me = am[e], ve = av[e];
-        adam_step(a.adam, 1.f, gv[e] + pv[e], pe, me, ve);
-        a.adam.p[eW + k] = pe;
-        a.adam.m[eW + k] = me;
-        a.adam.v[eW + k] = ve;
-        if (gv[e] != 0.f) gW[k] = 0.f;
-        if (PM)   // forward mirror: fragment (o>>4, i>>4), lane ((i>>2)&3)*16 + (o&15), component i&3
-          PM[mb + ((int64_t)((o >> 4) * nks + (i >> 4)) << 8) + ((((i >> 2) & 3) * 16 + (o & 15)) << 2) + (i & 3)] = pe;
-        if (PTM)  // transposed: fragment (i>>4, o>>4), lane ((o>>2)&3)*16 + (i&15), component o&3
-          PTM[mb + ((int64_t)((i >> 4) * ncb + (o >> 4)) << 8) + ((((o >> 2) & 3) * 16 + (i & 15)) << 2) + (o & 3)] = pe;
+        for (int w = 0; w < 4; ++w) v[w] = T[(ol + w) * 65 + il];   // zero past dout: the padding
+        run_store<4>(PTM + mb + pack_tr_index(o, i, ncb), v);
       }
     }
-    if (bias_mine) {
-      adam_step(a.adam, 1.f, gbv + pb, bp, bm, bvv);
-      a.adam.p[eb + o0 + tid] = bp;
-      a.adam.m[eb + o0 + tid] = bm;
-      a.adam.v[eb + o0 + tid] = bvv;
-      if (gbv != 0.f) gb[o0 + tid] = 0.f;
-    }
-    STAMPG(4);
-    return;
   }
-  // gradient += sum (the caller's gradient is zeroed or holds terms to accumulate)
+  if (U.bias_mine) {
+    adam_step(a.adam, 1.f, c.bg + pb, c.bp, c.bm, c.bv);
+    a.adam.p[U.eb + U.o0 + tid] = c.bp;
+    a.adam.m[U.eb + U.o0 + tid] = c.bm;
+    a.adam.v[U.eb + U.o0 + tid] = c.bv;
+    if (c.bg != 0.f) U.gb[U.o0 + tid] = 0.f;
+  }
+}
+
+// Plain finish: gradient += sum (the caller's gradient is zeroed or holds terms to
+// accumulate), and the tile's sum of squares for the clip norm
+template <int TO, int TI, int W>
+__device__ __forceinline__ void finish_grad(WgradArgsK& a, int q, const WgUnit& U, const TileCur<TO * TI / WG_NT>& c,
+                                            const float (&pv)[TO * TI / WG_NT], float pb, float* red) {
+  constexpr int E = TO * TI / WG_NT;
+  const auto& I = a.it[q];
+  const int tid = threadIdx.x;
   float sq = 0.f;
-  if (vf) {
 #pragma unroll
-    for (int j = 0; j < E / 4; ++j) {
-      int ol, il;
-      elem(4 * j, ol, il);
-      const int o = o0 + ol, i = i0 + il;
-      if (o >= dout || i >= din) continue;
-      f32x4 v4;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        v4[c] = gv[4 * j + c] + pv[4 * j + c];
-        sq = fmaf(v4[c], v4[c], sq);
-      }
-      *reinterpret_cast<f32x4*>(gW + (size_t)o * din + i) = v4;
-    }
-  } else
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
+  for (int j = 0; j < E / W; ++j) {
     int ol, il;
-    elem(e, ol, il);
-    const int o = o0 + ol, i = i0 + il;
-    if (o < dout && i < din) {
-      const float v = gv[e] + pv[e];
-      gW[(size_t)o * din + i] = v;
-      sq = fmaf(v, v, sq);
+    run_at<TI, W>(j, ol, il);
+    const int o = U.o0 + ol, i = U.i0 + il;
+    if (o >= U.dout || i >= U.din) continue;
+    float v[W];
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      v[w] = c.g[W * j + w] + pv[W * j + w];
+      sq = fmaf(v[w], v[w], sq);
     }
+    run_store<W>(U.gW + (size_t)o * U.din + i, v);
   }
-  if (bias_mine) {
-    const float v = gbv + pb;
-    gb[o0 + tid] = v;
+  if (U.bias_mine) {
+    const float v = c.bg + pb;
+    U.gb[U.o0 + tid] = v;
     sq = fmaf(v, v, sq);
   }
   if (I.sq) {
     const float s = wg_block_sum(sq, red);
-    if (tid == 0) I.sq[I.sq_off + tile_local] = s;
+    if (tid == 0) I.sq[I.sq_off + U.tile_local] = s;
   }
+}
+
+// From the waves' accumulators to the finished tile
+template <int TO, int TI, int W>
+__device__ __forceinline__ void wgrad_tile(WgradArgsK& a, int q, const WgUnit& U, const f32x4 (&acc)[TO / 16][TI / 16],
+                                           const f32x4& bsum, float* lds) {
+  constexpr int E = TO * TI / WG_NT;
+  const auto& P = a.pl[q];
+  float* red = lds + WG_NW * (TO / 16) * (TI / 16) * WG_SLD + WG_NW * TO;   // 4 floats + the last-arriver flag
+  TileCur<E> cur;
+  // A single-chunk tile (nch == 1) is finished by its only workgroup: its loads are
+  // issued here, ahead of the partial tiles' LDS reduction, which covers their latency
+  if (P.nch == 1) tile_load<TO, TI, W>(a, U, cur);
+  float pv[E], pb;
+  wave_combine<TO, TI, W>(acc, bsum, U, lds, pv, pb);
+  STAMPG(2);
+  if (P.nch > 1) {
+    if (!slab_publish<TO, TI>(a, q, U, pv, pb, red)) return;
+    tile_load<TO, TI, W>(a, U, cur);
+    slab_sum<TO, TI>(a, q, U, pv, pb);
+  }
+  if (a.has_adam) finish_adam<TO, TI, W>(a, q, U, cur, pv, pb, lds);
+  else finish_grad<TO, TI, W>(a, q, U, cur, pv, pb, red);
   STAMPG(4);
 }
 
-template <int TO, int TI, bool Z2>
-__device__ __forceinline__ void wgrad_unit_z(WgradArgsK& a, int q, int64_t u, float* lds) {
-  const auto& P = a.pl[q];
-  if (P.va && P.vb) wgrad_unit<TO, TI, true, true, Z2>(a, q, u, lds);
-  else if (P.va) wgrad_unit<TO, TI, true, false, Z2>(a, q, u, lds);
-  else if (P.vb) wgrad_unit<TO, TI, false, true, Z2>(a, q, u, lds);
-  else wgrad_unit<TO, TI, false, false, Z2>(a, q, u, lds);
-}
-
 template <int TO, int TI>
-__device__ __forceinline__ void wgrad_unit_v(WgradArgsK& a, int q, int64_t u, float* lds) {
-  if (a.pl[q].z2) wgrad_unit_z<TO, TI, true>(a, q, u, lds);
-  else wgrad_unit_z<TO, TI, false>(a, q, u, lds);
+__device__ __forceinline__ void wgrad_unit(WgradArgsK& a, int q, int64_t u, float* lds) {
+  const auto& P = a.pl[q];
+  const WgUnit U = unit_decode<TO, TI>(a, q, u);
+  f32x4 acc[TO / 16][TI / 16], bsum;
+  switch ((P.z2 ? 4 : 0) | (P.va ? 2 : 0) | (P.vb ? 1 : 0)) {   // <VA, VB, Z2>
+    case 0: wgrad_accumulate<TO, TI, false, false, false>(a, q, U, acc, bsum); break;
+    case 1: wgrad_accumulate<TO, TI, false, true, false>(a, q, U, acc, bsum); break;
+    case 2: wgrad_accumulate<TO, TI, true, false, false>(a, q, U, acc, bsum); break;
+    case 3: wgrad_accumulate<TO, TI, true, true, false>(a, q, U, acc, bsum); break;
+    case 4: wgrad_accumulate<TO, TI, false, false, true>(a, q, U, acc, bsum); break;
+    case 5: wgrad_accumulate<TO, TI, false, true, true>(a, q, U, acc, bsum); break;
+    case 6: wgrad_accumulate<TO, TI, true, false, true>(a, q, U, acc, bsum); break;
+    default: wgrad_accumulate<TO, TI, true, true, true>(a, q, U, acc, bsum); break;
+  }
+  if constexpr (TO == 64 && TI == 64) {
+    if (P.vf) return wgrad_tile<TO, TI, 4>(a, q, U, acc, bsum, lds);
+  }
+  wgrad_tile<TO, TI, 1>(a, q, U, acc, bsum, lds);
 }
 
 __global__ __launch_bounds__(WG_NT, 2) void mlp_wgrad_kernel(WgradArgs args) {
@@ -642,17 +698,13 @@ __global__ __launch_bounds__(WG_NT, 2) void mlp_wgrad_kernel(WgradArgs args) {
     else if (a.nsums) sums_block(a, wsm);
     return;
   }
-  // the item: the number of item starts <= bid, all read at once (independent scalar
-  // loads, one kernarg round trip; a dependent search costs one per item passed)
-  int q = 0;
-#pragma unroll
-  for (int i = 1; i < WG_MAXITEMS; ++i) q += bid >= a.first[i] ? 1 : 0;
+  const int q = block_item<WG_MAXITEMS>(a, bid);   // the item
   const auto& P = a.pl[q];
   const int64_t u = bid - P.first_unit;
-  if (P.to == 64 && P.ti == 64) wgrad_unit_v<64, 64>(a, q, u, wsm);
-  else if (P.to == 64) wgrad_unit_v<64, 16>(a, q, u, wsm);
-  else if (P.ti == 64) wgrad_unit_v<16, 64>(a, q, u, wsm);
-  else wgrad_unit_v<16, 16>(a, q, u, wsm);
+  if (P.to == 64 && P.ti == 64) wgrad_unit<64, 64>(a, q, u, wsm);
+  else if (P.to == 64) wgrad_unit<64, 16>(a, q, u, wsm);
+  else if (P.ti == 64) wgrad_unit<16, 64>(a, q, u, wsm);
+  else wgrad_unit<16, 16>(a, q, u, wsm);
 }
 
 static_assert(sizeof(WgradArgs) <= 4096, "weight-gradient kernarg");
@@ -764,7 +816,28 @@ int plan(const drpo_wgrad_item_t* items, int n, const drpo_ens_reduce_t* red, Pl
   return DRPO_OK;
 }
 
-size_t ws_bytes(const Plan& p) { return (size_t)((p.tiles * 4 + 255) / 256 * 256) + sizeof(float) * (size_t)p.slab; }
+// workspace: the arrival counters (rounded to 256 bytes), then the slabs
+size_t ctr_bytes(const Plan& p) { return (size_t)((p.tiles * 4 + 255) / 256 * 256); }
+size_t ws_bytes(const Plan& p) { return ctr_bytes(p) + sizeof(float) * (size_t)p.slab; }
+
+// Fused Adam: item k's matrix in the group's pack map (by its flat offset), for the mirrors.
+// The item is members [z0, z0 + nbatch) of one [nbatch][dout][din] matrix of the map (the
+// whole matrix, or a member shard's contiguous slice of it).
+int match_pack_layer(const drpo_pack_map_t& mh, const drpo_wgrad_item_t& I, const float* g, int k, WgradPlan& P) {
+  const int64_t off = I.gW - g;
+  for (int l = 0; l < mh.nlayers && l < 16; ++l) {
+    const int64_t per = (int64_t)mh.din[l] * mh.dout[l], rel = off - mh.off[l];
+    if (mh.din[l] != I.din || mh.dout[l] != I.dout || rel < 0 || rel % per != 0) continue;
+    const int64_t z0 = rel / per;
+    if (z0 + I.nbatch > mh.nbatch[l] || (I.nbatch > 1 && I.gwstride != per)) continue;
+    DRPO_REQUIRE(P.pk_layer < 0, "drpo_mlp_wgrad_adam: item %d matches layers %d and %d of the pack map", k,
+                 P.pk_layer, l);
+    P.pk_layer = l;
+    P.pk_z0 = (int)z0;
+  }
+  DRPO_REQUIRE(P.pk_layer >= 0, "drpo_mlp_wgrad_adam: item %d is not a matrix of the pack map", k);
+  return DRPO_OK;
+}
 
 }  // namespace
 
@@ -828,33 +901,18 @@ static int wgrad_launch(const drpo_wgrad_item_t* items, int n, const drpo_ens_re
   DRPO_REQUIRE(workspace_bytes >= need && (need == 0 || workspace),
                "drpo_mlp_wgrad: workspace %zu bytes < %zu (drpo_mlp_wgrad_workspace_size)", workspace_bytes, need);
   p.a.ctr = (unsigned*)workspace;
-  p.a.slab = (float*)((char*)workspace + (size_t)((p.tiles * 4 + 255) / 256 * 256));
+  p.a.slab = (float*)((char*)workspace + ctr_bytes(p));
   p.a.nsums = nsums;
   for (int q = 0; q < nsums; ++q) p.a.sums[q] = sums[q];
   p.a.has_adam = adam != nullptr;
   if (adam) {
     p.a.adam = *adam;
-    // each item's matrix in the group's pack map (by its flat offset), for the mirrors
     const drpo_pack_map_t* mh = (const drpo_pack_map_t*)adam->map_host;
     for (int k = 0; k < p.a.n; ++k) {
-      const drpo_wgrad_item_t& I = p.a.it[k];
-      p.a.pl[k].pk_layer = -1;
+      p.a.pl[k].pk_layer = -1;   // no map: no mirrors to refresh
       p.a.pl[k].pk_z0 = 0;
       if (!mh) continue;
-      const int64_t off = I.gW - adam->g;
-      // the item is members [z0, z0 + nbatch) of one [nbatch][dout][din] matrix of the map
-      // (the whole matrix, or a member shard's contiguous slice of it)
-      for (int l = 0; l < mh->nlayers && l < 16; ++l) {
-        const int64_t per = (int64_t)mh->din[l] * mh->dout[l], rel = off - mh->off[l];
-        if (mh->din[l] != I.din || mh->dout[l] != I.dout || rel < 0 || rel % per != 0) continue;
-        const int64_t z0 = rel / per;
-        if (z0 + I.nbatch > mh->nbatch[l] || (I.nbatch > 1 && I.gwstride != per)) continue;
-        DRPO_REQUIRE(p.a.pl[k].pk_layer < 0, "drpo_mlp_wgrad_adam: item %d matches layers %d and %d of the pack map", k,
-                     p.a.pl[k].pk_layer, l);
-        p.a.pl[k].pk_layer = l;
-        p.a.pl[k].pk_z0 = (int)z0;
-      }
-      DRPO_REQUIRE(p.a.pl[k].pk_layer >= 0, "drpo_mlp_wgrad_adam: item %d is not a matrix of the pack map", k);
+      if (const int e = match_pack_layer(*mh, p.a.it[k], adam->g, k, p.a.pl[k])) return e;
     }
     // the float4 finish also reads / writes p, m, v at the gradient's flat offsets
     const bool al = ((uintptr_t)adam->p & 15) == 0 && ((uintptr_t)adam->m & 15) == 0 &&

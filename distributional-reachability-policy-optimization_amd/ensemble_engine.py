@@ -44,7 +44,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .optim import fused_step
+from .optim import OPT_MAXSEG, fused_step
 from .rng import DeviceNoise
 from .mlp_desc import ACT_ID, Net, fill_bwd, fill_fwd, wgrad_workspace
 from ._abi import EnsReduce, EnsUpstream, WgradItem
@@ -610,7 +610,8 @@ class FitPlan:
                 self.bseg = (OptimSeg * 1)(m.optimizer.segment(lo, hi, (0.0, 1.0), zero_grad=True))
                 self.side, self.ev_bwd, self.ev_done = eng._side_stream()
                 self.side_s = ctypes.c_void_p(self.side.cuda_stream)
-        self.seg_arr = [(OptimSeg * len(segs[k:k + 8]))(*segs[k:k + 8]) for k in range(0, len(segs), 8)]
+        chunks = [segs[k:k + OPT_MAXSEG] for k in range(0, len(segs), OPT_MAXSEG)]
+        self.seg_arr = [(OptimSeg * len(c))(*c) for c in chunks]
         self.pending = False    # fused-shard: the previous step's bounds update is in flight
 
     def compute(self, i, k):

@@ -3,7 +3,7 @@
 ``Adam`` reproduces torch.optim.Adam (single-tensor path: coupled L2 weight decay,
 lerp first moment, bias corrections formed in double on the host) and
 ``clip_grad_norm_`` semantics for the reference's separate clip groups; the
-arithmetic runs in one HIP kernel per clip segment (csrc/optim.hip).
+arithmetic runs in the fused optimizer launch, drpo_optim_step (csrc/optim.hip).
 ``CosineAnnealingLR`` reproduces torch's recursive (chainable) schedule, which is
 host-side scalar logic in the reference too.
 """
@@ -51,22 +51,6 @@ class Adam:
         bc2 = 1 - b2 ** t
         return self.lr / bc1, bc2 ** 0.5
 
-    def apply(self, grad, start, end, scalars, clip=None, lr_scale=None):
-        """Adam on elements [start, end) of the flat data with ``grad`` (same indexing);
-        clip = (partial_sums_tensor, max_norm) or None."""
-        self._ensure_state()
-        d = self._data()
-        _lib.require_device(d, grad)
-        L = _lib.lib()
-        n = end - start
-        part, n_part, max_norm = (None, 0, 0.0) if clip is None else (clip[0], clip[0].numel(), clip[1])
-        _lib.check(L.drpo_adam(_lib.ptr(d[start:end]), _lib.ptr(grad[start:end]), _lib.ptr(self.m[start:end]),
-                               _lib.ptr(self.v[start:end]), n, scalars[0], scalars[1], self.betas[0],
-                               self.betas[1], self.eps, self.weight_decay, _lib.ptr(part), n_part,
-                               float(max_norm), _lib.ptr(lr_scale), _lib.stream()), 'adam')
-        if self.group is not None:
-            self.group.mark_dirty()
-
     def segment(self, start, end, scalars, clip=None, zero_grad=False, ema=None, pack_map=None, grad=None,
                 grad_from_sum=None, grad_from_sum_kind=0, grad_scale=1.0):
         """drpo_optim_seg_t for elements [start, end) of this optimizer's tensor:
@@ -93,9 +77,7 @@ class Adam:
         sg.zero_grad = int(zero_grad)
         if ema is not None:
             sg.ema_target, sg.ema_rate, sg.ema_keep = ema[0].data_ptr(), float(ema[1]), float(1.0 - float(ema[1]))
-        sg.map = 0 if pack_map is None else pack_map.data_ptr()
-        host = getattr(pack_map, 'host', None)
-        sg.map_host = 0 if host is None else ctypes.addressof(host)
+        _set_pack_map(sg, pack_map)
         if grad_from_sum is not None:
             sg.grad_from_sum, sg.grad_sum_rows = grad_from_sum[0].data_ptr(), int(grad_from_sum[1])
             sg.grad_from_sum_kind = int(grad_from_sum_kind)
@@ -105,10 +87,9 @@ class Adam:
 
     def step(self):
         """Plain step over the whole group (no clipping), for external training loops."""
-        sc = self.step_scalars()
-        d = self._data()
-        g = self.group.grad if self.group is not None else self.tensor.grad
-        self.apply(g, 0, d.numel(), sc)
+        fused_step([self.segment(0, self._data().numel(), self.step_scalars())])
+        if self.group is not None:
+            self.group.mark_dirty()
 
     def state_dict(self):
         return {'step': self.step_count, 'm': self.m, 'v': self.v, 'param_groups': self.param_groups}
@@ -146,6 +127,13 @@ class CosineAnnealingLR:
         self.last_epoch, self.base_lr = sd['last_epoch'], sd['base_lr']
 
 
+def _set_pack_map(sg, pack_map):
+    """The segment's device pack map and, where the map carries one, its host copy."""
+    sg.map = 0 if pack_map is None else pack_map.data_ptr()
+    host = getattr(pack_map, 'host', None)
+    sg.map_host = 0 if host is None else ctypes.addressof(host)
+
+
 def grad_sumsq(grad_slice, workspace=None):
     """First pass of clip_grad_norm_: per-block partial sums of squares (device)."""
     L = _lib.lib()
@@ -155,21 +143,13 @@ def grad_sumsq(grad_slice, workspace=None):
     return part
 
 
-def ema_(target, source, rate):
-    L = _lib.lib()
-    _lib.require_device(target, source)
-    _lib.check(L.drpo_ema(_lib.ptr(target), _lib.ptr(source), target.numel(), float(rate), _lib.stream()), 'ema')
-
-
 def ema_segment(p, start, end, target, rate, pack_map=None):
     """EMA-only segment (parameters not stepped by Adam, e.g. the vanilla log-std head)."""
     from ._abi import OptimSeg
     sg = OptimSeg()
     sg.p, sg.start, sg.end, sg.adam = p.data_ptr(), start, end, 0
     sg.ema_target, sg.ema_rate, sg.ema_keep = target.data_ptr(), float(rate), float(1.0 - float(rate))
-    sg.map = 0 if pack_map is None else pack_map.data_ptr()
-    host = getattr(pack_map, 'host', None)
-    sg.map_host = 0 if host is None else ctypes.addressof(host)
+    _set_pack_map(sg, pack_map)
     sg.grad_scale = 1.0
     return sg
 
@@ -189,10 +169,9 @@ def fused_step(segs):
 
 def grad_sumsq_multi(slices, outs):
     """Partial sums of squares of several gradient slices in one launch."""
-    import ctypes
     L = _lib.lib()
-    n = len(slices)
-    g = (ctypes.c_void_p * n)(*[t.data_ptr() for t in slices])
-    cnt = (ctypes.c_int64 * n)(*[t.numel() for t in slices])
-    o = (ctypes.c_void_p * n)(*[t.data_ptr() for t in outs])
-    _lib.check(L.drpo_grad_sumsq_multi(g, cnt, o, n, _lib.stream()), 'grad_sumsq_multi')
+    cnt = len(slices)
+    g = (ctypes.c_void_p * cnt)(*[t.data_ptr() for t in slices])
+    n = (ctypes.c_int64 * cnt)(*[t.numel() for t in slices])
+    out = (ctypes.c_void_p * cnt)(*[t.data_ptr() for t in outs])
+    _lib.check(L.drpo_grad_sumsq_multi(g, n, out, cnt, _lib.stream()), 'grad_sumsq_multi')

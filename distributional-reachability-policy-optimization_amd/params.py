@@ -55,7 +55,7 @@ class FlatGroup:
     def offset(self, name):
         return self.entries[name][0]
 
-    # ---- packed weight mirrors (csrc/pack.hip) ---------------------------------
+    # ---- packed weight mirrors (csrc/pack_layout.hpp, csrc/pack.hip) ---------------------------------
     def enable_packing(self, layers, transposed=None):
         """layers: [(weight_name, din, dout, nbatch)]. Allocates the forward mirror
         (and the transposed one for trained groups) that every MLP kernel streams."""

@@ -497,7 +497,7 @@ int drpo_mlp_wgrad_adam(const drpo_wgrad_item_t* items /* host */, int n, const 
 
 /* ---------------------------------------------------------------- packed weight mirrors
  * Every MLP kernel streams weights from fragment-linear mirrors of the PyTorch
- * [nbatch][dout][din] tensors (layout: csrc/pack.hip). The mirrors are refreshed
+ * [nbatch][dout][din] tensors (layout: csrc/pack_layout.hpp). The mirrors are refreshed
  * by one drpo_pack_weights launch per parameter group after it changes.        */
 typedef struct {
   const float* W;     /* [nbatch][dout][din], member stride wstride */
@@ -595,13 +595,12 @@ int drpo_ens_loss_reduce(const drpo_ens_reduce_t* red /* host */, drpo_stream_t 
 
 /* ---------------------------------------------------------------- optimizer
  * torch.optim.Adam (coupled L2), clip_grad_norm_, update_ema (src/ssac.py:446-455,
- * src/torch_util.py:223-226), over flat parameter groups                       */
+ * src/torch_util.py:223-226), over flat parameter groups: every step is a
+ * drpo_optim_step (or the weight-gradient launch's fused step, drpo_mlp_wgrad_adam).
+ * clip_grad_norm_'s first pass: drpo_grad_sumsq_blocks(n) partial sums of squares of
+ * g[0, n), one per 2048 elements (drpo_grad_sumsq: one slice; _multi below: up to 8) */
 int drpo_grad_sumsq_blocks(int64_t n);
 int drpo_grad_sumsq(const float* g, int64_t n, float* partial, drpo_stream_t stream);
-int drpo_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr_over_bc1, float bc2_sqrt, float beta1,
-              float beta2, float eps, float weight_decay, const float* clip_partial, int n_partial, float max_norm,
-              const float* lr_scale, drpo_stream_t stream);
-int drpo_ema(float* target, const float* source, int64_t n, float rate, drpo_stream_t stream);
 
 /* Fused optimizer step over segments of flat groups: clip coefficient from the
  * partial sums (clip_grad_norm_, src/ssac.py:450-451), Adam (src/defaults.py:4),

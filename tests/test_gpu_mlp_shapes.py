@@ -246,7 +246,7 @@ def _report():
 
 # ------------------------------------------------------------------------------ packer
 def packed_ref(W, transposed=False):
-    """csrc/pack.hip's index formula: P[(cb*NKS + s)*256 + 4*l + i] = W[16cb + (l&15)][16s + 4(l>>4) + i]
+    """csrc/pack_layout.hpp's index formula: P[(cb*NKS + s)*256 + 4*l + i] = W[16cb + (l&15)][16s + 4(l>>4) + i]
     (zero outside the matrix); the transposed mirror is the same formula on W^T."""
     if transposed:
         W = W.t()

@@ -19,7 +19,7 @@ import pytest
 import torch
 
 import drpo_amd  # noqa: F401
-from drpo_amd.optim import Adam, ema_segment, fused_step, grad_sumsq
+from drpo_amd.optim import Adam, ema_segment, fused_step, grad_sumsq, grad_sumsq_multi
 from drpo_amd.params import FlatGroup
 
 pytestmark = pytest.mark.gpu
@@ -122,3 +122,49 @@ def test_block_split_matches_flat_split_and_reference(clip, ema, partial):
         err = (got.double().cpu() - ref).abs()
         tol = 2e-6 * ref.abs() + 1e-7
         assert bool((err <= tol).all()), f'{what}: max err {float(err.max())}'
+
+
+def stepped_group(step):
+    """The file's group with a random Adam state, stepped by step(group, optimizer, scalars)."""
+    g = make_group('g', 1)
+    opt = Adam(g, lr=3e-3, weight_decay=1e-4)
+    opt._ensure_state()
+    gen = torch.Generator(device='cpu').manual_seed(3)
+    opt.m.copy_(torch.randn(g.size, generator=gen) * 0.01)
+    opt.v.copy_(torch.rand(g.size, generator=gen) * 0.01)
+    g0 = dict(p=g.data.clone(), g=g.grad.clone(), m=opt.m.clone(), v=opt.v.clone())
+    sc = Adam(None, lr=3e-3, tensor=g.data).step_scalars()   # the scalars of a first step
+    step(g, opt, sc)
+    torch.cuda.synchronize()
+    return g, opt, g0, sc
+
+
+def test_adam_step_matches_reference_and_one_segment_fused_step():
+    """Adam.step(), the surface of external loss.backward(); optimizer.step() loops: the
+    whole tensor, no clip, the gradient kept, the mirrors marked stale."""
+    gs, os_, g0, sc = stepped_group(lambda g, opt, sc: opt.step())
+    assert os_.step_count == 1 and gs._pk_ver is None
+    assert torch.equal(gs.grad, g0['g'])
+    p, m, v, _ = reference(g0, sc, False, (0, gs.size), False)
+    for got, ref, what in ((gs.data, p, 'p'), (os_.m, m, 'm'), (os_.v, v, 'v')):
+        err = (got.double().cpu() - ref).abs()
+        tol = 2e-6 * ref.abs() + 1e-7
+        assert bool((err <= tol).all()), f'{what}: max err {float(err.max())}'
+    gf, of, _, _ = stepped_group(lambda g, opt, sc: fused_step([opt.segment(0, g.size, sc)]))
+    assert torch.equal(gs.data, gf.data)
+    assert torch.equal(os_.m, of.m) and torch.equal(os_.v, of.v)
+
+
+@pytest.mark.parametrize('n', [1, 2048, 2048 * 3 + 1])
+def test_grad_sumsq_equals_multi_partials(n):
+    gen = torch.Generator(device='cpu').manual_seed(n)
+    x = torch.randn(n, generator=gen).to(DEV)
+    other = torch.randn(2048 + 5, generator=gen).to(DEV)
+    part = grad_sumsq(x)
+    outs = [torch.full((2,), -1.0, device=DEV), torch.full((part.numel(),), -1.0, device=DEV)]
+    grad_sumsq_multi([other, x], outs)
+    torch.cuda.synchronize()
+    assert part.numel() == (n + 2047) // 2048
+    assert torch.equal(part, outs[1])
+    ref = float(x.double().pow(2).sum())
+    assert abs(float(part.double().sum()) - ref) <= 1e-5 * ref

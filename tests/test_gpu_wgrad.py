@@ -184,3 +184,110 @@ def test_wgrad_second_dz_term(rows):
         for got, ref, what in ((d['gW'], gW, 'gW'), (d['gb'], gb, 'gb')):
             err = (got.double().cpu() - ref).abs()
             assert bool((err <= scale + 1e-5 * ref.abs()).all()), f'{what} {d["dout"]}x{d["din"]}: {float(err.max())}'
+
+
+# ---- drpo_mlp_wgrad_adam: the Adam step and mirror refresh by the workgroup that finishes a tile ----
+#
+# One case = one layer (dout, din, nbatch) of a packed FlatGroup, the item being members
+# [z0, z1) of it, driven twice from the same start: drpo_mlp_wgrad_adam, and drpo_mlp_wgrad +
+# drpo_optim_step (zero_grad, the group's pack map with its host copy). Both run adam_step on
+# gv + pv, so everything they leave is bitwise equal. The optimizer launch takes one segment
+# over the whole group when the item is the whole matrix; for a member slice it takes the
+# slice's weight and bias ranges, which is what the fused launch steps.
+ADAM_LAYERS = [(200, 200, 3),    # 64x64 tiles, float4 finish
+               (256, 53, 1),     # 64x64 tiles, scalar finish
+               (200, 14, 3),     # 64x16
+               (13, 200, 3),     # 16x64
+               (7, 13, 1)]       # 16x16
+# (layer, rows, members [z0, z1), start from a non-zero gradient); rows 37: one chunk with a
+# partial k-group, rows 256: 4 row chunks per tile (the slab hand-off and the last arriver)
+ADAM_CASES = [(ly, rows, (0, ly[2]), False) for ly in ADAM_LAYERS for rows in (37, 256)] + [
+    ((200, 200, 3), 256, (1, 3), False),
+    ((200, 200, 3), 37, (0, 3), True),
+    ((13, 200, 3), 256, (0, 3), True)]
+
+
+def adam_case(layer, rows, members, nonzero_grad, fused):
+    from drpo_amd._abi import OptimSeg, WgradAdam
+    from drpo_amd.optim import Adam
+    from drpo_amd.params import FlatGroup
+    dout, din, nb = layer
+    z0, z1 = members
+    nz = z1 - z0
+    L = _lib.lib()
+    g = FlatGroup('w')
+    g.add('w.weight', (nb, dout, din))
+    g.add('w.bias', (nb, dout))
+    g.allocate(DEV)
+    opt = Adam(g, lr=3e-3, weight_decay=1e-4)
+    opt._ensure_state()
+    gen = torch.Generator().manual_seed(1000 * dout + din + rows)
+    for name in ('w.weight', 'w.bias'):    # the alignment padding between entries stays zero
+        shape = g.entries[name][1]
+        g.view(name).copy_(torch.randn(shape, generator=gen))
+        g.view(name, opt.m).copy_(torch.randn(shape, generator=gen) * 0.01)
+        g.view(name, opt.v).copy_(torch.rand(shape, generator=gen) * 0.01)
+        if nonzero_grad:
+            g.view(name, g.grad)[z0:z1].copy_(torch.randn((nz,) + shape[1:], generator=gen) * 0.1)
+    dz = torch.randn(nz, rows, dout, generator=gen).to(DEV)
+    y = torch.randn(nz, rows, din, generator=gen).to(DEV)
+    g.enable_packing([('w.weight', din, dout, nb)], transposed=True)
+    g.ensure_packed()
+    start = dict(p=g.data.clone(), m=opt.m.clone(), v=opt.v.clone())
+    arr = (WgradItem * 1)()
+    it = arr[0]
+    it.dz, it.y = dz.data_ptr(), y.data_ptr()
+    it.gW, it.gb = g.view('w.weight', g.grad)[z0:].data_ptr(), g.view('w.bias', g.grad)[z0:].data_ptr()
+    it.dout, it.din, it.rows, it.nbatch = dout, din, rows, nz
+    it.zstride, it.ystride, it.gwstride, it.gbstride = rows * dout, rows * din, dout * din, dout
+    need = L.drpo_mlp_wgrad_workspace_size(arr, 1)
+    counters = (L.drpo_mlp_wgrad_tiles(ctypes.byref(it)) * 4 + 255) // 256 * 256
+    ws = torch.zeros(max(need, 256), dtype=torch.uint8, device=DEV)
+    sc = opt.step_scalars()
+    pm = g.pack_map()
+    if fused:
+        ad = WgradAdam()
+        ad.g, ad.p, ad.m, ad.v = g.grad.data_ptr(), g.data.data_ptr(), opt.m.data_ptr(), opt.v.data_ptr()
+        ad.lr_over_bc1, ad.bc2_sqrt = sc
+        ad.beta1, ad.beta2 = opt.betas
+        ad.eps, ad.weight_decay = opt.eps, opt.weight_decay
+        ad.map, ad.map_host = pm.data_ptr(), ctypes.addressof(pm.host)
+        _lib.check(L.drpo_mlp_wgrad_adam(arr, 1, None, ctypes.byref(ad), ws.data_ptr(), ws.numel(), _lib.stream()),
+                   'wgrad_adam')
+    else:
+        _lib.check(L.drpo_mlp_wgrad(arr, 1, ws.data_ptr(), ws.numel(), _lib.stream()), 'wgrad')
+        if nz == nb:
+            ranges = [(0, g.size)]
+        else:
+            ow, ob = g.offset('w.weight'), g.offset('w.bias')
+            ranges = [(ow + z0 * dout * din, ow + z1 * dout * din), (ob + z0 * dout, ob + z1 * dout)]
+        segs = [opt.segment(a, b, sc, zero_grad=True, pack_map=pm) for a, b in ranges]
+        _lib.check(L.drpo_optim_step((OptimSeg * len(segs))(*segs), len(segs), _lib.stream()), 'optim_step')
+    torch.cuda.synchronize()
+    return g, opt, start, need, counters
+
+
+@pytest.mark.parametrize('layer,rows,members,nonzero_grad', ADAM_CASES)
+def test_wgrad_adam_matches_wgrad_then_optim_step(layer, rows, members, nonzero_grad):
+    ga, oa, start, need, counters = adam_case(layer, rows, members, nonzero_grad, True)
+    gb, ob, _, _, _ = adam_case(layer, rows, members, nonzero_grad, False)
+    if rows == 256:   # row chunks: the slab hand-off and the last-arriver sum really ran
+        assert need > counters, (need, counters)
+    assert torch.equal(ga.data, gb.data), 'parameters'
+    assert torch.equal(oa.m, ob.m) and torch.equal(oa.v, ob.v), 'Adam moments'
+    assert torch.equal(ga.packed, gb.packed), 'forward mirror'
+    assert torch.equal(ga.packedT, gb.packedT), 'transposed mirror'
+    assert int((ga.grad != 0).sum()) == 0 and int((gb.grad != 0).sum()) == 0
+    # the step happened, and only on the item's members
+    dout, din, nb = layer
+    z0, z1 = members
+    W, W0 = ga.view('w.weight'), ga.view('w.weight', start['p'])
+    assert not torch.equal(W[z0:z1], W0[z0:z1])
+    assert torch.equal(W[:z0], W0[:z0]) and torch.equal(W[z1:], W0[z1:])
+    # both mirrors == a fresh drpo_pack_weights of the result
+    P, PT = ga.packed.clone(), ga.packedT.clone()
+    ga.mark_dirty()
+    ga.ensure_packed()
+    torch.cuda.synchronize()
+    assert torch.equal(P, ga.packed), 'forward mirror vs fresh pack'
+    assert torch.equal(PT, ga.packedT), 'transposed mirror vs fresh pack'
