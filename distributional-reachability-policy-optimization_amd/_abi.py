@@ -30,6 +30,13 @@ class RolloutDesc(ctypes.Structure):
     ]
 
 
+class RolloutTraj(ctypes.Structure):
+    """drpo_rollout_traj_t"""
+    _fields_ = [('len', P), ('states', P), ('actions', P), ('rewards', P), ('constraint_values', P),
+                ('dones', P), ('violations', P), ('weights', P), ('ret', P), ('hmax', P),
+                ('first_violation', P), ('terminated', P)]
+
+
 ENV_PROGRAM = 4          # DRPO_ENV_PROGRAM
 PROG_AFFINE, PROG_BALLS = 0, 1
 PROG_MAX_ROWS = PROG_MAX_TERMS = PROG_MAX_CENTRES = PROG_MAX_BOX = 8
@@ -93,6 +100,7 @@ PROTOTYPES = {
     'drpo_rollout_workspace_size': (c_size_t, [c_int, c_int, c_int]),
     'drpo_rollout_count_offset': (c_size_t, [c_int, c_int, c_int]),
     'drpo_rollout': (c_int, [POINTER(RolloutDesc), P]),
+    'drpo_rollout_trajectories': (c_int, [POINTER(RolloutDesc), POINTER(RolloutTraj), P]),
     'drpo_env_constraints': (c_int, [c_int, c_int, c_int, c_double, c_double, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_constraints_program': (c_int, [P, c_int, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_program_check': (c_int, [POINTER(EnvProgram), c_int]),

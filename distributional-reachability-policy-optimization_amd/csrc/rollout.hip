@@ -25,6 +25,9 @@
 //                                advance in one launch)
 //   larger                       rollout_scan_kernel + rollout_emit_kernel +
 //                                rollout_persist_finalize_kernel
+// drpo_rollout_trajectories runs the same kernel with rollout_traj_kernel as its tail: the
+// staging read per original row (trajectory-major outputs and per-trajectory summaries,
+// src/smbpo.py:229-249 with row identity kept), the virtual buffer untouched.
 #include <type_traits>
 
 #include <hip/hip_runtime.h>
@@ -1144,6 +1147,139 @@ __global__ void rollout_persist_finalize_kernel(int64_t* vptr, const int* n, int
 }
 
 // ---------------------------------------------------------------------------
+// The trajectory tail (drpo_rollout_trajectories): runs after rollout_persist_kernel in
+// place of the ordered emit and reads the same staging trajectory-major. A row was
+// staged at step t exactly when it was alive at t, so a row's done bits say how far its
+// staging reaches; nothing is read beyond that (a tile that empties leaves the horizon
+// loop, so later steps were never written).
+//
+// One workgroup per TRAJ_ROWS original rows, two phases:
+//  A. one lane per row walks the row's done bits (the only dependent chain: one load per
+//     step), and handles what is one value per (row, step) on the way: rewards, dones,
+//     violations, the return, first violation, terminated, length.
+//  B. one lane per (row, k) element of the states, actions and constraint values, each
+//     looping over the steps of its element with the lengths known (independent loads).
+//     At a fixed step adjacent lanes read adjacent staging addresses (coalesced reads);
+//     each lane writes one float per step into its row's own block, so a row's S floats
+//     of a step form one segment and the segments of a row fill whole lines over the
+//     loop. The constraint lanes keep the running maximum: no atomics.
+// Every element of every output given is written (zero at or beyond the length).
+// ---------------------------------------------------------------------------
+constexpr int TRAJ_ROWS = 16;   // rows x (S + A + C) ~ one 256-lane pass at quadrotor dims; B 4096 -> 256 workgroups
+constexpr int TRAJ_NT = 256;
+
+struct TrajArgs {
+  int S, A, C, B, H;
+  const float *st_s, *st_s2, *st_a, *st_r, *st_h;   // staging [t][original row], real widths A and C
+  const uint8_t* st_dv;
+  drpo_rollout_traj_t out;
+};
+
+// the weights are wave-uniform data no kernel writes: read like the constraint programs
+typedef const __attribute__((address_space(4))) double* TrajWeightsK;
+
+// n >= 1 steps of one element: dst[t * ds] = src[t * ss] (dst may be null), four loads in
+// flight at a time; restrict parameters (a struct's members cannot say so), so the loads
+// need not wait for earlier stores. MAX: returns the maximum the way numpy does (a NaN stays).
+template <bool MAX>
+__device__ __forceinline__ float traj_steps(const float* __restrict__ src, size_t ss, float* __restrict__ dst,
+                                            size_t ds, int n) {
+  float m = MAX ? src[0] : 0.f;
+  int t = 0;
+  for (; t + 4 <= n; t += 4) {
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = src[(size_t)(t + u) * ss];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (dst) dst[(size_t)(t + u) * ds] = v[u];
+      if (MAX) m = (v[u] > m || v[u] != v[u]) ? v[u] : m;
+    }
+  }
+  for (; t < n; ++t) {
+    const float v = src[(size_t)t * ss];
+    if (dst) dst[(size_t)t * ds] = v;
+    if (MAX) m = (v > m || v != v) ? v : m;
+  }
+  return m;
+}
+
+__global__ __launch_bounds__(TRAJ_NT) void rollout_traj_kernel(TrajArgs p) {
+  __shared__ int s_len[TRAJ_ROWS];
+  const int tid = threadIdx.x;
+  const int S = p.S, A = p.A, C = p.C, H = p.H;
+  const size_t B = (size_t)p.B;
+  const int row0 = blockIdx.x * TRAJ_ROWS;
+  const int nr = min(TRAJ_ROWS, p.B - row0);
+  const drpo_rollout_traj_t& o = p.out;
+
+  // ---- A. length walk + the per-(row, step) scalars and the summaries ---------
+  if (tid < TRAJ_ROWS) {
+    int len = 0;
+    if (tid < nr) {
+      const size_t i = (size_t)row0 + tid;
+      TrajWeightsK w = (TrajWeightsK)(uintptr_t)o.weights;
+      int fv = -1;
+      unsigned last = 0;
+      double acc = 0.0;
+      for (int t = 0; t < H; ++t) {
+        const size_t src = (size_t)t * B + i;
+        const unsigned dv = p.st_dv[src];
+        const float r = p.st_r[src];
+        if (o.rewards) o.rewards[i * H + t] = r;
+        if (o.dones) o.dones[i * H + t] = dv & 1;
+        if (o.violations) o.violations[i * H + t] = (dv >> 1) & 1;
+        if (o.ret) acc = __dadd_rn(acc, __dmul_rn(w[t], (double)r));
+        if ((dv & 2) && fv < 0) fv = t;
+        last = dv;
+        len = t + 1;
+        if (dv & 1) break;
+      }
+      for (int t = len; t < H; ++t) {
+        if (o.rewards) o.rewards[i * H + t] = 0.f;
+        if (o.dones) o.dones[i * H + t] = 0;
+        if (o.violations) o.violations[i * H + t] = 0;
+      }
+      o.len[i] = len;
+      if (o.ret) o.ret[i] = (float)acc;
+      if (o.first_violation) o.first_violation[i] = fv;
+      if (o.terminated) o.terminated[i] = last & 1;
+    }
+    s_len[tid] = len;
+  }
+  __syncthreads();
+
+  // ---- B. the [row][step][k] arrays, one lane per (row, k) ---------------------
+  const int nS = o.states ? nr * S : 0;
+  const int nA = o.actions ? nr * A : 0;
+  const int nC = (o.constraint_values || o.hmax) ? nr * C : 0;
+  for (int e = tid; e < nS + nA + nC; e += TRAJ_NT) {
+    if (e < nS) {
+      const int r = e / S, k = e - r * S, len = s_len[r];
+      const size_t i = (size_t)row0 + r;
+      float* dst = o.states + i * (H + 1) * S + k;
+      traj_steps<false>(p.st_s + i * S + k, B * S, dst, S, len);
+      dst[(size_t)len * S] = p.st_s2[((size_t)(len - 1) * B + i) * S + k];
+      for (int t = len + 1; t <= H; ++t) dst[(size_t)t * S] = 0.f;
+    } else if (e < nS + nA) {
+      const int q = e - nS, r = q / A, d = q - r * A, len = s_len[r];
+      const size_t i = (size_t)row0 + r;
+      float* dst = o.actions + i * H * A + d;
+      traj_steps<false>(p.st_a + i * A + d, B * A, dst, A, len);
+      for (int t = len; t < H; ++t) dst[(size_t)t * A] = 0.f;
+    } else {
+      const int q = e - nS - nA, r = q / C, c = q - r * C, len = s_len[r];
+      const size_t i = (size_t)row0 + r;
+      float* dst = o.constraint_values ? o.constraint_values + i * H * C + c : nullptr;
+      const float m = traj_steps<true>(p.st_h + i * C + c, B * C, dst, C, len);
+      if (dst)
+        for (int t = len; t < H; ++t) dst[(size_t)t * C] = 0.f;
+      if (o.hmax) o.hmax[i * C + c] = m;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
 
@@ -1258,11 +1394,13 @@ static void launch_persist(bool paired, bool pg, const PersistArgs& a, size_t ld
   k<<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
 }
 
-// engine 2: fused-horizon kernel + one of the two emit tails
-static int rollout_fused(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt, int64_t rlen, hipStream_t stream) {
-  DRPO_REQUIRE(d->H <= PERSIST_MAX_H, "drpo_rollout: engine 2 supports horizon <= %d", PERSIST_MAX_H);
+// engine 2's horizon kernel for either tail (`who`: the entry point, for its messages).
+// Fills `a`, which the tails read too. self_emit: the kernel copies the buffer pointer for
+// rollout_emit_self_kernel; without it the kernel touches neither the buffer nor its pointer.
+static int persist_run(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt, int64_t rlen, bool self_emit,
+                       const char* who, hipStream_t stream, PersistArgs& a) {
+  DRPO_REQUIRE(d->H <= PERSIST_MAX_H, "%s: engine 2 supports horizon <= %d", who, PERSIST_MAX_H);
   const int S = d->S, A = d->A, S1 = d->S + 1, B = d->B, H = d->H;
-  PersistArgs a{};
   fill_shared_args(a, d, rlen);
   a.B = B; a.H = H;
   a.ntiles = (B + rpt - 1) / rpt;
@@ -1277,13 +1415,12 @@ static int rollout_fused(const drpo_rollout_desc_t* d, const RolloutWs& w, int r
   for (int t = 0; t < H; ++t) a.members[t] = d->members[t];
 
   const size_t lds_bytes = persist_lds_bytes(S, A, d->Ha, d->Hm, rpt, 8);
-  DRPO_REQUIRE(lds_bytes <= 160 * 1024, "drpo_rollout: LDS %zu too large", lds_bytes);
+  DRPO_REQUIRE(lds_bytes <= 160 * 1024, "%s: LDS %zu too large", who, lds_bytes);
   // LDS-resident actor weights (see rollout_persist_kernel) when they fit
   const size_t lw_bytes = sizeof(float) * (size_t)(32 + 16 * PERSIST_L2_LDS) * 256;
   const bool lw = rpt == 16 && S <= 16 && d->Ha == 256 && 2 * A <= 16 && lds_bytes + lw_bytes <= 160 * 1024;
   const bool paired = S1 <= 16 && d->Hm == 200;   // the kernel's PM specialisation
   const bool pg = d->env_id == DRPO_ENV_PROGRAM;
-  const bool self_emit = (int64_t)H * a.ntiles <= EMIT_SELF_MAX;
   if (self_emit) {
     a.vptr_in = d->vptr;
     a.base_slot = w.off + H + 1;
@@ -1294,6 +1431,15 @@ static int rollout_fused(const drpo_rollout_desc_t* d, const RolloutWs& w, int r
   else launch_persist<1, false>(paired, pg, a, lds_bytes, stream);
   DRPO_LAUNCH_CHECK("rollout_persist");
   if (d->step_events) hipEventRecord((hipEvent_t)d->step_events[1], stream);
+  return DRPO_OK;
+}
+
+// engine 2: fused-horizon kernel + one of the two emit tails
+static int rollout_fused(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt, int64_t rlen, hipStream_t stream) {
+  const int H = d->H;
+  const bool self_emit = (int64_t)H * ((d->B + rpt - 1) / rpt) <= EMIT_SELF_MAX;
+  PersistArgs a{};
+  if (const int rc = persist_run(d, w, rpt, rlen, self_emit, "drpo_rollout", stream, a)) return rc;
   const dim3 eg((unsigned)((a.ntiles * rpt + 255) / 256), (unsigned)H);
   const EmitDst dst{d->vs, d->va, d->vs2, d->vr, d->vh, d->vd, d->vv, d->vcap};
   if (self_emit) {
@@ -1362,32 +1508,38 @@ static int rollout_stepwise(const drpo_rollout_desc_t* d, const RolloutWs& w, in
   return DRPO_OK;
 }
 
-// validation, tile choice, engine choice
-DRPO_API int drpo_rollout(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  DRPO_REQUIRE(d, "drpo_rollout: null descriptor");
-  DRPO_REQUIRE(d->S >= 1 && d->S <= 64 && d->A >= 1 && d->A <= 8, "drpo_rollout: S=%d A=%d out of range", d->S, d->A);
-  DRPO_REQUIRE(d->Ha >= 1 && d->Ha <= 256 && d->Hm >= 1 && d->Hm <= 256, "drpo_rollout: hidden dims must be <= 256");
-  DRPO_REQUIRE(d->S + 1 <= 64, "drpo_rollout: state_dim+1 must be <= 64");
-  DRPO_REQUIRE(d->env_id >= 0 && d->env_id <= DRPO_ENV_PROGRAM, "drpo_rollout: unknown env id %d", d->env_id);
+// What drpo_rollout and drpo_rollout_trajectories check alike, and the tile choice (`who`:
+// the entry point, for its messages). buffer: the checks on the virtual-buffer fields
+// (vptr, vcap), which only drpo_rollout writes.
+static int rollout_checks(const drpo_rollout_desc_t* d, const char* who, bool buffer, int& rpt_out, int64_t& rlen_out) {
+  DRPO_REQUIRE(d, "%s: null descriptor", who);
+  DRPO_REQUIRE(d->S >= 1 && d->S <= 64 && d->A >= 1 && d->A <= 8, "%s: S=%d A=%d out of range", who, d->S, d->A);
+  DRPO_REQUIRE(d->Ha >= 1 && d->Ha <= 256 && d->Hm >= 1 && d->Hm <= 256, "%s: hidden dims must be <= 256", who);
+  DRPO_REQUIRE(d->S + 1 <= 64, "%s: state_dim+1 must be <= 64", who);
+  DRPO_REQUIRE(d->env_id >= 0 && d->env_id <= DRPO_ENV_PROGRAM, "%s: unknown env id %d", who, d->env_id);
   if (d->env_id == DRPO_ENV_PROGRAM)
     // the program's row count lives in device memory: the caller states it (C) and has
     // checked the program with drpo_env_program_check before the upload
     DRPO_REQUIRE(d->C >= 1 && d->C <= DRPO_PROG_MAX_ROWS && d->env_program,
-                 "drpo_rollout: env id %d needs 1 <= con_dim (%d) <= %d and a device program (env_program)", d->env_id,
+                 "%s: env id %d needs 1 <= con_dim (%d) <= %d and a device program (env_program)", who, d->env_id,
                  d->C, (int)DRPO_PROG_MAX_ROWS);
   else
     DRPO_REQUIRE(d->C >= 1 && d->C <= 8 && d->C == env_con_dim(d->env_id, d->tracking_n_surr),
-                 "drpo_rollout: con_dim %d does not match env %d", d->C, d->env_id);
-  DRPO_REQUIRE(d->B >= 1 && d->H >= 1 && (int64_t)d->B * d->H <= d->vcap,
-               "drpo_rollout: B*H=%lld exceeds buffer capacity %lld", (long long)d->B * d->H, (long long)d->vcap);
-  DRPO_REQUIRE(d->workspace && d->vptr && d->replay_states, "drpo_rollout: null pointer");
-  DRPO_REQUIRE(d->B <= 16 * 8192, "drpo_rollout: batch %d too large (max 131072)", d->B);
+                 "%s: con_dim %d does not match env %d", who, d->C, d->env_id);
+  if (buffer) {
+    DRPO_REQUIRE(d->B >= 1 && d->H >= 1 && (int64_t)d->B * d->H <= d->vcap,
+                 "%s: B*H=%lld exceeds buffer capacity %lld", who, (long long)d->B * d->H, (long long)d->vcap);
+    DRPO_REQUIRE(d->workspace && d->vptr && d->replay_states, "%s: null pointer", who);
+  } else {
+    DRPO_REQUIRE(d->B >= 1 && d->H >= 1, "%s: B=%d H=%d must be positive", who, d->B, d->H);
+    DRPO_REQUIRE(d->workspace && d->replay_states, "%s: null pointer", who);
+  }
+  DRPO_REQUIRE(d->B <= 16 * 8192, "%s: batch %d too large (max 131072)", who, d->B);
   const int64_t rlen = d->replay_ptr < d->replay_cap ? d->replay_ptr : d->replay_cap;
-  DRPO_REQUIRE(rlen >= d->B, "drpo_rollout: replay has %lld rows < batch %d (sampling without replacement)",
+  DRPO_REQUIRE(rlen >= d->B, "%s: replay has %lld rows < batch %d (sampling without replacement)", who,
                (long long)rlen, d->B);
   if (d->env_id == ENV_TRACKING)
-    DRPO_REQUIRE(d->tracking_surr_start + 4 * d->tracking_n_surr <= d->S, "drpo_rollout: tracking layout");
+    DRPO_REQUIRE(d->tracking_surr_start + 4 * d->tracking_n_surr <= d->S, "%s: tracking layout", who);
 
   // 32-row tiles halve the weight bytes per MFMA once the batch fills the chip with
   // them (B >= 8192), when the wider tile still fits the LDS (not for tracking's S=51)
@@ -1395,10 +1547,21 @@ DRPO_API int drpo_rollout(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
                                    : (d->B >= 256 * 32 &&
                                               persist_lds_bytes(d->S, d->A, d->Ha, d->Hm, 32, 8) <= 160 * 1024
                                           ? 32 : 16);
-  DRPO_REQUIRE(rpt == 16 || rpt == 32, "drpo_rollout: rows_per_tile must be 16 or 32");
+  DRPO_REQUIRE(rpt == 16 || rpt == 32, "%s: rows_per_tile must be 16 or 32", who);
   DRPO_REQUIRE(d->engine >= 0 && d->engine <= 2 && (d->eps_layout == 0 || d->eps_layout == 1),
-               "drpo_rollout: engine %d / eps_layout %d", d->engine, d->eps_layout);
-  DRPO_REQUIRE((d->eps_a == nullptr) == (d->eps_m == nullptr), "drpo_rollout: eps_a and eps_m go together");
+               "%s: engine %d / eps_layout %d", who, d->engine, d->eps_layout);
+  DRPO_REQUIRE((d->eps_a == nullptr) == (d->eps_m == nullptr), "%s: eps_a and eps_m go together", who);
+  rpt_out = rpt;
+  rlen_out = rlen;
+  return DRPO_OK;
+}
+
+// validation, tile choice, engine choice
+DRPO_API int drpo_rollout(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  int rpt;
+  int64_t rlen;
+  if (const int rc = rollout_checks(d, "drpo_rollout", true, rpt, rlen)) return rc;
   int engine = d->engine;
   if (engine == 0) engine = (d->eps_a && d->eps_layout == 0) || d->H > PERSIST_MAX_H ? 1 : 2;
   if (d->eps_a)
@@ -1407,6 +1570,30 @@ DRPO_API int drpo_rollout(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
   RolloutWs w;
   rollout_ws(d->B, d->S, d->H, reinterpret_cast<uintptr_t>(d->workspace), w);
   return engine == 2 ? rollout_fused(d, w, rpt, rlen, stream) : rollout_stepwise(d, w, rpt, rlen, stream);
+}
+
+// The fused engine's horizon kernel + the trajectory tail: the rollout per original row
+// (row identity) instead of into the virtual buffer, which it never touches.
+DRPO_API int drpo_rollout_trajectories(const drpo_rollout_desc_t* d, const drpo_rollout_traj_t* out,
+                                       drpo_stream_t stream_) {
+  static const char who[] = "drpo_rollout_trajectories";
+  hipStream_t stream = (hipStream_t)stream_;
+  int rpt;
+  int64_t rlen;
+  if (const int rc = rollout_checks(d, who, false, rpt, rlen)) return rc;
+  DRPO_REQUIRE(d->engine != 1, "%s: runs the fused engine only (engine 0 or 2, not 1)", who);
+  DRPO_REQUIRE(!(d->eps_a && d->eps_layout == 0),
+               "%s: recorded draws must be indexed by original row (eps_layout 1), not compacted per step", who);
+  DRPO_REQUIRE(out && out->len, "%s: null len (the one required output)", who);
+  DRPO_REQUIRE(!out->ret || out->weights, "%s: ret needs weights", who);
+  RolloutWs w;
+  rollout_ws(d->B, d->S, d->H, reinterpret_cast<uintptr_t>(d->workspace), w);
+  PersistArgs a{};
+  if (const int rc = persist_run(d, w, rpt, rlen, false, who, stream, a)) return rc;
+  const TrajArgs ta{d->S, d->A, d->C, d->B, d->H, w.st_s, w.st_s2, w.st_a, w.st_r, w.st_h, w.st_dv, *out};
+  rollout_traj_kernel<<<(d->B + TRAJ_ROWS - 1) / TRAJ_ROWS, TRAJ_NT, 0, stream>>>(ta);
+  DRPO_LAUNCH_CHECK("rollout_traj");
+  return DRPO_OK;
 }
 
 __global__ void prp_kernel(int64_t* out, int64_t B, int64_t N, int hb, uint32_t k0, uint32_t k1, uint32_t k2,

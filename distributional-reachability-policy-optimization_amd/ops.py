@@ -75,21 +75,44 @@ def _rollout_static(alg, policy, B, H):
     virtual-buffer pointers, and the workspace. Built once and cached on ``alg``; per
     call only the members, the noise, the initial-state source and the events change.
     (Building it took ~20 tensor views per call: most of the call's host time.)"""
-    model = alg.model_ensemble
     vb = alg.virt_buffer._module
-    pg, mg = policy.group, model.group
-    norm = model.state_normalizer
     # every device pointer the descriptor stores is part of the key (a buffer reallocated
     # under one of them must never leave a stale pointer behind)
-    key = (id(policy), B, H, pg.data.data_ptr(), pg.packed.data_ptr(), mg.data.data_ptr(), mg.packed.data_ptr(),
-           norm.mean.data_ptr(), norm.std.data_ptr(), model.min_log_var.data_ptr(), model.max_log_var.data_ptr(),
-           vb.capacity) + tuple(getattr(vb, f).data_ptr() for f in _VB_FIELDS)
+    key = _rollout_key(alg, policy, B, H) + (vb.capacity,) + tuple(getattr(vb, f).data_ptr() for f in _VB_FIELDS)
     cache = alg.__dict__.setdefault('_rollout_desc_cache', {})
     hit = cache.get(key)
     if hit is not None:
         return hit
     if len(cache) >= _ROLLOUT_CACHE_MAX:   # (B, H) or buffers changed: drop the old entries
         cache.clear()
+    L = _lib.lib()
+    d, members, ws, prog = _rollout_desc(alg, policy, B, H, f'rollout.{B}.{H}')
+    d.vs, d.va, d.vs2, d.vr = vb._states.data_ptr(), vb._actions.data_ptr(), vb._next_states.data_ptr(), \
+        vb._rewards.data_ptr()
+    d.vh, d.vd, d.vv = vb._constraint_values.data_ptr(), vb._dones.data_ptr(), vb._violations.data_ptr()
+    d.vptr, d.vcap = vb._pointer.data_ptr(), vb.capacity
+    off = L.drpo_rollout_count_offset(B, alg.state_dim, H)
+    count = ws[off:off + 8].view(torch.int64)[0]
+    hit = cache[key] = (d, members, count, prog)   # prog: keeps the uploaded program alive
+    return hit
+
+
+def _rollout_key(alg, policy, B, H):
+    """The device pointers and shapes of _rollout_desc, as a cache key."""
+    model = alg.model_ensemble
+    pg, mg = policy.group, model.group
+    norm = model.state_normalizer
+    return (id(policy), B, H, pg.data.data_ptr(), pg.packed.data_ptr(), mg.data.data_ptr(), mg.packed.data_ptr(),
+            norm.mean.data_ptr(), norm.std.data_ptr(), model.min_log_var.data_ptr(), model.max_log_var.data_ptr())
+
+
+def _rollout_desc(alg, policy, B, H, ws_name):
+    """A rollout descriptor without the virtual-buffer fields, on a workspace of its own
+    (``ws_name``): what drpo_rollout and drpo_rollout_trajectories read alike. Returns
+    (descriptor, its members array, the workspace, the uploaded program or None)."""
+    model = alg.model_ensemble
+    pg, mg = policy.group, model.group
+    norm = model.state_normalizer
     L = _lib.lib()
     S, A, C = alg.state_dim, alg.action_dim, alg.con_dim
     pa = [(pg.pview(f'net.{2 * i}.weight')[0], pg.view(f'net.{2 * i}.bias')) for i in range(policy.spec.n_layers)]
@@ -113,19 +136,12 @@ def _rollout_static(alg, policy, B, H):
     (d.lW1, d.lb1), (d.lW2, d.lb2) = [(W.data_ptr(), b.data_ptr()) for W, b in logv]
     d.norm_mean, d.norm_std = norm.mean.data_ptr(), norm.std.data_ptr()
     d.min_lv, d.max_lv = model.min_log_var.data_ptr(), model.max_log_var.data_ptr()
-    d.vs, d.va, d.vs2, d.vr = vb._states.data_ptr(), vb._actions.data_ptr(), vb._next_states.data_ptr(), \
-        vb._rewards.data_ptr()
-    d.vh, d.vd, d.vv = vb._constraint_values.data_ptr(), vb._dones.data_ptr(), vb._violations.data_ptr()
-    d.vptr, d.vcap = vb._pointer.data_ptr(), vb.capacity
     # a workspace of its own per entry (the cached pointers must never see it reallocated)
-    ws = alg._workspace(f'rollout.{B}.{H}', L.drpo_rollout_workspace_size(B, S, H))
+    ws = alg._workspace(ws_name, L.drpo_rollout_workspace_size(B, S, H))
     d.workspace = ws.data_ptr()
     members = (ctypes.c_int * H)()
     d.members = members
-    off = L.drpo_rollout_count_offset(B, S, H)
-    count = ws[off:off + 8].view(torch.int64)[0]
-    hit = cache[key] = (d, members, count, prog)   # prog: keeps the uploaded program alive
-    return hit
+    return d, members, ws, prog
 
 
 def rollout(alg, policy, initial_states, noise, timer=None, eps_layout=0):
@@ -194,6 +210,172 @@ def rollout(alg, policy, initial_states, noise, timer=None, eps_layout=0):
     view = _RolloutResult(vb, start_ptr, count)
     view.tape_counts = ns
     return view
+
+
+TRAJ_MAX_H = 128    # the fused engine's horizon limit (PERSIST_MAX_H)
+
+
+class ImaginedRollout:
+    """Imagined trajectories, one per start state (row i of every tensor is the rollout
+    from start state i). With B rows, horizon H:
+
+      states [B, H+1, S]         states[i, t] at the start of step t, states[i, lengths[i]] the last next state
+      actions [B, H, A], rewards [B, H], constraint_values [B, H, C]
+      dones, violations [B, H]   bool
+      lengths [B] int32          steps the row lived, 1..H
+      returns [B]                sum_t weights[t] * rewards[i, t] (weights: discount ** t)
+      max_constraint [B, C]      max over the row's steps of constraint_values
+      first_violation [B] int32  first step with a violation, -1 if none
+      terminated [B] bool        the row ended with done (False: cut by the horizon)
+      mask [B, H] bool           t < lengths[i]
+
+    Everything at or beyond a row's length is zero. ``members`` is the ensemble member
+    of each step. members='each' stacks the runs on a new leading axis."""
+    TENSORS = ('states', 'actions', 'rewards', 'constraint_values', 'dones', 'violations', 'lengths', 'returns',
+               'max_constraint', 'first_violation', 'terminated')
+
+    def __init__(self, members, **tensors):
+        assert set(tensors) == set(self.TENSORS)
+        self.members = members
+        self.__dict__.update(tensors)
+
+    @property
+    def mask(self):
+        H = self.rewards.shape[-1]
+        return torch.arange(H, device=self.lengths.device) < self.lengths.unsqueeze(-1)
+
+    @classmethod
+    def stack(cls, runs):
+        return cls([r.members for r in runs], **{k: torch.stack([getattr(r, k) for r in runs]) for k in cls.TENSORS})
+
+
+def _traj_static(alg, policy, B, H):
+    """_rollout_static's counterpart for drpo_rollout_trajectories: a cache, descriptor and
+    workspace of its own (never the entry drpo_rollout's pointers live in), and the
+    virtual-buffer fields left NULL."""
+    key = _rollout_key(alg, policy, B, H)
+    cache = alg.__dict__.setdefault('_rollout_traj_desc_cache', {})
+    hit = cache.get(key)
+    if hit is None:
+        if len(cache) >= _ROLLOUT_CACHE_MAX:
+            cache.clear()
+        d, members, _, prog = _rollout_desc(alg, policy, B, H, f'rollout_traj.{B}.{H}')
+        hit = cache[key] = (d, members, prog)
+    return hit
+
+
+def _traj_members(model, members, H):
+    """members as an int (every step) or a sequence of H ints, checked against the
+    ensemble size here: the descriptor does not carry it."""
+    mem = [members] * H if isinstance(members, (int, np.integer)) else list(members)
+    if len(mem) != H:
+        raise ValueError(f'members: {len(mem)} entries for horizon {H}')
+    E = model.ensemble_size
+    for m in mem:
+        if not isinstance(m, (int, np.integer)) or not 0 <= m < E:
+            raise ValueError(f'members: {m!r} is not a member index of an ensemble of {E}')
+    return [int(m) for m in mem]
+
+
+def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, eps_a=None, eps_m=None, eps_layout=1,
+                         weights=None, out=None, horizon=None, ctr=None):
+    """One imagined rollout (src/smbpo.py:229-249) kept per trajectory: the fused horizon
+    kernel and the trajectory tail (drpo_rollout_trajectories). Never touches
+    alg.virt_buffer. Mirrors ``rollout``: the same start states, members and draws for
+    the same noise object, so row i here is the trajectory whose surviving steps
+    ``rollout`` writes into the buffer.
+
+    members: None = one random elite per step (from ``noise``, as ``rollout``), an int, or
+    H ints. eps_a [H, B, A] / eps_m [H, B, S+1]: recorded draws on the device, indexed by
+    original row (eps_layout 1); a TapeNoise in that layout supplies its own. weights: H
+    float64 per-step weights of ``returns`` (default ones). out: dict of preallocated
+    tensors by ImaginedRollout name. horizon: default alg.horizon. ctr: the noise counter
+    (default: the next one of ``noise``)."""
+    from ._abi import RolloutTraj
+    L = _lib.lib()
+    dev = alg.device
+    B = alg.rollout_batch_size
+    H = alg.horizon if horizon is None else int(horizon)
+    if not 1 <= H <= TRAJ_MAX_H:
+        raise ValueError(f'horizon {H}: imagined trajectories run the fused engine, 1 <= horizon <= {TRAJ_MAX_H}')
+    S, A, C = alg.state_dim, alg.action_dim, alg.con_dim
+    S1 = S + 1
+    model = alg.model_ensemble
+    rb = alg.replay_buffer._module
+    _lib.require_device(policy.group.data, model.group.data)
+
+    if initial_states is not None:
+        src = initial_states.contiguous().float()
+        _lib.require_device(src)
+        assert src.dim() == 2 and src.shape[1] == S, 'initial_states must be [n, state_dim]'
+        B = len(src)
+        src_ptr = src_cap = B
+        init_idx = torch.arange(B, device=dev, dtype=torch.int64)
+    else:
+        src, src_ptr, src_cap = rb._states, rb.pointer, rb.capacity
+        idx = noise.np_choice(min(src_ptr, src_cap), B)
+        init_idx = None if idx is None else _dev(idx, dev, torch.int64)
+
+    if noise.parity:
+        assert members is None and eps_a is None and eps_m is None, 'a tape supplies its own members and draws'
+        ks, _, ea, em = _tape_rollout_noise(noise, H, B, A, S1)
+        mem = [model._elite_inds[k] for k in ks] + [0] * (H - len(ks))
+        eps_a, eps_m = _dev(ea, dev), _dev(em, dev)
+    else:
+        if members is None:
+            elites = model._elite_inds
+            members = [elites[noise.choice(len(elites))] for _ in range(H)]
+        mem = _traj_members(model, members, H)
+        assert (eps_a is None) == (eps_m is None), 'eps_a and eps_m go together'
+        if eps_a is not None:
+            _lib.require_device(eps_a, eps_m)
+            assert eps_a.dtype == eps_m.dtype == torch.float32 and eps_a.is_contiguous() and eps_m.is_contiguous() \
+                and eps_a.shape == (H, B, A) and eps_m.shape == (H, B, S1), 'eps_a [H, B, A] / eps_m [H, B, S+1] float32'
+    ctr = noise.next() if ctr is None else ctr
+
+    w = torch.ones(H, dtype=torch.float64, device=dev) if weights is None else \
+        torch.as_tensor(weights, dtype=torch.float64).to(dev).contiguous()
+    assert w.shape == (H,), 'weights: one float64 per step'
+
+    f32, i32, b8 = torch.float32, torch.int32, torch.bool
+    spec = {'lengths': ((B,), i32), 'states': ((B, H + 1, S), f32), 'actions': ((B, H, A), f32),
+            'rewards': ((B, H), f32), 'constraint_values': ((B, H, C), f32), 'dones': ((B, H), b8),
+            'violations': ((B, H), b8), 'returns': ((B,), f32), 'max_constraint': ((B, C), f32),
+            'first_violation': ((B,), i32), 'terminated': ((B,), b8)}
+    out = {} if out is None else dict(out)
+    assert set(out) <= set(spec), f'out: unknown names {sorted(set(out) - set(spec))}'
+    res = {}
+    for name, (shape, dt) in spec.items():
+        t = out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dt, device=dev)
+        else:
+            _lib.require_device(t)
+            assert (t.dtype == dt or (dt == b8 and t.dtype == torch.uint8)) and tuple(t.shape) == shape and \
+                t.is_contiguous(), f'out[{name!r}]: need contiguous {dt} {shape}'
+        res[name] = t
+
+    policy.group.ensure_packed()
+    model.group.ensure_packed()
+    d, marr, _ = _traj_static(alg, policy, B, H)
+    marr[:] = mem
+    d.replay_states, d.replay_ptr, d.replay_cap = src.data_ptr(), src_ptr, src_cap
+    d.init_idx = 0 if init_idx is None else init_idx.data_ptr()
+    d.eps_a = 0 if eps_a is None else eps_a.data_ptr()
+    d.eps_m = 0 if eps_m is None else eps_m.data_ptr()
+    d.seed, d.ctr = noise.seed, ctr
+    d.rows_per_tile = getattr(alg, 'rows_per_tile', 0)
+    d.engine, d.eps_layout = 2, (eps_layout if eps_a is not None else 0)
+    d.step_events = None
+    t = RolloutTraj()
+    t.len, t.states, t.actions, t.rewards = (res[k].data_ptr() for k in ('lengths', 'states', 'actions', 'rewards'))
+    t.constraint_values, t.dones, t.violations = (res[k].data_ptr() for k in ('constraint_values', 'dones',
+                                                                              'violations'))
+    t.weights = w.data_ptr()
+    t.ret, t.hmax, t.first_violation, t.terminated = (res[k].data_ptr() for k in ('returns', 'max_constraint',
+                                                                                  'first_violation', 'terminated'))
+    _lib.check(L.drpo_rollout_trajectories(ctypes.byref(d), ctypes.byref(t), _lib.stream()), 'rollout_trajectories')
+    return ImaginedRollout(mem, **res)
 
 
 def rollout_host_env(alg, policy, initial_states, noise):

@@ -251,6 +251,76 @@ class SMBPO(Configurable, Module):
             return ops.rollout_host_env(self, policy, initial_states, noise)
         return ops.rollout(self, policy, initial_states, noise, timer)
 
+    IMAGINE_SALT = 0x1A6E
+
+    def imagine(self, states=None, policy=None, horizon=None, *, members=None, deterministic=False,
+                model_noise=True, discount=None, noise=None):
+        """What the model predicts happens from ``states`` under ``policy``: the rollout of
+        src/smbpo.py:229-249 kept per trajectory (ops.ImaginedRollout: row i of every tensor
+        is the trajectory from start state i), on the fused horizon kernel. Nothing of the
+        training state changes: not the virtual buffer, its pointer or steps_sampled.
+
+        states     None: rollout_batch_size start states drawn from the replay buffer as
+                   ``rollout`` draws them; else one trajectory per given row.
+        policy     default the actor; horizon default self.horizon (<= 128).
+        members    None: one random elite per step, as ``rollout``; an int: that ensemble
+                   member at every step; H ints; 'each': one launch per elite member with
+                   common draws (same noise counter), stacked in _elite_inds order.
+        deterministic   the policy's mean action; model_noise=False: the member's mean
+                   prediction. (Recorded-draw inputs of the kernel: zeros for the
+                   switched-off draw, device-generated normals for the other.)
+        discount   of ``returns``; default the solver's.
+        noise      default a stream private to imagine, derived from the trainer's seed, so
+                   the training stream is left alone. A given noise object is used the way
+                   ``rollout`` uses it (imagine(noise=DeviceNoise(s)) is rollout(noise=
+                   DeviceNoise(s)) row for row) and advances by one counter."""
+        from . import ops
+        from .rng import _mix64
+        if self.env_params is None:
+            raise NotImplementedError('imagine needs the constraint functions on the device: give the env a '
+                                      'ConstraintProgram (drpo_constraint_program, see INTEGRATION.md); the host '
+                                      'round trip of such envs is not supported here')
+        H = self.horizon if horizon is None else int(horizon)
+        if not 1 <= H <= ops.TRAJ_MAX_H:
+            raise ValueError(f'horizon {H}: imagine runs the fused engine, 1 <= horizon <= {ops.TRAJ_MAX_H}')
+        policy = self.actor if policy is None else policy
+        if noise is None:
+            if self.__dict__.get('_imagine_noise') is None:
+                self._imagine_noise = DeviceNoise(_mix64(self.noise.base_seed ^ self.IMAGINE_SALT), rank=0, world=1)
+            noise = self._imagine_noise
+        gamma = float(self.solver.discount if discount is None else discount)
+        weights = np.power(np.float64(gamma), np.arange(H, dtype=np.float64))
+        if states is not None:
+            states = torch.as_tensor(states, dtype=torch.float32).to(self.device).reshape(-1, self.state_dim)
+        B = self.rollout_batch_size if states is None else len(states)
+
+        each = isinstance(members, str)
+        if each and members != 'each':
+            raise ValueError(f"members: {members!r} (None, an int, {H} ints or 'each')")
+        kw = {}
+        if each or deterministic or not model_noise:
+            if noise.parity:
+                raise ValueError("a recorded tape fixes the members and the draws: no 'each', deterministic or "
+                                 'model_noise with it')
+            kw['ctr'] = noise.next()
+        if deterministic or not model_noise:
+            # the kernel's recorded-draw inputs, indexed by original row
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(_mix64(noise.seed ^ _mix64(kw['ctr'])) & 0x7FFFFFFFFFFFFFFF)
+            A, S1 = self.action_dim, self.state_dim + 1
+
+            def draws(on, width):
+                if not on:
+                    return torch.zeros(H, B, width, device=self.device)
+                return torch.randn(H, B, width, device=self.device, generator=gen)
+            kw.update(eps_a=draws(not deterministic, A), eps_m=draws(model_noise, S1), eps_layout=1)
+
+        def run(m):
+            return ops.rollout_trajectories(self, policy, states, noise, members=m, weights=weights, horizon=H, **kw)
+        if each:
+            return ops.ImaginedRollout.stack([run(int(m)) for m in self.model_ensemble._elite_inds])
+        return run(members)
+
     def update_models(self, model_steps, noise=None):
         """src/smbpo.py:214-227."""
         log.message(f'Fitting models @ t = {self.steps_sampled.item()}')

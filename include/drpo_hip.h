@@ -143,6 +143,42 @@ size_t drpo_rollout_workspace_size(int B, int S, int H);
 size_t drpo_rollout_count_offset(int B, int S, int H); /* byte offset of the int64 row count in the workspace */
 int drpo_rollout(const drpo_rollout_desc_t* d /* host */, drpo_stream_t stream);
 
+/* The same imagined rollout (src/smbpo.py:229-249), kept per trajectory instead of
+ * written into the virtual buffer. drpo_rollout's ordered emit compacts each step's
+ * surviving rows, after which no buffer row can be traced to its start state; this
+ * entry point adds exactly that, row identity: trajectory i of every output is the
+ * rollout from initial state i. It runs the fused engine's horizon kernel and, in
+ * place of the emit, a tail that reads the staging trajectory-major.
+ *   - `d` is drpo_rollout's descriptor, unchanged. vs .. vv, vptr and vcap are ignored
+ *     (NULL / 0 allowed): neither the virtual buffer nor its pointer is written. Every
+ *     other check of drpo_rollout applies. Fused engine only: H <= 128, engine 0 or 2,
+ *     recorded draws (eps_a / eps_m) in original-row layout (eps_layout 1).
+ *   - workspace: drpo_rollout_workspace_size(B, S, H) bytes.
+ *   - A row is alive at step 0, and at step t + 1 iff it was alive at t and not done
+ *     there; len[i] in 1..H counts its steps. Every output is optional (NULL skips it)
+ *     except len; every element of a given output is written, those at or beyond a
+ *     row's length as zero.
+ *   - ret[i] = sum_{t < len} weights[t] * rewards[i][t], accumulated in step order in
+ *     double without contraction and rounded to float32 once; hmax propagates NaN. */
+typedef struct {            /* all device pointers */
+  int32_t* len;             /* [B], required */
+  float* states;            /* [B][H+1][S]: [i][t] the state at the start of step t, [i][len] the last next state */
+  float* actions;           /* [B][H][A] */
+  float* rewards;           /* [B][H] */
+  float* constraint_values; /* [B][H][C] */
+  uint8_t* dones;           /* [B][H] */
+  uint8_t* violations;      /* [B][H] */
+  const double* weights;    /* [H] per-step weights of ret (discount^t); required iff ret != NULL; not written
+                               while the call runs */
+  float* ret;               /* [B] */
+  float* hmax;              /* [B][C]: max_{t < len} constraint_values[i][t][c] */
+  int32_t* first_violation; /* [B]: smallest t whose violation bit is set, -1 if none */
+  uint8_t* terminated;      /* [B]: the done bit of step len - 1; 0 = cut by the horizon */
+} drpo_rollout_traj_t;
+
+int drpo_rollout_trajectories(const drpo_rollout_desc_t* d /* host */, const drpo_rollout_traj_t* out /* host */,
+                              drpo_stream_t stream);
+
 /* batched env constraint functions, e.g. PointRobot.get_constraint_values /
  * check_violation / check_done (src/env/point_robot.py:96-131); h is [n][C] */
 int drpo_env_constraints(int env_id, int tracking_surr_start, int tracking_n_surr, double env_thr0,

@@ -1,0 +1,285 @@
+"""Imagined rollouts per trajectory (SMBPO.imagine, ops.rollout_trajectories,
+drpo_rollout_trajectories): the fused horizon kernel with the trajectory tail in place
+of the ordered emit.
+
+The scene of most tests is test_gpu_env_program._drifting_quadrotor_alg: B 72 (full
+tiles plus one of 8 rows), H 3, rows leaving at steps 0, 1 and 2 while others survive.
+Tolerances: against the buffer path and between calls everything is compared bit for bit
+(float32 as int32); against the oracle the tolerance of the rollout test this mirrors
+(2e-4); the actor's mean action at the project's forward tolerance 1e-4 + 1e-4 |ref|."""
+import numpy as np
+import pytest
+import torch
+
+import drpo_amd
+from drpo_amd import ops
+from gpu_helpers import DEV, COMP, close
+from oracle import drpo_oracle as O
+from test_gpu_env_program import (CustomEnv, EP, _drifting_quadrotor_alg, _no_host_env,  # noqa: F401
+                                  custom_oracle_env)
+from test_gpu_rollout import original_row_tape
+
+pytestmark = pytest.mark.gpu
+
+B, H = 72, 3
+TENSORS = ops.ImaginedRollout.TENSORS
+
+
+def flatten(im):
+    """The trajectories in the reference's order (src/smbpo.py:243-246): for t in 0..H-1,
+    the rows with length > t, in batch order. states[:, t] stands for the states and
+    states[:, t + 1] for the next states."""
+    length = im.lengths.cpu()
+    t_ = {k: getattr(im, k).cpu() for k in TENSORS}
+    rows = {k: [] for k in COMP}
+    for t in range(t_['rewards'].shape[1]):
+        keep = length > t
+        rows['states'].append(t_['states'][keep, t])
+        rows['next_states'].append(t_['states'][keep, t + 1])
+        for k in ('actions', 'rewards', 'constraint_values', 'dones', 'violations'):
+            rows[k].append(t_[k][keep, t])
+    return {k: torch.cat(v) for k, v in rows.items()}
+
+
+def bits(x):
+    x = x.detach().cpu()
+    return x.view(torch.int32) if x.dtype == torch.float32 else x
+
+
+def assert_same(a, b, names=TENSORS):
+    for k in names:
+        x, y = (getattr(a, k), getattr(b, k)) if not isinstance(a, dict) else (a[k], b[k])
+        assert x.dtype == y.dtype and x.shape == y.shape, k
+        assert torch.equal(bits(x), bits(y)), k
+
+
+@pytest.fixture(scope='module')
+def alg16():
+    return _drifting_quadrotor_alg(16)
+
+
+def _assert_every_length(im):
+    """Otherwise the scene shows nothing: rows of every length, ended and cut ones."""
+    length, term = im.lengths.cpu().numpy(), im.terminated.cpu().numpy().astype(bool)
+    assert set(length.tolist()) == {1, 2, 3}
+    assert term.any() and (~term).any()
+    assert (length[~term] == H).all()
+
+
+# ------------------------------------------------------------------ 1. the buffer path, bit for bit
+@pytest.mark.parametrize('rpt', [16, 32])
+def test_imagine_equals_rollout_bit_for_bit(rpt):
+    a, b = _drifting_quadrotor_alg(rpt), _drifting_quadrotor_alg(rpt)
+    out = a.rollout(a.actor, noise=drpo_amd.DeviceNoise(1234))
+    im = b.imagine(noise=drpo_amd.DeviceNoise(1234))
+    torch.cuda.synchronize()
+    _assert_every_length(im)
+    n, want = len(out), out.get(as_dict=True)
+    got = flatten(im)
+    assert int(im.lengths.sum()) == n == len(got['states'])
+    for k in COMP:
+        x, y = got[k], want[k].cpu().reshape(got[k].shape)
+        assert x.dtype == y.dtype, k
+        assert torch.equal(bits(x), bits(y)), k
+    assert len(b.virt_buffer) == 0
+
+
+# ------------------------------------------------------------------ 2. the oracle
+def test_trajectories_match_oracle_custom_program(monkeypatch, custom_oracle_env):
+    """The set-up of test_custom_program_rollout_matches_oracle (S 9, C 3, B 72, H 3, the
+    oracle's rollout with live RNG): the program route with C = 3, driven by the tape
+    re-indexed by original row."""
+    _no_host_env(monkeypatch)
+    torch.manual_seed(5)
+    cfg = drpo_amd.SMBPO.Config()
+    cfg.update({'horizon': H, 'rollout_batch_size': B, 'buffer_max': 20000})
+    alg = drpo_amd.SMBPO(cfg, lambda id=None: CustomEnv(), None, 1, device=DEV)
+    assert alg.env_params['env_id'] == 4 and (alg.state_dim, alg.con_dim) == (9, 3)
+    states = EP.custom_states()
+    N = len(states)
+    rng = np.random.RandomState(3)
+    rows = dict(states=states, actions=rng.uniform(-1, 1, (N, 2)).astype(np.float32), next_states=states,
+                rewards=rng.normal(0, 1, N).astype(np.float32), dones=np.zeros(N, bool), violations=np.zeros(N, bool),
+                constraint_values=np.zeros((N, 3), np.float32))
+    alg.replay_buffer.extend(**{k: torch.from_numpy(v).to(DEV) for k, v in rows.items()})
+    m = alg.model_ensemble
+    st = torch.from_numpy(states)
+    mean, std = O.normalizer_fit(st)
+    m.state_normalizer.mean.copy_(mean)
+    m.state_normalizer.std.copy_(std)
+    m._elite_inds = [3, 0, 6, 2, 5]
+    sd = {k: v.detach().cpu() for k, v in alg.state_dict().items()}
+    P = {k[len('solver.'):]: v for k, v in sd.items() if k.startswith('solver.actor.')}
+    P.update({k: v for k, v in sd.items() if k.startswith('model_ensemble.')})
+    live = O.LiveRNG()
+    ref = O.rollout(P, 'actor.net.', 'model_ensemble.', m._elite_inds, st, custom_oracle_env, B, H, live)
+    n = len(ref['states'])
+    assert B < n < B * H and bool(ref['dones'][:B].any())      # rows die, rows survive
+    tape = drpo_amd.TapeNoise(original_row_tape(live.entries, ref, B))
+    im = ops.rollout_trajectories(alg, alg.actor, None, tape)
+    torch.cuda.synchronize()
+    assert tape.done() and int(im.lengths.sum()) == n
+    got = flatten(im)
+    for k in COMP:
+        close(got[k], ref[k], tol=2e-4, msg=k)
+    assert len(alg.virt_buffer) == 0
+
+
+# ------------------------------------------------------------------ 3. summaries and padding
+@pytest.mark.parametrize('discount', [0.99, 1.0])
+def test_summaries_and_padding(alg16, discount):
+    alg = alg16
+    S, A, C = alg.state_dim, alg.action_dim, alg.con_dim
+    w = np.power(np.float64(discount), np.arange(H, dtype=np.float64))
+    nan = float('nan')
+
+    def full(shape, dtype, fill):
+        return torch.full(shape, fill, dtype=dtype, device=DEV)
+    out = {'states': full((B, H + 1, S), torch.float32, nan), 'actions': full((B, H, A), torch.float32, nan),
+           'rewards': full((B, H), torch.float32, nan), 'constraint_values': full((B, H, C), torch.float32, nan),
+           'dones': full((B, H), torch.uint8, 0xFF), 'violations': full((B, H), torch.uint8, 0xFF),
+           'lengths': full((B,), torch.int32, -99), 'returns': full((B,), torch.float32, nan),
+           'max_constraint': full((B, C), torch.float32, nan), 'first_violation': full((B,), torch.int32, -99),
+           'terminated': full((B,), torch.uint8, 0xFF)}
+    im = ops.rollout_trajectories(alg, alg.actor, None, drpo_amd.DeviceNoise(1234), weights=w, out=out)
+    torch.cuda.synchronize()
+    for k in TENSORS:
+        assert getattr(im, k) is out[k], k
+    _assert_every_length(im)
+    g = {k: out[k].cpu().numpy() for k in TENSORS}
+    for k in ('states', 'actions', 'rewards', 'constraint_values', 'returns', 'max_constraint'):
+        assert not np.isnan(g[k]).any(), k
+    for k in ('dones', 'violations', 'terminated'):
+        assert set(np.unique(g[k]).tolist()) <= {0, 1}, k
+
+    # the numpy restatement, over the returned trajectory tensors
+    length = np.empty(B, np.int32)
+    first = np.empty(B, np.int32)
+    term = np.empty(B, np.uint8)
+    hmax = np.empty((B, C), np.float32)
+    ret = np.empty(B, np.float32)
+    for i in range(B):
+        n = H
+        for t in range(H):
+            if g['dones'][i, t]:
+                n = t + 1
+                break
+        length[i] = n
+        v = np.flatnonzero(g['violations'][i, :n])
+        first[i] = v[0] if len(v) else -1
+        term[i] = g['dones'][i, n - 1]
+        hmax[i] = g['constraint_values'][i, :n].max(axis=0)
+        acc = np.float64(0.0)
+        for t in range(n):
+            acc = acc + w[t] * np.float64(g['rewards'][i, t])
+        ret[i] = np.float32(acc)
+        # everything at or beyond the length is exactly zero
+        assert not g['states'][i, n + 1:].any() and not g['actions'][i, n:].any()
+        assert not g['rewards'][i, n:].any() and not g['constraint_values'][i, n:].any()
+        assert not g['dones'][i, n:].any() and not g['violations'][i, n:].any()
+    np.testing.assert_array_equal(g['lengths'], length)
+    np.testing.assert_array_equal(g['first_violation'], first)
+    np.testing.assert_array_equal(g['terminated'], term)
+    np.testing.assert_array_equal(g['max_constraint'].view(np.int32), hmax.view(np.int32))
+    np.testing.assert_array_equal(g['returns'].view(np.int32), ret.view(np.int32))
+    assert (first >= 0).any() and (first < 0).any()
+    np.testing.assert_array_equal(im.mask.cpu().numpy(), np.arange(H)[None, :] < length[:, None])
+
+
+# ------------------------------------------------------------------ 4. small and odd shapes
+def test_small_and_odd_shapes(alg16, monkeypatch):
+    alg = alg16
+    S, A, C = alg.state_dim, alg.action_dim, alg.con_dim
+    replay = alg.replay_buffer.get('states')
+    s5 = replay[[0, 100, 200, 300, 399]].clone()
+    im = alg.imagine(states=s5, horizon=1, noise=drpo_amd.DeviceNoise(5))
+    torch.cuda.synchronize()
+    assert im.states.shape == (5, 2, S) and im.actions.shape == (5, 1, A) and im.rewards.shape == (5, 1)
+    assert im.constraint_values.shape == (5, 1, C) and im.max_constraint.shape == (5, C)
+    assert im.dones.shape == im.violations.shape == im.mask.shape == (5, 1)
+    assert torch.equal(bits(im.states[:, 0]), bits(s5))            # no replay sampling: row i is state i
+    assert (im.lengths == 1).all() and bool(im.mask.all())
+    assert torch.equal(im.terminated, im.dones[:, 0])
+    assert 0 < int(im.terminated.sum()) < 5                          # z = 1.6 leaves, z = 0.6 stays
+    # the constraint phase saw the next states
+    done, viol, h = alg.check_constraints(im.states[:, 1])
+    assert torch.equal(done, im.dones[:, 0]) and torch.equal(viol, im.violations[:, 0])
+    np.testing.assert_allclose(im.constraint_values[:, 0].cpu().numpy(), h.reshape(5, C).cpu().numpy(), rtol=0,
+                               atol=1e-6)
+    assert torch.equal(bits(im.max_constraint), bits(im.constraint_values[:, 0]))
+
+    s40 = replay[::10].clone()                                       # 40 rows: two full tiles and one of 8
+    m = int(alg.model_ensemble._elite_inds[1])
+    x = alg.imagine(states=s40, members=m, noise=drpo_amd.DeviceNoise(5))
+    y = alg.imagine(states=s40, members=[m] * H, noise=drpo_amd.DeviceNoise(5))
+    torch.cuda.synchronize()
+    assert x.states.shape == (40, H + 1, S) and x.members == y.members == [m] * H
+    assert set(x.lengths.cpu().tolist()) == {1, 2, 3}
+    assert_same(x, y)
+    with pytest.raises(ValueError, match='not a member index'):
+        alg.imagine(states=s40, members=alg.model_ensemble.ensemble_size)
+    with pytest.raises(ValueError, match='horizon 129'):
+        alg.imagine(states=s40, horizon=129)
+    monkeypatch.setattr(alg, 'env_params', None)             # an env on the host round trip
+    with pytest.raises(NotImplementedError, match='ConstraintProgram'):
+        alg.imagine(states=s40)
+
+
+# ------------------------------------------------------------------ 5. members='each'
+def test_members_each_equals_single_member_calls():
+    alg = _drifting_quadrotor_alg(16)
+    m = alg.model_ensemble
+    _, diff, _ = m.views()
+    bias = diff[-1][1]                       # a drift on z of its own per member: the members differ
+    E = m.ensemble_size
+    bias[..., 2] = 0.1 + 0.03 * torch.arange(E, device=DEV, dtype=torch.float32).reshape(E, *([1] * (bias.dim() - 2)))
+    m._elite_inds = [4, 1, 6, 0, 3]
+    im = alg.imagine(members='each', noise=drpo_amd.DeviceNoise(77))
+    torch.cuda.synchronize()
+    assert im.states.shape == (5, B, H + 1, alg.state_dim) and im.lengths.shape == (5, B)
+    assert im.mask.shape == (5, B, H)
+    assert not torch.equal(im.states[0], im.states[1])
+    assert torch.equal(bits(im.states[0][:, 0]), bits(im.states[1][:, 0]))    # common start states
+    for k, member in enumerate(m._elite_inds):
+        one = alg.imagine(members=member, noise=drpo_amd.DeviceNoise(77))
+        for name in TENSORS:
+            assert torch.equal(bits(getattr(im, name)[k]), bits(getattr(one, name))), (k, name)
+        assert im.members[k] == one.members == [member] * H
+
+
+# ------------------------------------------------------------------ 6. deterministic / model_noise, side effects
+def test_deterministic_model_noise_and_side_effects(alg16):
+    alg = alg16
+    alg.rollout(alg.actor, noise=drpo_amd.DeviceNoise(9))       # the buffer holds rows, its pointer is not 0
+    torch.cuda.synchronize()
+    vb = alg.virt_buffer._module
+    before = {f: getattr(vb, f).clone() for f in ops._VB_FIELDS}
+    n_before, steps_before = len(alg.virt_buffer), int(alg.steps_sampled)
+    assert n_before > 0
+    s40 = alg.replay_buffer.get('states')[::10].clone()
+    m = int(alg.model_ensemble._elite_inds[0])
+
+    im = alg.imagine(states=s40, deterministic=True, noise=drpo_amd.DeviceNoise(3))
+    torch.cuda.synchronize()
+    assert set(im.lengths.cpu().tolist()) == {1, 2, 3}
+    for t in range(H):
+        ref = alg.actor.act(im.states[:, t], eval=True)
+        live = im.mask[:, t]
+        err = (im.actions[:, t] - ref).abs()[live]
+        assert bool((err <= 1e-4 + 1e-4 * ref.abs()[live]).all()), (t, float(err.max()))
+
+    # no draw left: the seed does not matter (start states and member given, so that
+    # neither the replay sample nor the member choice depends on it)
+    x = alg.imagine(states=s40, members=m, deterministic=True, model_noise=False, noise=drpo_amd.DeviceNoise(1))
+    y = alg.imagine(states=s40, members=m, deterministic=True, model_noise=False, noise=drpo_amd.DeviceNoise(2))
+    assert_same(x, y)
+    z = alg.imagine(states=s40, members=m, noise=drpo_amd.DeviceNoise(1))
+    assert not torch.equal(z.states, x.states)
+
+    alg.imagine()                                   # replay start states, the private noise stream
+    alg.imagine(members='each', model_noise=False)
+    torch.cuda.synchronize()
+    for f in ops._VB_FIELDS:
+        assert torch.equal(getattr(vb, f), before[f]), f
+    assert len(alg.virt_buffer) == n_before and int(alg.steps_sampled) == steps_before
+
