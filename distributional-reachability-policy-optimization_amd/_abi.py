@@ -37,6 +37,11 @@ class RolloutTraj(ctypes.Structure):
                 ('first_violation', P), ('terminated', P)]
 
 
+class RolloutGiven(ctypes.Structure):
+    """drpo_rollout_given_t"""
+    _fields_ = [('actions', P), ('steps', c_int)]
+
+
 ENV_PROGRAM = 4          # DRPO_ENV_PROGRAM
 PROG_AFFINE, PROG_BALLS = 0, 1
 PROG_MAX_ROWS = PROG_MAX_TERMS = PROG_MAX_CENTRES = PROG_MAX_BOX = 8
@@ -101,6 +106,7 @@ PROTOTYPES = {
     'drpo_rollout_count_offset': (c_size_t, [c_int, c_int, c_int]),
     'drpo_rollout': (c_int, [POINTER(RolloutDesc), P]),
     'drpo_rollout_trajectories': (c_int, [POINTER(RolloutDesc), POINTER(RolloutTraj), P]),
+    'drpo_rollout_trajectories_given': (c_int, [POINTER(RolloutDesc), POINTER(RolloutGiven), POINTER(RolloutTraj), P]),
     'drpo_env_constraints': (c_int, [c_int, c_int, c_int, c_double, c_double, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_constraints_program': (c_int, [P, c_int, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_program_check': (c_int, [POINTER(EnvProgram), c_int]),

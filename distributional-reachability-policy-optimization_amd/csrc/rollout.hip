@@ -482,6 +482,10 @@ struct PersistArgs {
   // env id 4: the constraint program (device memory; read by the PG instantiations only).
   // Last, so that every other field keeps its kernarg offset.
   const void* env_prog;
+  // given actions [B][n_given][A], trajectory-major (read by the GA instantiations only):
+  // steps t < n_given take given[row][t] in place of the actor's sample. Appended likewise.
+  const float* given;
+  int n_given;
 };
 
 typedef const __attribute__((address_space(4))) PersistArgs* PersistArgsK;   // scalar (constant) loads
@@ -669,10 +673,14 @@ __device__ __forceinline__ void pair_split_heads(const float* in, int ldi, int N
 
 // This step's Gaussian draws into LDS: recorded (original-row layout) or the step
 // engine's Philox keys with the original row. Threads [first, first + count) work.
-template <int ROWS>
+// GA: at a step t < n_given the action slots take the row's given action instead of a
+// draw (the step then copies it, see the kernel); the draws are keyed by (row, step,
+// kind), so leaving one out shifts no other.
+template <int ROWS, bool GA = false>
 __device__ __forceinline__ void persist_noise(const float* eps_a, const float* eps_m, uint64_t seed, uint64_t ctr,
                                               int A, int S1, int B, int t, int row0, int nrows, float* nz_a,
-                                              float* nz_m, int first, int count) {
+                                              float* nz_m, int first, int count, const float* given = nullptr,
+                                              int n_given = 0) {
   const int NA4 = (A + 3) >> 2, NM4 = (S1 + 3) >> 2;
   const int total = ROWS * (NA4 + NM4);
   for (int base = 0; base < total; base += count) {   // uniform trip count, divergent body
@@ -680,6 +688,13 @@ __device__ __forceinline__ void persist_noise(const float* eps_a, const float* e
     if (i < base || i >= base + count || i >= total) continue;
     const int r = i / (NA4 + NM4), q = i - r * (NA4 + NM4);
     const uint32_t row = (uint32_t)(row0 + r);
+    if constexpr (GA) {
+      if (t < n_given && q < NA4) {
+        for (int d = 4 * q; d < min(A, 4 * q + 4); ++d)
+          nz_a[r * 8 + d] = r < nrows ? given[((size_t)row * n_given + t) * A + d] : 0.f;
+        continue;
+      }
+    }
     if (eps_a) {
       if (q < NA4) {
         for (int d = 4 * q; d < min(A, 4 * q + 4); ++d)
@@ -725,7 +740,11 @@ constexpr int PERSIST_L2_LDS = 3;
 // PG: the constraint phase (on the step's critical path) runs the program interpreter
 // (env id 4): instantiations of their own, the built-in environments' kernels keep
 // their code, registers and LDS. The program needs no LDS (scalar loads).
-template <int RB, int NW, bool LW, int PM, bool PG = false>
+// GA: given actions (drpo_rollout_trajectories_given). Steps t < n_given skip the actor
+// and take the row's action from memory, staged into nz_a by persist_noise one step
+// ahead like a recorded draw; later steps are the actor's. Instantiations of their own
+// again: the production kernels keep their code.
+template <int RB, int NW, bool LW, int PM, bool PG = false, bool GA = false>
 __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p) {
   constexpr int ROWS = RB * 16;
   constexpr int NT = NW * 64;
@@ -802,7 +821,12 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
     if (k < S) sraw[r * p.lds + k] = v;
   }
   if (tid < ROWS) alive[tid] = tid < nrows;
-  persist_noise<ROWS>(p.eps_a, p.eps_m, p.seed, p.ctr, A, S1, B, 0, row0, nrows, nz_a, nz_m, 0, NT);   // step 0's draws
+  // step 0's draws
+  if constexpr (GA)
+    persist_noise<ROWS, true>(p.eps_a, p.eps_m, p.seed, p.ctr, A, S1, B, 0, row0, nrows, nz_a, nz_m, 0, NT, p.given,
+                              p.n_given);
+  else
+  persist_noise<ROWS>(p.eps_a, p.eps_m, p.seed, p.ctr, A, S1, B, 0, row0, nrows, nz_a, nz_m, 0, NT);
   lds_barrier();
   }
   for (int t = 0; t < p.H; ++t) {
@@ -825,6 +849,10 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
     // constraint wave writes the next step's while the staging waves read these)
     int* alive_cur = (t & 1) ? flags : alive;
     int* alive_nxt = (t & 1) ? alive : flags;
+    // GA: a given step has no actor (workgroup-uniform, on a kernarg)
+    bool given_step = false;
+    if constexpr (GA) given_step = t < PARG(n_given);
+    if (!given_step) {
     // ---- actor MLP (src/policy.py:61-100) ------------------------------------
     if constexpr (LW) {
       tile_dense_impl<NW, RB, MAXC, ACT_RELU, 1, 1>(xin, ldx, S, step_opaque(PARG(aW1)),
@@ -848,10 +876,21 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
     static_assert(16 % NW == 0, "wave-local head hand-off needs NW | 16");
     wave_lds_sync();
     if (t == 2) RSTAMP(3);
+    }
     // ---- actor head + squashed Gaussian sample + model input [normalize(s), a]:
     //      the head's split-K partials are reduced by the threads that sample
     //      (one thread per (row, action dim) sums the mu and log-std columns) ----
     {
+      if (given_step) {
+        // the action as given (post-tanh, neither clamped nor squashed); 0 in the rows
+        // past a partial tile's last
+        if (tid < ROWS * A) {
+          const int r = tid / A, d = tid - r * A;
+          const float a = nz_a[r * 8 + d];
+          act[r * 8 + d] = a;
+          xin[r * ldx + S + d] = a;
+        }
+      } else {
       float bmu = 0.f, braw = 0.f;
       if (tid < ROWS * A) {   // ROWS * A <= NT (A <= 8)
         const int d = tid % A;
@@ -868,6 +907,7 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
         const float a = fast_tanh(nz_a[r * 8 + d] * fast_exp(ls) + mu);
         act[r * 8 + d] = a;
         xin[r * ldx + S + d] = a;
+      }
       }
       for (int e = tid; e < ROWS * S; e += NT) {
         const int r = e / S, k = e - r * S;
@@ -1004,6 +1044,10 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
         if (alive_cur[r]) PARG(st_a)[(sb + r) * A + d] = act[r * 8 + d];
       }
     } else if (t + 1 < PARG(H)) {
+      if constexpr (GA)
+        persist_noise<ROWS, true>(PARG(eps_a), PARG(eps_m), PARG(seed), PARG(ctr), A, S1, B, t + 1, row0, nrows, nz_a,
+                                  nz_m, NT / 2, NT / 2, PARG(given), PARG(n_given));
+      else
       persist_noise<ROWS>(PARG(eps_a), PARG(eps_m), PARG(seed), PARG(ctr), A, S1, B, t + 1, row0, nrows, nz_a, nz_m, NT / 2, NT / 2);
     }
     lds_barrier();
@@ -1387,18 +1431,29 @@ static size_t step_lds_bytes(int S, int A, int Ha, int Hm, int rpt, int nw, int 
 }
 
 // 8-wave workgroups (16 waves measured 3.5 % slower at config 2, profiles/r02/rollout_ab)
+template <int RB, bool LW, bool GA>
+static void launch_persist_ga(bool paired, bool pg, const PersistArgs& a, size_t lds_bytes, hipStream_t stream) {
+  auto k = paired ? (pg ? rollout_persist_kernel<RB, 8, LW, 1, true, GA>
+                        : rollout_persist_kernel<RB, 8, LW, 1, false, GA>)
+                  : (pg ? rollout_persist_kernel<RB, 8, LW, 0, true, GA>
+                        : rollout_persist_kernel<RB, 8, LW, 0, false, GA>);
+  k<<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
+}
+
+// a.n_given > 0: the given-actions instantiations
 template <int RB, bool LW>
 static void launch_persist(bool paired, bool pg, const PersistArgs& a, size_t lds_bytes, hipStream_t stream) {
-  auto k = paired ? (pg ? rollout_persist_kernel<RB, 8, LW, 1, true> : rollout_persist_kernel<RB, 8, LW, 1, false>)
-                  : (pg ? rollout_persist_kernel<RB, 8, LW, 0, true> : rollout_persist_kernel<RB, 8, LW, 0, false>);
-  k<<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
+  if (a.n_given > 0) launch_persist_ga<RB, LW, true>(paired, pg, a, lds_bytes, stream);
+  else launch_persist_ga<RB, LW, false>(paired, pg, a, lds_bytes, stream);
 }
 
 // engine 2's horizon kernel for either tail (`who`: the entry point, for its messages).
 // Fills `a`, which the tails read too. self_emit: the kernel copies the buffer pointer for
 // rollout_emit_self_kernel; without it the kernel touches neither the buffer nor its pointer.
+// given: actions for the first given->steps steps (nullptr or steps == 0: none).
 static int persist_run(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt, int64_t rlen, bool self_emit,
-                       const char* who, hipStream_t stream, PersistArgs& a) {
+                       const char* who, hipStream_t stream, PersistArgs& a,
+                       const drpo_rollout_given_t* given = nullptr) {
   DRPO_REQUIRE(d->H <= PERSIST_MAX_H, "%s: engine 2 supports horizon <= %d", who, PERSIST_MAX_H);
   const int S = d->S, A = d->A, S1 = d->S + 1, B = d->B, H = d->H;
   fill_shared_args(a, d, rlen);
@@ -1413,12 +1468,18 @@ static int persist_run(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt
   a.st_s = w.st_s; a.st_s2 = w.st_s2; a.st_a = w.st_a; a.st_r = w.st_r; a.st_h = w.st_h; a.st_dv = w.st_dv;
   a.cnt = w.st_cnt; a.inv = w.st_inv;
   for (int t = 0; t < H; ++t) a.members[t] = d->members[t];
+  if (given && given->steps > 0) {
+    a.given = given->actions;
+    a.n_given = given->steps;
+  }
 
   const size_t lds_bytes = persist_lds_bytes(S, A, d->Ha, d->Hm, rpt, 8);
   DRPO_REQUIRE(lds_bytes <= 160 * 1024, "%s: LDS %zu too large", who, lds_bytes);
   // LDS-resident actor weights (see rollout_persist_kernel) when they fit
   const size_t lw_bytes = sizeof(float) * (size_t)(32 + 16 * PERSIST_L2_LDS) * 256;
-  const bool lw = rpt == 16 && S <= 16 && d->Ha == 256 && 2 * A <= 16 && lds_bytes + lw_bytes <= 160 * 1024;
+  // (not when every step's action is given: the actor never runs)
+  const bool lw = rpt == 16 && S <= 16 && d->Ha == 256 && 2 * A <= 16 && lds_bytes + lw_bytes <= 160 * 1024 &&
+                  a.n_given < H;
   const bool paired = S1 <= 16 && d->Hm == 200;   // the kernel's PM specialisation
   const bool pg = d->env_id == DRPO_ENV_PROGRAM;
   if (self_emit) {
@@ -1574,10 +1635,8 @@ DRPO_API int drpo_rollout(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
 
 // The fused engine's horizon kernel + the trajectory tail: the rollout per original row
 // (row identity) instead of into the virtual buffer, which it never touches.
-DRPO_API int drpo_rollout_trajectories(const drpo_rollout_desc_t* d, const drpo_rollout_traj_t* out,
-                                       drpo_stream_t stream_) {
-  static const char who[] = "drpo_rollout_trajectories";
-  hipStream_t stream = (hipStream_t)stream_;
+static int rollout_trajectories(const drpo_rollout_desc_t* d, const drpo_rollout_given_t* given,
+                                const drpo_rollout_traj_t* out, const char* who, hipStream_t stream) {
   int rpt;
   int64_t rlen;
   if (const int rc = rollout_checks(d, who, false, rpt, rlen)) return rc;
@@ -1586,14 +1645,31 @@ DRPO_API int drpo_rollout_trajectories(const drpo_rollout_desc_t* d, const drpo_
                "%s: recorded draws must be indexed by original row (eps_layout 1), not compacted per step", who);
   DRPO_REQUIRE(out && out->len, "%s: null len (the one required output)", who);
   DRPO_REQUIRE(!out->ret || out->weights, "%s: ret needs weights", who);
+  if (given) {
+    DRPO_REQUIRE(given->steps >= 0 && given->steps <= d->H, "%s: given steps %d outside [0, horizon %d]", who,
+                 given->steps, d->H);
+    DRPO_REQUIRE(given->steps == 0 || given->actions, "%s: given steps %d need actions", who, given->steps);
+  }
   RolloutWs w;
   rollout_ws(d->B, d->S, d->H, reinterpret_cast<uintptr_t>(d->workspace), w);
   PersistArgs a{};
-  if (const int rc = persist_run(d, w, rpt, rlen, false, who, stream, a)) return rc;
+  if (const int rc = persist_run(d, w, rpt, rlen, false, who, stream, a, given)) return rc;
   const TrajArgs ta{d->S, d->A, d->C, d->B, d->H, w.st_s, w.st_s2, w.st_a, w.st_r, w.st_h, w.st_dv, *out};
   rollout_traj_kernel<<<(d->B + TRAJ_ROWS - 1) / TRAJ_ROWS, TRAJ_NT, 0, stream>>>(ta);
   DRPO_LAUNCH_CHECK("rollout_traj");
   return DRPO_OK;
+}
+
+DRPO_API int drpo_rollout_trajectories(const drpo_rollout_desc_t* d, const drpo_rollout_traj_t* out,
+                                       drpo_stream_t stream) {
+  return rollout_trajectories(d, nullptr, out, "drpo_rollout_trajectories", (hipStream_t)stream);
+}
+
+// The same under given actions: the first given->steps steps take their action from
+// memory instead of from the actor (the GA instantiations of rollout_persist_kernel).
+DRPO_API int drpo_rollout_trajectories_given(const drpo_rollout_desc_t* d, const drpo_rollout_given_t* given,
+                                             const drpo_rollout_traj_t* out, drpo_stream_t stream) {
+  return rollout_trajectories(d, given, out, "drpo_rollout_trajectories_given", (hipStream_t)stream);
 }
 
 __global__ void prp_kernel(int64_t* out, int64_t B, int64_t N, int hb, uint32_t k0, uint32_t k1, uint32_t k2,

@@ -230,13 +230,15 @@ class ImaginedRollout:
       mask [B, H] bool           t < lengths[i]
 
     Everything at or beyond a row's length is zero. ``members`` is the ensemble member
-    of each step. members='each' stacks the runs on a new leading axis."""
+    of each step. members='each' stacks the runs on a new leading axis. ``given_steps``:
+    the leading steps whose actions the caller gave (0: every action is the policy's)."""
     TENSORS = ('states', 'actions', 'rewards', 'constraint_values', 'dones', 'violations', 'lengths', 'returns',
                'max_constraint', 'first_violation', 'terminated')
 
-    def __init__(self, members, **tensors):
+    def __init__(self, members, given_steps=0, **tensors):
         assert set(tensors) == set(self.TENSORS)
         self.members = members
+        self.given_steps = given_steps
         self.__dict__.update(tensors)
 
     @property
@@ -246,7 +248,30 @@ class ImaginedRollout:
 
     @classmethod
     def stack(cls, runs):
-        return cls([r.members for r in runs], **{k: torch.stack([getattr(r, k) for r in runs]) for k in cls.TENSORS})
+        return cls([r.members for r in runs], runs[0].given_steps,
+                   **{k: torch.stack([getattr(r, k) for r in runs]) for k in cls.TENSORS})
+
+
+class ModelRolloutError:
+    """The k-step open-loop model error on real episode segments (SMBPO.model_rollout_error).
+    With n segments of k steps:
+
+      starts [n] int64       chronological replay index of each segment's first row
+      imagined               the ImaginedRollout from states[starts] under the segments' real actions
+      state_error [n, k]     || (imagined.states[:, t+1] - real next_states[starts+t]) / (state_std + 1e-7) ||_2
+      reward_error [n, k]    | imagined.rewards[:, t] - real rewards[starts+t] |
+      alive [n, k] bool      the imagined mask; both errors are NaN where it is False
+
+    members='each' adds a leading elite axis to everything but ``starts``."""
+
+    def __init__(self, starts, imagined, state_error, reward_error, alive):
+        self.starts, self.imagined = starts, imagined
+        self.state_error, self.reward_error, self.alive = state_error, reward_error, alive
+
+    def deciles(self, t):
+        """Deciles (0, 10, .., 100 %) of state_error[..., t] over the rows alive at step t."""
+        e = self.state_error[..., t][self.alive[..., t]]
+        return torch.quantile(e, torch.linspace(0, 1, 11, device=e.device, dtype=e.dtype))
 
 
 def _traj_static(alg, policy, B, H):
@@ -278,7 +303,7 @@ def _traj_members(model, members, H):
 
 
 def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, eps_a=None, eps_m=None, eps_layout=1,
-                         weights=None, out=None, horizon=None, ctr=None):
+                         weights=None, out=None, horizon=None, ctr=None, actions=None, timer=None):
     """One imagined rollout (src/smbpo.py:229-249) kept per trajectory: the fused horizon
     kernel and the trajectory tail (drpo_rollout_trajectories). Never touches
     alg.virt_buffer. Mirrors ``rollout``: the same start states, members and draws for
@@ -290,8 +315,14 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
     original row (eps_layout 1); a TapeNoise in that layout supplies its own. weights: H
     float64 per-step weights of ``returns`` (default ones). out: dict of preallocated
     tensors by ImaginedRollout name. horizon: default alg.horizon. ctr: the noise counter
-    (default: the next one of ``noise``)."""
-    from ._abi import RolloutTraj
+    (default: the next one of ``noise``).
+
+    actions: a contiguous float32 device tensor [B, K, A] (or [B, A]: K = 1), 1 <= K <=
+    horizon: steps 0 .. K-1 of trajectory i take actions[i, t] in place of the policy's
+    action, as given (post-tanh; neither clamped nor squashed), and the policy acts from
+    step K on (drpo_rollout_trajectories_given). No other draw moves. timer: an
+    EventTimer whose first pair brackets the horizon kernel."""
+    from ._abi import RolloutGiven, RolloutTraj
     L = _lib.lib()
     dev = alg.device
     B = alg.rollout_batch_size
@@ -303,6 +334,8 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
     model = alg.model_ensemble
     rb = alg.replay_buffer._module
     _lib.require_device(policy.group.data, model.group.data)
+    if actions is not None and noise.parity:
+        raise ValueError('actions with a recorded tape: a tape fixes the policy\'s draws')
 
     if initial_states is not None:
         src = initial_states.contiguous().float()
@@ -315,6 +348,21 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
         src, src_ptr, src_cap = rb._states, rb.pointer, rb.capacity
         idx = noise.np_choice(min(src_ptr, src_cap), B)
         init_idx = None if idx is None else _dev(idx, dev, torch.int64)
+
+    K = 0
+    if actions is not None:
+        if not torch.is_tensor(actions) or actions.dtype != torch.float32 or not actions.is_contiguous():
+            raise ValueError('actions: a contiguous float32 tensor [B, K, A] (or [B, A])')
+        _lib.require_device(actions)
+        if actions.dim() == 2:
+            actions = actions.unsqueeze(1)
+        if actions.dim() != 3 or actions.shape[2] != A:
+            raise ValueError(f'actions: shape {tuple(actions.shape)} is not [B, K, {A}]')
+        if actions.shape[0] != B:
+            raise ValueError(f'actions: {actions.shape[0]} rows for {B} trajectories')
+        K = actions.shape[1]
+        if not 1 <= K <= H:
+            raise ValueError(f'actions: {K} given steps, need 1 <= K <= horizon {H}')
 
     if noise.parity:
         assert members is None and eps_a is None and eps_m is None, 'a tape supplies its own members and draws'
@@ -366,7 +414,9 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
     d.seed, d.ctr = noise.seed, ctr
     d.rows_per_tile = getattr(alg, 'rows_per_tile', 0)
     d.engine, d.eps_layout = 2, (eps_layout if eps_a is not None else 0)
-    d.step_events = None
+    d.step_events = timer.events if timer is not None else None
+    if timer is not None:
+        timer.pairs = 1
     t = RolloutTraj()
     t.len, t.states, t.actions, t.rewards = (res[k].data_ptr() for k in ('lengths', 'states', 'actions', 'rewards'))
     t.constraint_values, t.dones, t.violations = (res[k].data_ptr() for k in ('constraint_values', 'dones',
@@ -374,8 +424,15 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
     t.weights = w.data_ptr()
     t.ret, t.hmax, t.first_violation, t.terminated = (res[k].data_ptr() for k in ('returns', 'max_constraint',
                                                                                   'first_violation', 'terminated'))
-    _lib.check(L.drpo_rollout_trajectories(ctypes.byref(d), ctypes.byref(t), _lib.stream()), 'rollout_trajectories')
-    return ImaginedRollout(mem, **res)
+    if K:
+        g = RolloutGiven()
+        g.actions, g.steps = actions.data_ptr(), K
+        _lib.check(L.drpo_rollout_trajectories_given(ctypes.byref(d), ctypes.byref(g), ctypes.byref(t), _lib.stream()),
+                   'rollout_trajectories_given')
+    else:
+        _lib.check(L.drpo_rollout_trajectories(ctypes.byref(d), ctypes.byref(t), _lib.stream()),
+                   'rollout_trajectories')
+    return ImaginedRollout(mem, K, **res)
 
 
 def rollout_host_env(alg, policy, initial_states, noise):

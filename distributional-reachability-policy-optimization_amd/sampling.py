@@ -109,3 +109,31 @@ def stat_forwards(solver, states, actions, distributional, mlp_multiplier):
     if mlp_multiplier:
         out['lam'] = solver.multiplier(states, safe_qcs)
     return out
+
+
+def episode_segments(states, next_states, dones, k):
+    """Chronological start indices (int64) of the k-step episode segments in a replay
+    buffer's rows: every i for which rows i .. i+k-1 are consecutive steps of one episode,
+    i.e. for each j < k-1 row i+j is not done and next_states[i+j] is bitwise states[i+j+1].
+    A reset after a done or after a time-out (which the buffer does not mark) therefore
+    breaks a segment. k = 1 returns every row. Pure torch, on the inputs' device."""
+    k = int(k)
+    if k < 1:
+        raise ValueError(f'segment length {k} must be >= 1')
+    n = len(states)
+    dev = states.device
+    if n < k:
+        return torch.empty(0, dtype=torch.int64, device=dev)
+    if k == 1:
+        return torch.arange(n, dtype=torch.int64, device=dev)
+
+    def bits(x):   # bitwise, so -0.0 != 0.0 and a NaN equals itself
+        x = x.reshape(n, -1).contiguous()
+        return x.view(torch.int32) if x.dtype == torch.float32 else x
+    a, b = bits(next_states), bits(states)
+    # link[i]: row i+1 continues row i's episode
+    link = (a[:-1] == b[1:]).all(dim=1) & ~dones.reshape(n)[:-1].to(torch.bool)
+    # a start needs k-1 links in a row: a window sum over the link flags
+    c = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), link.to(torch.int64).cumsum(0)])
+    run = c[k - 1:] - c[:n - k + 1]
+    return torch.nonzero(run == k - 1).reshape(-1)

@@ -254,7 +254,7 @@ class SMBPO(Configurable, Module):
     IMAGINE_SALT = 0x1A6E
 
     def imagine(self, states=None, policy=None, horizon=None, *, members=None, deterministic=False,
-                model_noise=True, discount=None, noise=None):
+                model_noise=True, discount=None, noise=None, actions=None):
         """What the model predicts happens from ``states`` under ``policy``: the rollout of
         src/smbpo.py:229-249 kept per trajectory (ops.ImaginedRollout: row i of every tensor
         is the trajectory from start state i), on the fused horizon kernel. Nothing of the
@@ -273,7 +273,13 @@ class SMBPO(Configurable, Module):
         noise      default a stream private to imagine, derived from the trainer's seed, so
                    the training stream is left alone. A given noise object is used the way
                    ``rollout`` uses it (imagine(noise=DeviceNoise(s)) is rollout(noise=
-                   DeviceNoise(s)) row for row) and advances by one counter."""
+                   DeviceNoise(s)) row for row) and advances by one counter.
+        actions    [B, K, A] (or [B, A]: K = 1), 1 <= K <= horizon: "from this state AND
+                   this action". Steps 0 .. K-1 of row i take actions[i, t] as given
+                   (post-tanh, as ImaginedRollout.actions holds them; not clamped); the
+                   policy acts from step K on, with the draws it would have had anyway.
+                   With K = horizon the policy is never evaluated. The result's
+                   ``given_steps`` is K."""
         from . import ops
         from .rng import _mix64
         if self.env_params is None:
@@ -293,11 +299,13 @@ class SMBPO(Configurable, Module):
         if states is not None:
             states = torch.as_tensor(states, dtype=torch.float32).to(self.device).reshape(-1, self.state_dim)
         B = self.rollout_batch_size if states is None else len(states)
+        if actions is not None:
+            actions = torch.as_tensor(actions, dtype=torch.float32).to(self.device).contiguous()
 
         each = isinstance(members, str)
         if each and members != 'each':
             raise ValueError(f"members: {members!r} (None, an int, {H} ints or 'each')")
-        kw = {}
+        kw = {} if actions is None else {'actions': actions}
         if each or deterministic or not model_noise:
             if noise.parity:
                 raise ValueError("a recorded tape fixes the members and the draws: no 'each', deterministic or "
@@ -411,6 +419,39 @@ class SMBPO(Configurable, Module):
         for i in range(self.model_cfg.ensemble_size):
             errors = torch.norm((predicted[i] - next_states) / (state_std + 1e-7), dim=1)
             log.message(f'Model {i + 1} error deciles: {deciles(errors)}')
+
+    def model_rollout_error(self, horizon, *, max_segments=None, members=None, model_noise=False, noise=None):
+        """The k-step open-loop model error on the real buffer (k = ``horizon``): the model
+        rolled forward from the first state of a real episode segment under the actions
+        the episode actually took, against the states it actually reached. One ``imagine``
+        call (given actions at every step, so the policy never runs) over at most
+        ``max_segments`` (default rollout_batch_size) of the buffer's k-step segments,
+        evenly spaced over their chronological list (no RNG). Returns an
+        ops.ModelRolloutError. Changes nothing of the training state and logs nothing."""
+        from . import ops
+        from .sampling import episode_segments
+        k = int(horizon)
+        s, a, s2, r, dn = self.replay_buffer.get('states', 'actions', 'next_states', 'rewards', 'dones',
+                                                 device=self.device)
+        starts = episode_segments(s, s2, dn, k)
+        if len(starts) == 0:
+            raise ValueError(f'the replay buffer ({len(s)} rows) holds no episode segment of {k} steps')
+        cap = self.rollout_batch_size if max_segments is None else int(max_segments)
+        if cap < 1:
+            raise ValueError(f'max_segments {cap} must be >= 1')
+        if len(starts) > cap:
+            pick = (torch.arange(cap, device=starts.device) * len(starts)) // cap
+            starts = starts[pick]
+        rows = starts.unsqueeze(1) + torch.arange(k, device=starts.device)       # [n, k]
+        im = self.imagine(states=s[starts], actions=a[rows].reshape(len(starts), k, self.action_dim), horizon=k,
+                          model_noise=model_noise, members=members, noise=noise)
+        state_std = s.std(dim=0)                   # as evaluate_models forms it
+        state_std[state_std < 1e-7] = 1.0
+        alive = im.mask
+        nan = torch.full((), float('nan'), device=self.device)
+        se = torch.norm((im.states[..., 1:, :] - s2[rows]) / (state_std + 1e-7), dim=-1)
+        re = (im.rewards - r[rows].reshape(len(starts), k)).abs()
+        return ops.ModelRolloutError(starts, im, torch.where(alive, se, nan), torch.where(alive, re, nan), alive)
 
     def _consume_chunk_draws(self, n, noise):
         """The reference's constraint_critic(sample=True) draws one randn_like per

@@ -179,6 +179,27 @@ typedef struct {            /* all device pointers */
 int drpo_rollout_trajectories(const drpo_rollout_desc_t* d /* host */, const drpo_rollout_traj_t* out /* host */,
                               drpo_stream_t stream);
 
+/* The imagined rollout (src/smbpo.py:229-249) from given (state, action) pairs: the
+ * first `steps` steps of trajectory i take actions[i][t] in place of the policy's
+ * action (src/smbpo.py:238, the actor.act call), later steps are the policy's again.
+ * The reference has no counterpart: its rollout always asks the actor.
+ *   - Everything of drpo_rollout_trajectories holds: its descriptor, outputs and checks.
+ *     given == NULL or steps == 0 is that call. steps < 0, steps > H, or steps > 0 with
+ *     NULL actions: DRPO_EINVAL before any launch.
+ *   - An action is used as given, neither clamped nor squashed: pass post-tanh actions,
+ *     as drpo_rollout_traj_t.actions holds them (whose layout `actions` shares).
+ *   - The draws are keyed by (row, step, kind): a given step makes no action draw and
+ *     shifts no other, so every model draw and every later action draw is the one the
+ *     call without `given` makes. With steps == H the actor is never evaluated. */
+typedef struct {
+  const float* actions;   /* device [B][steps][A], trajectory-major; not written while the call runs */
+  int steps;              /* K: steps 0 .. K-1 take actions[i][t] in place of the policy's action; 1 <= K <= H */
+} drpo_rollout_given_t;
+
+int drpo_rollout_trajectories_given(const drpo_rollout_desc_t* d /* host */,
+                                    const drpo_rollout_given_t* given /* host; NULL or steps == 0: none */,
+                                    const drpo_rollout_traj_t* out /* host */, drpo_stream_t stream);
+
 /* batched env constraint functions, e.g. PointRobot.get_constraint_values /
  * check_violation / check_done (src/env/point_robot.py:96-131); h is [n][C] */
 int drpo_env_constraints(int env_id, int tracking_surr_start, int tracking_n_surr, double env_thr0,
