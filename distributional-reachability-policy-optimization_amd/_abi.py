@@ -42,6 +42,16 @@ class RolloutGiven(ctypes.Structure):
     _fields_ = [('actions', P), ('steps', c_int)]
 
 
+class RolloutShield(ctypes.Structure):
+    """drpo_rollout_shield_t"""
+    _fields_ = [('sW1', P), ('sb1', P), ('sW2', P), ('sb2', P), ('sW3', P), ('sb3', P),
+                ('cW1', P), ('cb1', P), ('cW2', P), ('cb2', P), ('qW1', P), ('qb1', P), ('qW2', P), ('qb2', P),
+                ('zW1', P), ('zb1', P), ('zW2', P), ('zb2', P),
+                ('Hc', c_int), ('Cq', c_int), ('distributional', c_int),
+                ('std_ratio', c_float), ('log_std_min', c_float), ('log_std_max', c_float), ('threshold', c_float),
+                ('interventions', P), ('certificate', P)]
+
+
 ENV_PROGRAM = 4          # DRPO_ENV_PROGRAM
 PROG_AFFINE, PROG_BALLS = 0, 1
 PROG_MAX_ROWS = PROG_MAX_TERMS = PROG_MAX_CENTRES = PROG_MAX_BOX = 8
@@ -107,6 +117,8 @@ PROTOTYPES = {
     'drpo_rollout': (c_int, [POINTER(RolloutDesc), P]),
     'drpo_rollout_trajectories': (c_int, [POINTER(RolloutDesc), POINTER(RolloutTraj), P]),
     'drpo_rollout_trajectories_given': (c_int, [POINTER(RolloutDesc), POINTER(RolloutGiven), POINTER(RolloutTraj), P]),
+    'drpo_rollout_trajectories_shielded': (c_int, [POINTER(RolloutDesc), POINTER(RolloutShield), POINTER(RolloutTraj),
+                                                   P]),
     'drpo_env_constraints': (c_int, [c_int, c_int, c_int, c_double, c_double, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_constraints_program': (c_int, [P, c_int, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_program_check': (c_int, [POINTER(EnvProgram), c_int]),

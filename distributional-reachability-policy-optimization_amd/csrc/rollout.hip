@@ -66,6 +66,7 @@ extern "C" __attribute__((visibility("default"))) int drpo_debug_stamps_rollout(
 #include "common.hpp"
 #include "env_constraints.hpp"
 #include "prp.hpp"
+#include "sac_rows.hpp"
 
 using namespace drpo;
 
@@ -486,6 +487,15 @@ struct PersistArgs {
   // steps t < n_given take given[row][t] in place of the actor's sample. Appended likewise.
   const float* given;
   int n_given;
+  // the shield (read by the SH instantiations only; appended likewise). Safe actor (the
+  // actor's shape) and constraint critic: packed mirrors + biases. cW: trunk, qW: mean
+  // head, zW: log-std head (null when !sh_dist). cW1 != null selects the SH kernels.
+  const float *sW1, *sb1, *sW2, *sb2, *sW3, *sb3;
+  const float *cW1, *cb1, *cW2, *cb2, *qW1, *qb1, *qW2, *qb2, *zW1, *zb1, *zW2, *zb2;
+  int Hc, Cq, sh_dist;
+  float sh_ratio, sh_lmin, sh_lmax, sh_thr;
+  uint8_t* sh_iv;     // [B][H] or null
+  float* sh_cert;     // [B][H] or null
 };
 
 typedef const __attribute__((address_space(4))) PersistArgs* PersistArgsK;   // scalar (constant) loads
@@ -744,7 +754,13 @@ constexpr int PERSIST_L2_LDS = 3;
 // and take the row's action from memory, staged into nz_a by persist_noise one step
 // ahead like a recorded draw; later steps are the actor's. Instantiations of their own
 // again: the production kernels keep their code.
-template <int RB, int NW, bool LW, int PM, bool PG = false, bool GA = false>
+// SH: the safety shield of the real-environment controller (src/smbpo.py:124-136) inside
+// the step (drpo_rollout_trajectories_shielded). Between the actor's sample and the
+// member's normalisation, while xin still holds [s_raw, a]: the constraint critic's
+// certificate of (s, a) (cc_bound_row), the decision certificate > threshold, the safe
+// actor's mean action for the tiles with an intervening row, and the select into act /
+// xin. No draw is made or moved. Instantiations of their own once more.
+template <int RB, int NW, bool LW, int PM, bool PG = false, bool GA = false, bool SH = false>
 __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p) {
   constexpr int ROWS = RB * 16;
   constexpr int NT = NW * 64;
@@ -908,6 +924,88 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
         act[r * 8 + d] = a;
         xin[r * ldx + S + d] = a;
       }
+      }
+      if constexpr (SH) {
+        // ---- the shield (src/smbpo.py:124-136) on [s_raw, a]: xin's states are still raw.
+        //      All weights streamed from the packed mirrors; h1 / h2 / h3, dout / lout and
+        //      red are free between the actor and the member ----
+        lds_barrier();   // act / xin[.., S + d] of every row; the sampling threads are done with red
+        const int Hc = PARG(Hc), Cq = PARG(Cq);
+        const bool dist = PARG(sh_dist) != 0;
+        // 1. certificate: the constraint critic's trunk [S+A -> Hc -> Hc] (ReLU, ReLU
+        //    output), the heads [Hc -> Hc -> Cq] (src/ssac.py:64-92)
+        tile_dense<NW, RB, MAXC, ACT_RELU>(xin, ldx, S + A, step_opaque(PARG(cW1)), step_opaque(PARG(cb1)), Hc, h1,
+                                           ldh);
+        lds_barrier();
+        tile_dense<NW, RB, MAXC, ACT_RELU>(h1, ldh, Hc, step_opaque(PARG(cW2)), step_opaque(PARG(cb2)), Hc, h2, ldh);
+        lds_barrier();
+        // the heads' hidden layers: mean -> h3, log-std -> h1 (the trunk is done with it)
+        tile_dense<NW, RB, MAXC, ACT_RELU>(h2, ldh, Hc, step_opaque(PARG(qW1)), step_opaque(PARG(qb1)), Hc, h3, ldh);
+        if (dist)
+          tile_dense<NW, RB, MAXC, ACT_RELU>(h2, ldh, Hc, step_opaque(PARG(zW1)), step_opaque(PARG(zb1)), Hc, h1,
+                                             ldh);
+        lds_barrier();
+        // the output layers one after the other through the one set of narrow partials
+        // (ROWS * Cq <= NT: Cq <= 8): mu -> dout, raw log-std -> lout
+        {
+          float bq = 0.f;
+          if (tid < ROWS * Cq) bq = gload(step_opaque(PARG(qb2)) + tid % Cq);
+          tile_dense_narrow_partials<NW, RB>(h3, ldh, Hc, step_opaque(PARG(qW2)), red);
+          if (tid < ROWS * Cq) {
+            const int r = tid / Cq, c = tid - r * Cq;
+            dout[r * ldm + c] = narrow_sum<NW, RB>(red, r, c) + bq;
+          }
+          lds_barrier();
+        }
+        if (dist) {
+          float bz = 0.f;
+          if (tid < ROWS * Cq) bz = gload(step_opaque(PARG(zb2)) + tid % Cq);
+          tile_dense_narrow_partials<NW, RB>(h1, ldh, Hc, step_opaque(PARG(zW2)), red);
+          if (tid < ROWS * Cq) {
+            const int r = tid / Cq, c = tid - r * Cq;
+            lout[r * ldm + c] = narrow_sum<NW, RB>(red, r, c) + bz;
+          }
+          lds_barrier();
+        }
+        // 2. decision (wave 0, one lane per row): the float comparison of
+        //    drpo_shield_select mode 1; the tile's intervening rows as a bit mask in LDS
+        if (tid < 64) {
+          bool iv = false;
+          if (tid < ROWS && alive_cur[tid]) {
+            const float* mu = dout + tid * ldm;
+            const float* ls = lout + tid * ldm;
+            const CcBound b = cc_bound_row([&](int c) { return mu[c]; }, [&](int c) { return ls[c]; }, Cq, dist,
+                                           PARG(sh_ratio), PARG(sh_lmin), PARG(sh_lmax));
+            iv = b.best > PARG(sh_thr);
+            const size_t o = (size_t)(row0 + tid) * PARG(H) + t;   // alive: row0 + tid < B
+            if (PARG(sh_cert)) PARG(sh_cert)[o] = b.best;
+            if (PARG(sh_iv)) PARG(sh_iv)[o] = iv ? 1 : 0;
+          }
+          const uint64_t ivk = __ballot(iv);
+          if (tid == 0) s_nalive[1] = (int)(uint32_t)ivk;   // ROWS <= 32
+        }
+        lds_barrier();
+        const unsigned ivm = (unsigned)__builtin_amdgcn_readfirstlane(s_nalive[1]);
+        // 3. safe actor (the actor's shape), only in a tile with an intervening row: the
+        //    test is workgroup-uniform, so every barrier below is reached by all waves or none
+        if (ivm != 0u) {
+          tile_dense<NW, RB, MAXC, ACT_RELU>(xin, ldx, S, step_opaque(PARG(sW1)), step_opaque(PARG(sb1)), Ha, h1, ldh);
+          lds_barrier();
+          tile_dense<NW, RB, MAXC, ACT_RELU>(h1, ldh, Ha, step_opaque(PARG(sW2)), step_opaque(PARG(sb2)), Ha, h2, ldh);
+          lds_barrier();
+          float bmu = 0.f;
+          if (tid < ROWS * A) bmu = gload(step_opaque(PARG(sb3)) + tid % A);
+          tile_dense_narrow_partials<NW, RB>(h2, ldh, Ha, step_opaque(PARG(sW3)), red);
+          // 4. select: a_safe = tanh(mu_safe) (the squashing of the actor's sample, no draw)
+          if (tid < ROWS * A) {
+            const int r = tid / A, d = tid - r * A;
+            if ((ivm >> r) & 1u) {
+              const float a = fast_tanh(narrow_sum<NW, RB>(red, r, d) + bmu);
+              act[r * 8 + d] = a;
+              xin[r * ldx + S + d] = a;
+            }
+          }
+        }
       }
       for (int e = tid; e < ROWS * S; e += NT) {
         const int r = e / S, k = e - r * S;
@@ -1440,10 +1538,21 @@ static void launch_persist_ga(bool paired, bool pg, const PersistArgs& a, size_t
   k<<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
 }
 
-// a.n_given > 0: the given-actions instantiations
+// the shield instantiations (GA = false: given actions and the shield do not combine)
+template <int RB, bool LW>
+static void launch_persist_sh(bool paired, bool pg, const PersistArgs& a, size_t lds_bytes, hipStream_t stream) {
+  auto k = paired ? (pg ? rollout_persist_kernel<RB, 8, LW, 1, true, false, true>
+                        : rollout_persist_kernel<RB, 8, LW, 1, false, false, true>)
+                  : (pg ? rollout_persist_kernel<RB, 8, LW, 0, true, false, true>
+                        : rollout_persist_kernel<RB, 8, LW, 0, false, false, true>);
+  k<<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
+}
+
+// a.cW1: the shield instantiations; a.n_given > 0: the given-actions instantiations
 template <int RB, bool LW>
 static void launch_persist(bool paired, bool pg, const PersistArgs& a, size_t lds_bytes, hipStream_t stream) {
-  if (a.n_given > 0) launch_persist_ga<RB, LW, true>(paired, pg, a, lds_bytes, stream);
+  if (a.cW1) launch_persist_sh<RB, LW>(paired, pg, a, lds_bytes, stream);
+  else if (a.n_given > 0) launch_persist_ga<RB, LW, true>(paired, pg, a, lds_bytes, stream);
   else launch_persist_ga<RB, LW, false>(paired, pg, a, lds_bytes, stream);
 }
 
@@ -1451,9 +1560,10 @@ static void launch_persist(bool paired, bool pg, const PersistArgs& a, size_t ld
 // Fills `a`, which the tails read too. self_emit: the kernel copies the buffer pointer for
 // rollout_emit_self_kernel; without it the kernel touches neither the buffer nor its pointer.
 // given: actions for the first given->steps steps (nullptr or steps == 0: none).
+// shield: the safety shield inside the step (checked by the caller; not together with given).
 static int persist_run(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt, int64_t rlen, bool self_emit,
                        const char* who, hipStream_t stream, PersistArgs& a,
-                       const drpo_rollout_given_t* given = nullptr) {
+                       const drpo_rollout_given_t* given = nullptr, const drpo_rollout_shield_t* shield = nullptr) {
   DRPO_REQUIRE(d->H <= PERSIST_MAX_H, "%s: engine 2 supports horizon <= %d", who, PERSIST_MAX_H);
   const int S = d->S, A = d->A, S1 = d->S + 1, B = d->B, H = d->H;
   fill_shared_args(a, d, rlen);
@@ -1472,8 +1582,22 @@ static int persist_run(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt
     a.given = given->actions;
     a.n_given = given->steps;
   }
+  // the critic's hidden activations share h1 - h3 with the actor's and the member's
+  int Hw = d->Ha;
+  if (shield) {
+    const drpo_rollout_shield_t& s = *shield;
+    a.sW1 = s.sW1; a.sb1 = s.sb1; a.sW2 = s.sW2; a.sb2 = s.sb2; a.sW3 = s.sW3; a.sb3 = s.sb3;
+    a.cW1 = s.cW1; a.cb1 = s.cb1; a.cW2 = s.cW2; a.cb2 = s.cb2;
+    a.qW1 = s.qW1; a.qb1 = s.qb1; a.qW2 = s.qW2; a.qb2 = s.qb2;
+    a.zW1 = s.zW1; a.zb1 = s.zb1; a.zW2 = s.zW2; a.zb2 = s.zb2;
+    a.Hc = s.Hc; a.Cq = s.Cq; a.sh_dist = s.distributional ? 1 : 0;
+    a.sh_ratio = s.std_ratio; a.sh_lmin = s.log_std_min; a.sh_lmax = s.log_std_max; a.sh_thr = s.threshold;
+    a.sh_iv = s.interventions; a.sh_cert = s.certificate;
+    if (s.Hc > Hw) Hw = s.Hc;
+    a.ldh = lds_ld(Hw > d->Hm ? Hw : d->Hm);
+  }
 
-  const size_t lds_bytes = persist_lds_bytes(S, A, d->Ha, d->Hm, rpt, 8);
+  const size_t lds_bytes = persist_lds_bytes(S, A, Hw, d->Hm, rpt, 8);
   DRPO_REQUIRE(lds_bytes <= 160 * 1024, "%s: LDS %zu too large", who, lds_bytes);
   // LDS-resident actor weights (see rollout_persist_kernel) when they fit
   const size_t lw_bytes = sizeof(float) * (size_t)(32 + 16 * PERSIST_L2_LDS) * 256;
@@ -1485,6 +1609,13 @@ static int persist_run(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt
   if (self_emit) {
     a.vptr_in = d->vptr;
     a.base_slot = w.off + H + 1;
+  }
+  if (shield) {
+    // after every refusal: the kernel's rows write their own steps, zero at and beyond a
+    // row's length comes from here
+    const size_t BH = (size_t)B * H;
+    if (shield->interventions) DRPO_CHECK_HIP(hipMemsetAsync(shield->interventions, 0, BH, stream));
+    if (shield->certificate) DRPO_CHECK_HIP(hipMemsetAsync(shield->certificate, 0, BH * sizeof(float), stream));
   }
   if (d->step_events) hipEventRecord((hipEvent_t)d->step_events[0], stream);
   if (rpt == 32) launch_persist<2, false>(paired, pg, a, lds_bytes, stream);
@@ -1636,10 +1767,27 @@ DRPO_API int drpo_rollout(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
 // The fused engine's horizon kernel + the trajectory tail: the rollout per original row
 // (row identity) instead of into the virtual buffer, which it never touches.
 static int rollout_trajectories(const drpo_rollout_desc_t* d, const drpo_rollout_given_t* given,
-                                const drpo_rollout_traj_t* out, const char* who, hipStream_t stream) {
+                                const drpo_rollout_shield_t* shield, const drpo_rollout_traj_t* out, const char* who,
+                                hipStream_t stream) {
+  if (shield) {
+    // the shapes the SH instantiations run; anything else is refused, never run another way
+    const drpo_rollout_shield_t& s = *shield;
+    DRPO_REQUIRE(s.Hc >= 1 && s.Hc <= 256, "%s: shield critic hidden width %d outside 1..256", who, s.Hc);
+    DRPO_REQUIRE(s.Cq >= 1 && s.Cq <= 8, "%s: shield critic outputs %d outside 1..8", who, s.Cq);
+    DRPO_REQUIRE(s.sW1 && s.sb1 && s.sW2 && s.sb2 && s.sW3 && s.sb3, "%s: shield with a null safe-actor pointer", who);
+    DRPO_REQUIRE(s.cW1 && s.cb1 && s.cW2 && s.cb2 && s.qW1 && s.qb1 && s.qW2 && s.qb2,
+                 "%s: shield with a null critic trunk / mean head pointer", who);
+    DRPO_REQUIRE(!s.distributional || (s.zW1 && s.zb1 && s.zW2 && s.zb2),
+                 "%s: distributional shield needs the log-std head", who);
+  }
   int rpt;
   int64_t rlen;
   if (const int rc = rollout_checks(d, who, false, rpt, rlen)) return rc;
+  // the wider of the actor's and the critic's hidden layers sizes the tile: an automatic
+  // 32-row tile that no longer fits falls back to 16 rows (a requested one is refused below)
+  if (shield && !d->rows_per_tile && rpt == 32 &&
+      persist_lds_bytes(d->S, d->A, d->Ha > shield->Hc ? d->Ha : shield->Hc, d->Hm, 32, 8) > 160 * 1024)
+    rpt = 16;
   DRPO_REQUIRE(d->engine != 1, "%s: runs the fused engine only (engine 0 or 2, not 1)", who);
   DRPO_REQUIRE(!(d->eps_a && d->eps_layout == 0),
                "%s: recorded draws must be indexed by original row (eps_layout 1), not compacted per step", who);
@@ -1653,7 +1801,7 @@ static int rollout_trajectories(const drpo_rollout_desc_t* d, const drpo_rollout
   RolloutWs w;
   rollout_ws(d->B, d->S, d->H, reinterpret_cast<uintptr_t>(d->workspace), w);
   PersistArgs a{};
-  if (const int rc = persist_run(d, w, rpt, rlen, false, who, stream, a, given)) return rc;
+  if (const int rc = persist_run(d, w, rpt, rlen, false, who, stream, a, given, shield)) return rc;
   const TrajArgs ta{d->S, d->A, d->C, d->B, d->H, w.st_s, w.st_s2, w.st_a, w.st_r, w.st_h, w.st_dv, *out};
   rollout_traj_kernel<<<(d->B + TRAJ_ROWS - 1) / TRAJ_ROWS, TRAJ_NT, 0, stream>>>(ta);
   DRPO_LAUNCH_CHECK("rollout_traj");
@@ -1662,14 +1810,21 @@ static int rollout_trajectories(const drpo_rollout_desc_t* d, const drpo_rollout
 
 DRPO_API int drpo_rollout_trajectories(const drpo_rollout_desc_t* d, const drpo_rollout_traj_t* out,
                                        drpo_stream_t stream) {
-  return rollout_trajectories(d, nullptr, out, "drpo_rollout_trajectories", (hipStream_t)stream);
+  return rollout_trajectories(d, nullptr, nullptr, out, "drpo_rollout_trajectories", (hipStream_t)stream);
 }
 
 // The same under given actions: the first given->steps steps take their action from
 // memory instead of from the actor (the GA instantiations of rollout_persist_kernel).
 DRPO_API int drpo_rollout_trajectories_given(const drpo_rollout_desc_t* d, const drpo_rollout_given_t* given,
                                              const drpo_rollout_traj_t* out, drpo_stream_t stream) {
-  return rollout_trajectories(d, given, out, "drpo_rollout_trajectories_given", (hipStream_t)stream);
+  return rollout_trajectories(d, given, nullptr, out, "drpo_rollout_trajectories_given", (hipStream_t)stream);
+}
+
+// The same under the shielded controller (src/smbpo.py:124-136): the SH instantiations of
+// rollout_persist_kernel. shield == nullptr is drpo_rollout_trajectories.
+DRPO_API int drpo_rollout_trajectories_shielded(const drpo_rollout_desc_t* d, const drpo_rollout_shield_t* shield,
+                                                const drpo_rollout_traj_t* out, drpo_stream_t stream) {
+  return rollout_trajectories(d, nullptr, shield, out, "drpo_rollout_trajectories_shielded", (hipStream_t)stream);
 }
 
 __global__ void prp_kernel(int64_t* out, int64_t B, int64_t N, int hb, uint32_t k0, uint32_t k1, uint32_t k2,

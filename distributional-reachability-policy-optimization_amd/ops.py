@@ -231,7 +231,12 @@ class ImaginedRollout:
 
     Everything at or beyond a row's length is zero. ``members`` is the ensemble member
     of each step. members='each' stacks the runs on a new leading axis. ``given_steps``:
-    the leading steps whose actions the caller gave (0: every action is the policy's)."""
+    the leading steps whose actions the caller gave (0: every action is the policy's).
+
+    Under the shield (imagine(shield=)) three attributes are set, None otherwise:
+      interventions [B, H] bool  the step took the safe actor's action
+      certificate [B, H]         the constraint critic's certificate of the actor's action
+      shield_threshold           the threshold the certificate was compared with"""
     TENSORS = ('states', 'actions', 'rewards', 'constraint_values', 'dones', 'violations', 'lengths', 'returns',
                'max_constraint', 'first_violation', 'terminated')
 
@@ -239,6 +244,7 @@ class ImaginedRollout:
         assert set(tensors) == set(self.TENSORS)
         self.members = members
         self.given_steps = given_steps
+        self.interventions = self.certificate = self.shield_threshold = None
         self.__dict__.update(tensors)
 
     @property
@@ -248,8 +254,13 @@ class ImaginedRollout:
 
     @classmethod
     def stack(cls, runs):
-        return cls([r.members for r in runs], runs[0].given_steps,
-                   **{k: torch.stack([getattr(r, k) for r in runs]) for k in cls.TENSORS})
+        out = cls([r.members for r in runs], runs[0].given_steps,
+                  **{k: torch.stack([getattr(r, k) for r in runs]) for k in cls.TENSORS})
+        if runs[0].interventions is not None:
+            out.interventions = torch.stack([r.interventions for r in runs])
+            out.certificate = torch.stack([r.certificate for r in runs])
+            out.shield_threshold = runs[0].shield_threshold
+        return out
 
 
 class ModelRolloutError:
@@ -289,6 +300,43 @@ def _traj_static(alg, policy, B, H):
     return hit
 
 
+def _shield_desc(alg, policy, B, H, threshold):
+    """drpo_rollout_shield_t of alg's shield: alg.actor_safe, alg.constraint_critic (with
+    the solver's distributional_qc), fresh [B, H] outputs. Refuses what the kernels do not
+    run. Returns (descriptor, (interventions uint8, certificate))."""
+    from ._abi import RolloutShield
+    safe, cc = alg.actor_safe, alg.constraint_critic
+    dist = bool(alg.solver.distributional_qc)
+    if safe.spec.dims != policy.spec.dims:
+        raise ValueError(f'shield: the safe actor\'s layers {safe.spec.dims} are not the policy\'s {policy.spec.dims}')
+    Hc, Cq = cc.hidden_dim, cc.output_dim
+    if cc.trunk_layers != 2 or cc.head_layers != 1:
+        raise ValueError(f'shield: the kernels run the reference\'s ConstraintCritic (trunk_layers 2, head_layers 1), '
+                         f'not {cc.trunk_layers} / {cc.head_layers}')
+    if not (1 <= Hc <= 256 and 1 <= Cq <= 8):
+        raise ValueError(f'shield: constraint critic hidden width {Hc} / outputs {Cq} outside 1..256 / 1..8')
+    _lib.require_device(safe.group.data, cc.group.data)
+    safe.group.ensure_packed()
+    cc.group.ensure_packed()
+
+    def views(g, prefix, n):
+        return [x for i in range(n) for x in (g.pview(f'{prefix}{2 * i}.weight')[0].data_ptr(),
+                                              g.view(f'{prefix}{2 * i}.bias').data_ptr())]
+    sh = RolloutShield()
+    sh.sW1, sh.sb1, sh.sW2, sh.sb2, sh.sW3, sh.sb3 = views(safe.group, 'net.', 3)
+    sh.cW1, sh.cb1, sh.cW2, sh.cb2 = views(cc.group, cc.prefix + 'trunk.', 2)
+    sh.qW1, sh.qb1, sh.qW2, sh.qb2 = views(cc.group, cc.prefix + 'mean_head.', 2)
+    if dist:
+        sh.zW1, sh.zb1, sh.zW2, sh.zb2 = views(cc.group, cc.prefix + 'log_std_head.', 2)
+    sh.Hc, sh.Cq, sh.distributional = Hc, Cq, int(dist)
+    sh.std_ratio, sh.log_std_min, sh.log_std_max = float(cc.std_ratio), float(cc.log_std_min), float(cc.log_std_max)
+    sh.threshold = threshold
+    dev = alg.device
+    keep = (torch.empty(B, H, dtype=torch.uint8, device=dev), torch.empty(B, H, dtype=torch.float32, device=dev))
+    sh.interventions, sh.certificate = keep[0].data_ptr(), keep[1].data_ptr()
+    return sh, keep
+
+
 def _traj_members(model, members, H):
     """members as an int (every step) or a sequence of H ints, checked against the
     ensemble size here: the descriptor does not carry it."""
@@ -303,7 +351,7 @@ def _traj_members(model, members, H):
 
 
 def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, eps_a=None, eps_m=None, eps_layout=1,
-                         weights=None, out=None, horizon=None, ctr=None, actions=None, timer=None):
+                         weights=None, out=None, horizon=None, ctr=None, actions=None, timer=None, shield=None):
     """One imagined rollout (src/smbpo.py:229-249) kept per trajectory: the fused horizon
     kernel and the trajectory tail (drpo_rollout_trajectories). Never touches
     alg.virt_buffer. Mirrors ``rollout``: the same start states, members and draws for
@@ -321,7 +369,15 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
     horizon: steps 0 .. K-1 of trajectory i take actions[i, t] in place of the policy's
     action, as given (post-tanh; neither clamped nor squashed), and the policy acts from
     step K on (drpo_rollout_trajectories_given). No other draw moves. timer: an
-    EventTimer whose first pair brackets the horizon kernel."""
+    EventTimer whose first pair brackets the horizon kernel.
+
+    shield: a float threshold: every step runs the real-environment controller's safety
+    shield (src/smbpo.py:124-136) inside the kernel (drpo_rollout_trajectories_shielded):
+    the certificate of the policy's action from alg.constraint_critic (its quantile bound
+    when the solver's distributional_qc is set, else its mean; the maximum over its
+    outputs), and alg.actor_safe's mean action where it exceeds the threshold. The result
+    carries interventions, certificate and shield_threshold. No draw is made or moved. Not
+    with ``actions`` or a recorded tape."""
     from ._abi import RolloutGiven, RolloutTraj
     L = _lib.lib()
     dev = alg.device
@@ -336,6 +392,12 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
     _lib.require_device(policy.group.data, model.group.data)
     if actions is not None and noise.parity:
         raise ValueError('actions with a recorded tape: a tape fixes the policy\'s draws')
+    if shield is not None:
+        if actions is not None:
+            raise ValueError('shield with actions: a given action is taken as it is (the shielded given-actions '
+                             'kernels are not built)')
+        if noise.parity:
+            raise ValueError('shield with a recorded tape: the reference rollout a tape records has no shield')
 
     if initial_states is not None:
         src = initial_states.contiguous().float()
@@ -424,6 +486,13 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
     t.weights = w.data_ptr()
     t.ret, t.hmax, t.first_violation, t.terminated = (res[k].data_ptr() for k in ('returns', 'max_constraint',
                                                                                   'first_violation', 'terminated'))
+    if shield is not None:
+        sh, keep = _shield_desc(alg, policy, B, H, float(shield))
+        _lib.check(L.drpo_rollout_trajectories_shielded(ctypes.byref(d), ctypes.byref(sh), ctypes.byref(t),
+                                                        _lib.stream()), 'rollout_trajectories_shielded')
+        im = ImaginedRollout(mem, 0, **res)
+        im.interventions, im.certificate, im.shield_threshold = keep[0].view(torch.bool), keep[1], float(shield)
+        return im
     if K:
         g = RolloutGiven()
         g.actions, g.steps = actions.data_ptr(), K

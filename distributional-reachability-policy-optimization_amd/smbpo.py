@@ -254,7 +254,7 @@ class SMBPO(Configurable, Module):
     IMAGINE_SALT = 0x1A6E
 
     def imagine(self, states=None, policy=None, horizon=None, *, members=None, deterministic=False,
-                model_noise=True, discount=None, noise=None, actions=None):
+                model_noise=True, discount=None, noise=None, actions=None, shield=None):
         """What the model predicts happens from ``states`` under ``policy``: the rollout of
         src/smbpo.py:229-249 kept per trajectory (ops.ImaginedRollout: row i of every tensor
         is the trajectory from start state i), on the fused horizon kernel. Nothing of the
@@ -279,7 +279,17 @@ class SMBPO(Configurable, Module):
                    (post-tanh, as ImaginedRollout.actions holds them; not clamped); the
                    policy acts from step K on, with the draws it would have had anyway.
                    With K = horizon the policy is never evaluated. The result's
-                   ``given_steps`` is K."""
+                   ``given_steps`` is K.
+        shield     None / False: the policy alone. True: the controller that drives the real
+                   environment, the policy behind the safety shield (_shielded_action,
+                   src/smbpo.py:124-136) at self.safe_shield_threshold; a float: at that
+                   threshold. Each step the constraint critic's certificate of the policy's
+                   action (uncertainty=solver.distributional_qc) is compared with the
+                   threshold, and actor_safe's mean action taken where it is exceeded, inside
+                   the kernel. The shield makes and moves no draw: with the same noise and
+                   members the shielded and the unshielded run share every draw. The result
+                   carries ``interventions``, ``certificate`` and ``shield_threshold``. Not
+                   with ``actions`` or a recorded tape (ValueError)."""
         from . import ops
         from .rng import _mix64
         if self.env_params is None:
@@ -306,6 +316,8 @@ class SMBPO(Configurable, Module):
         if each and members != 'each':
             raise ValueError(f"members: {members!r} (None, an int, {H} ints or 'each')")
         kw = {} if actions is None else {'actions': actions}
+        if shield is not None and shield is not False:   # (with actions or a tape: refused by ops)
+            kw['shield'] = float(self.safe_shield_threshold if shield is True else shield)
         if each or deterministic or not model_noise:
             if noise.parity:
                 raise ValueError("a recorded tape fixes the members and the draws: no 'each', deterministic or "

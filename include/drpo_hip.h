@@ -200,6 +200,40 @@ int drpo_rollout_trajectories_given(const drpo_rollout_desc_t* d /* host */,
                                     const drpo_rollout_given_t* given /* host; NULL or steps == 0: none */,
                                     const drpo_rollout_traj_t* out /* host */, drpo_stream_t stream);
 
+/* The imagined rollout (src/smbpo.py:229-249) under the controller that drives the real
+ * environment: the actor behind the safety shield (SMBPO._shielded_action,
+ * src/smbpo.py:124-136). Each step, after a ~ actor(s): the certificate Qc(s, a) of the
+ * constraint critic (src/ssac.py:64-92), max over its Cq outputs of mu_c + std_ratio *
+ * std_c (distributional) or of mu_c, the first maximum winning a tie; where it exceeds
+ * `threshold` (the float comparison of drpo_shield_select mode 1) the step takes the safe
+ * actor's mean action tanh(mu_safe(s)) instead. All inside the fused horizon kernel.
+ *   - Everything of drpo_rollout_trajectories holds: its descriptor, outputs and checks.
+ *     shield == NULL is that call.
+ *   - The shield makes and moves no draw: every action and model draw is the one the
+ *     unshielded call makes, so the two runs of the same start states are paired.
+ *   - Shapes: the safe actor has the actor's shape (S -> Ha -> Ha -> 2A); the critic's
+ *     trunk is S+A -> Hc -> Hc (ReLU, ReLU output), each head Hc -> Hc -> Cq (the
+ *     reference's ConstraintCritic: trunk_layers 2, head_layers 1). 1 <= Hc <= 256,
+ *     1 <= Cq <= 8, no NULL safe-actor / trunk / mean-head pointer, the log-std head
+ *     present iff distributional: anything else DRPO_EINVAL before any launch.
+ *   - interventions / certificate: [B][H], either may be NULL; written for the steps a
+ *     row is alive at, zero at and beyond its length (zero-filled on the stream first). */
+typedef struct {
+  const float *sW1, *sb1, *sW2, *sb2, *sW3, *sb3;   /* safe actor: packed weight mirrors + biases */
+  const float *cW1, *cb1, *cW2, *cb2;               /* critic trunk */
+  const float *qW1, *qb1, *qW2, *qb2;               /* mean head */
+  const float *zW1, *zb1, *zW2, *zb2;               /* log-std head; NULL when !distributional */
+  int Hc, Cq, distributional;
+  float std_ratio, log_std_min, log_std_max;        /* std_c = exp(soft clamp of the raw log-std into [min, max]) */
+  float threshold;
+  uint8_t* interventions;   /* device [B][H]: 1 where the step took the safe actor's action */
+  float* certificate;       /* device [B][H]: the certificate of the actor's action */
+} drpo_rollout_shield_t;
+
+int drpo_rollout_trajectories_shielded(const drpo_rollout_desc_t* d /* host */,
+                                       const drpo_rollout_shield_t* shield /* host; NULL: none */,
+                                       const drpo_rollout_traj_t* out /* host */, drpo_stream_t stream);
+
 /* batched env constraint functions, e.g. PointRobot.get_constraint_values /
  * check_violation / check_done (src/env/point_robot.py:96-131); h is [n][C] */
 int drpo_env_constraints(int env_id, int tracking_surr_start, int tracking_n_surr, double env_thr0,
