@@ -18,8 +18,20 @@ using namespace drpo;
 
 // ---------------------------------------------------------------------------
 // Normalizer.fit: column mean and unbiased std over X [N][S] (double accumulation)
+//
+// The sums run over d = x - X[0][c], not over x: the variance is shift-invariant and
+// the difference of two floats is exact in double, so a constant column accumulates
+// exact zeros (variance exactly 0 at any N, hence std 1.0 as torch.std gives), and a
+// column with a large offset loses nothing in (sum d^2 - sum d * mean d): the shifted
+// mean is of the order of the spread, not of the offset. A non-finite X[0][c] shifts
+// by 0 (inf - inf would turn an inf column's mean into NaN).
 // ---------------------------------------------------------------------------
 static constexpr int NORM_ROWS = 2048;
+
+__device__ __forceinline__ double colstats_shift(const float* X, int c) {
+  const double k = X[c];
+  return (k - k == 0.0) ? k : 0.0;
+}
 
 __global__ __launch_bounds__(256) void colstats_partial_kernel(const float* X, int64_t N, int S, double* part) {
   // block b: rows [b*NORM_ROWS, ...); thread t: column t % S, row lane t / S
@@ -28,12 +40,13 @@ __global__ __launch_bounds__(256) void colstats_partial_kernel(const float* X, i
   const int c = threadIdx.x % S, rl = threadIdx.x / S;
   double s = 0.0, q = 0.0;
   if (rl < lanes) {
+    const double k = colstats_shift(X, c);
     const int64_t r0 = (int64_t)blockIdx.x * NORM_ROWS;
     const int64_t r1 = min(N, r0 + NORM_ROWS);
     for (int64_t r = r0 + rl; r < r1; r += lanes) {
-      const double x = X[r * S + c];
-      s += x;
-      q += x * x;
+      const double d = (double)X[r * S + c] - k;
+      s += d;
+      q += d * d;
     }
   }
   sh[threadIdx.x] = (rl < lanes) ? s : 0.0;
@@ -50,20 +63,21 @@ __global__ __launch_bounds__(256) void colstats_partial_kernel(const float* X, i
   }
 }
 
-__global__ void colstats_final_kernel(const double* part, int nb, int64_t N, int S, float* mean, float* std) {
+__global__ void colstats_final_kernel(const float* X, const double* part, int nb, int64_t N, int S, float* mean,
+                                      float* std) {
   const int c = threadIdx.x;
   if (c >= S) return;
-  double s = 0.0, q = 0.0;
+  double s = 0.0, q = 0.0;   // sums of d = x - shift and of d^2
   for (int b = 0; b < nb; ++b) {
     s += part[(int64_t)b * 2 * S + c];
     q += part[(int64_t)b * 2 * S + S + c];
   }
-  const double mu = s / (double)N;
-  double var = N > 1 ? (q - s * mu) / (double)(N - 1) : __longlong_as_double(0x7ff8000000000000LL);
+  const double md = s / (double)N;
+  double var = N > 1 ? (q - s * md) / (double)(N - 1) : __longlong_as_double(0x7ff8000000000000LL);
   if (var < 0) var = 0;
   float sd = (float)sqrt(var);
   if (!(sd >= 1e-6f)) sd = (sd < 1e-6f) ? 1.0f : sd;   // std[std < 1e-6] = 1.0 (NaN stays NaN)
-  mean[c] = (float)mu;
+  mean[c] = (float)(colstats_shift(X, c) + md);
   std[c] = sd;
 }
 
@@ -78,7 +92,7 @@ DRPO_API int drpo_normalizer_fit(const float* X, int64_t N, int S, float* mean, 
   const int nb = (int)((N + NORM_ROWS - 1) / NORM_ROWS);
   colstats_partial_kernel<<<nb, 256, 2 * 256 * sizeof(double), stream>>>(X, N, S, (double*)workspace);
   DRPO_LAUNCH_CHECK("normalizer_partial");
-  colstats_final_kernel<<<1, 256, 0, stream>>>((const double*)workspace, nb, N, S, mean, std);
+  colstats_final_kernel<<<1, 256, 0, stream>>>(X, (const double*)workspace, nb, N, S, mean, std);
   DRPO_LAUNCH_CHECK("normalizer_final");
   return DRPO_OK;
 }

@@ -55,3 +55,53 @@ def close(a, b, tol=1e-4, msg=''):
         np.testing.assert_allclose(a, b, rtol=tol, atol=tol, err_msg=msg)
 
 
+# ---------------------------------------------------------------------------
+# float64 comparisons under a per-element error model (tests/test_gpu_rowwise_*.py)
+# ---------------------------------------------------------------------------
+U32 = 2.0 ** -24        # unit roundoff of float32
+C_LIBM = 8              # a handful of correctly-rounded operations, each under 1 ulp
+C_HW = 32               # chains of up to ~8 v_exp_f32 / v_log_f32 / v_rcp_f32 results (1 ulp each) and the adds between
+TINY32 = 2.0 ** -126    # smallest normal float32: a result or an intermediate under it may be flushed to 0
+
+
+def f64(x):
+    return x.detach().cpu().double()
+
+
+def sp64(x):
+    """torch softplus (beta 1, threshold 20) in float64: the reference's own formula"""
+    return torch.nn.functional.softplus(x)
+
+
+def error_ratio(name, got, ref, terms, c, exp_arg=None):
+    """max |got - ref| / bound with bound = c * 2^-24 * (terms + |ref| * exp_arg) + 2^-126, all float64
+    on the CPU: ``terms`` the sum of the absolute terms of the float64 formula, ``exp_arg`` the largest
+    |argument| of an exp whose result scales the value. The relative model has no meaning under the
+    smallest normal float32: the GPU flushes denormal results and operands of its transcendentals to
+    zero (sigmoid(-100) = 3.7e-44 becomes 0, and with it a gradient of -1e-44), so one 2^-126 is allowed
+    absolutely. Prints the ratio and returns it."""
+    got, ref = f64(got), f64(ref)
+    assert got.shape == ref.shape, (name, got.shape, ref.shape)
+    assert torch.isfinite(ref).all(), name + ': reference not finite'
+    assert torch.isfinite(got).all(), name + ': kernel output not finite'
+    bound = c * U32 * (terms + (ref.abs() * exp_arg if exp_arg is not None else 0.0)) + TINY32
+    bound = torch.broadcast_to(torch.as_tensor(bound, dtype=torch.float64).detach(), ref.shape)
+    err = (got - ref).abs()
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, float('inf'), 0.0))
+    worst = ratio.max().item() if ratio.numel() else 0.0
+    k = int(ratio.reshape(-1).argmax()) if ratio.numel() else 0
+    print(f'edge-ratio {name}: max err/bound {worst:.3g} (err {err.reshape(-1)[k].item():.3g}, '
+          f'ref {ref.reshape(-1)[k].item():.6g}, flat index {k})')
+    return worst
+
+
+def within(name, got, ref, terms, c, exp_arg=None):
+    worst = error_ratio(name, got, ref, terms, c, exp_arg)
+    assert worst <= 1.0, f'{name}: error is {worst:.3g} x its bound'
+
+
+def ulp32(x):
+    """float32 spacing at |x| (float64 tensor in, float64 tensor out)"""
+    a = np.abs(f64(x).numpy()).astype(np.float32)
+    return torch.from_numpy(np.spacing(a).astype(np.float64))
+

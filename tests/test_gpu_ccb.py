@@ -8,7 +8,11 @@ forward kernel a written-out copy of it, on the same float32 head outputs: they 
 bit for bit (as they did on the parent commit). Against float64 the error is that of the hardware exp / log / rcp
 (~1e-6 relative per call; raw log-stds in [-3.1, 1.3], bounds up to 6.7): measured
 1.521e-06 on this input before the formula was shared, and 0 without ccb_dist, a plain
-maximum (profiles/sac_refactor/README.md); twice that is allowed."""
+maximum (profiles/sac_refactor/README.md); twice that is allowed.
+
+A second job scales the log-std head until its raw outputs span both soft clamps at +-4 (about
+[-57, 70]): the same bit-equality, and the float64 comparison under the per-element error model of
+tests/test_gpu_rowwise_edges.py (hardware transcendentals, c = 32)."""
 import ctypes
 
 import pytest
@@ -17,6 +21,7 @@ import torch
 from drpo_amd import _abi, _lib
 from drpo_amd.mlp_desc import ACT_ID, Net, fill_fwd
 from drpo_amd.params import packed_size
+from gpu_helpers import C_HW, within
 
 pytestmark = pytest.mark.gpu
 
@@ -46,11 +51,11 @@ def _net(gen, dims, acts, out_scale=1.0):
     return net
 
 
-def make_job():
-    """The job's nets (head outputs saved) and inputs."""
-    gen = torch.Generator().manual_seed(1234)
+def make_job(seed=1234, ls_scale=24.0):
+    """The job's nets (head outputs saved) and inputs; ls_scale 24: raw log-stds of a few units."""
+    gen = torch.Generator().manual_seed(seed)
     nets = [_net(gen, [S + A, 256, 256], ['relu', 'relu']), _net(gen, [256, 256, C], ['relu', None]),
-            _net(gen, [256, 256, C], ['relu', None], out_scale=24.0)]   # raw log-stds of a few units
+            _net(gen, [256, 256, C], ['relu', None], out_scale=ls_scale)]
     s = (torch.randn(ROWS, S, generator=gen)).cuda()
     a = (torch.rand(ROWS, A, generator=gen) * 2 - 1).cuda()
     return nets, s, a
@@ -61,13 +66,16 @@ def job():
     return make_job()
 
 
+def log_std_f64(ls):
+    sp = torch.nn.functional.softplus
+    return LMIN + sp(LMAX - sp(LMAX - ls.double()) - LMIN)
+
+
 def bound_f64(mu, ls, dist):
-    mu, ls = mu.double(), ls.double()
+    mu = mu.double()
     if not dist:
         return mu.max(dim=1).values
-    sp = torch.nn.functional.softplus
-    log_std = LMIN + sp(LMAX - sp(LMAX - ls) - LMIN)
-    return (mu + RATIO * log_std.exp()).max(dim=1).values
+    return (mu + RATIO * log_std_f64(ls).exp()).max(dim=1).values
 
 
 def run_bounds(job, dist):
@@ -85,15 +93,32 @@ def run_bounds(job, dist):
     _lib.check(L.drpo_cc_head(mu.data_ptr(), ls.data_ptr(), ROWS, C, int(dist), RATIO, LMIN, LMAX, alone.data_ptr(),
                               None, _lib.stream()), 'cc_head')
     torch.cuda.synchronize()
-    return out.cpu(), alone.cpu(), bound_f64(mu.cpu(), ls.cpu(), dist), ls.cpu()
+    return out.cpu(), alone.cpu(), bound_f64(mu.cpu(), ls.cpu(), dist), ls.cpu(), mu.cpu()
 
 
 @pytest.mark.parametrize('dist', [False, True])
 def test_in_kernel_bound_matches_cc_head_and_float64(job, dist):
-    fused, alone, ref, ls = run_bounds(job, dist)
+    fused, alone, ref, ls, _ = run_bounds(job, dist)
     err = (fused.double() - ref).abs().max().item()
     print(f'ccb dist={int(dist)}: bit-equal to drpo_cc_head: {torch.equal(fused, alone)}; max |fused - f64| = {err:.3e}; '
           f'|bound| <= {ref.abs().max().item():.3f}; raw log-std in [{ls.min().item():.2f}, {ls.max().item():.2f}]')
     assert torch.isfinite(fused).all()
     assert torch.equal(fused, alone)
     assert err <= (CCB_F64_TOL if dist else 0.0)
+
+
+def test_in_kernel_bound_with_both_clamps_acting():
+    """raw log-stds far outside [-4, 4] on both sides: std saturates at exp(-4) and exp(4)"""
+    fused, alone, ref, ls, mu = run_bounds(make_job(seed=4321, ls_scale=576.0), True)
+    print(f'ccb wide: bit-equal to drpo_cc_head: {torch.equal(fused, alone)}; |bound| <= {ref.abs().max().item():.3f}; '
+          f'raw log-std in [{ls.min().item():.2f}, {ls.max().item():.2f}]; below -4: {(ls < LMIN).float().mean().item():.2f}, '
+          f'above 4: {(ls > LMAX).float().mean().item():.2f}')
+    assert ls.min() < -40 and ls.max() > 40
+    assert torch.isfinite(fused).all()
+    assert torch.equal(fused, alone)
+    log_std = log_std_f64(ls)
+    std = log_std.exp()
+    v = mu.double() + RATIO * std
+    # |max_c got_c - max_c ref_c| <= max_c |got_c - ref_c|: the largest element bound of the row
+    terms = (mu.double().abs() + RATIO * std + v.abs() * log_std.abs()).max(dim=1).values
+    within('ccb wide in-kernel bound', fused, ref, terms, C_HW)

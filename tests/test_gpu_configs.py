@@ -614,6 +614,71 @@ def test_fit_fb_matches_two_launches(c):
             np.testing.assert_allclose(a, b, rtol=2e-5, atol=1e-6, err_msg=k)
 
 
+@pytest.mark.parametrize('fb', [True, False])
+def test_fit_step_tight_log_var_bounds_vs_oracle(fb):
+    """The fused flavour of the NLL (nll_element with the hardware sp_grad: fit_fb_body when fb, else
+    ens_upstream inside drpo_mlp_backward_ens) with a good share of elements OUTSIDE each log-variance
+    bound, where the bound-gradient shares cmn / cmx and the clamp's slopes are not ~0 / ~1 as they are
+    at the initial bounds [-10, 1]: the bounds are set to the 30 % / 70 % quantiles of the initial raw
+    log-variance outputs, per column. One fit step on recorded draws against O.ens_fit: the step loss
+    (rtol 1e-4, test_config_full_width_fit_vs_oracle) and every parameter's gradient, the log-var
+    bounds' included, read back from Adam's first moment after its first step (0.1 x the effective
+    gradient on both sides) with the gradient tolerance of test_gpu_ensemble.py."""
+    alg, cd = _alg(2, B=256)
+    m = alg.model_ensemble
+    eng = m.engine
+    _fill(alg, cd['env'], 30000, 9)
+    buf = {k: v.cpu() for k, v in alg.replay_buffer.get(as_dict=True).items()}
+    P = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
+    _oracle_threads()
+    E = m.ensemble_size
+
+    def raw_log_var(s, a):
+        x = torch.cat([O.normalize(P, '', s), a], dim=-1)
+        return O._batched(P, 'log_var_head.', O._batched(P, 'trunk.', x, True), False)
+    P['state_normalizer.mean'], P['state_normalizer.std'] = O.normalizer_fit(buf['states'])
+    raw = raw_log_var(buf['states'][:2048].repeat(E, 1, 1), buf['actions'][:2048].repeat(E, 1, 1))
+    flat = raw.reshape(-1, raw.shape[-1])
+    lo, hi = torch.quantile(flat, 0.3, dim=0), torch.quantile(flat, 0.7, dim=0)
+    P['min_log_var'], P['max_log_var'] = lo.clone(), hi.clone()
+    m.min_log_var.data.copy_(lo.to(DEV))
+    m.max_log_var.data.copy_(hi.to(DEV))
+    torch.manual_seed(17)
+    live = O.LiveRNG()
+    opt = {}
+    P0 = {k: v.clone() for k, v in P.items()}
+    ref_losses, _ = O.ens_fit(P, '', opt, buf, 1, E, m.batch_size, m.holdout_size, m.num_elites, live)
+    idx = torch.as_tensor(np.asarray(live.entries[0][1])).long().reshape(E, -1)
+    P, P_after = P0, P                           # the shares: the oracle's raw outputs on the step's minibatch
+    raw = raw_log_var(buf['states'][idx], buf['actions'][idx])
+    below, above = (raw < lo).float().mean().item(), (raw > hi).float().mean().item()
+    print(f'tight log-var bounds (fb={fb}): {below:.3f} of the elements below min_log_var, {above:.3f} above max_log_var')
+    assert below >= 0.10 and above >= 0.10
+    tape = drpo_amd.TapeNoise(live.entries)
+    m.optimizer._ensure_state()
+    eng.ws.clear()
+    eng.wg_ws.clear()
+    try:
+        eng.fit_fb_enabled = fb
+        losses = m.fit(alg.replay_buffer, steps=1, noise=tape)
+        torch.cuda.synchronize()
+    finally:
+        eng.fit_fb_enabled = True
+    assert tape.done()
+    assert eng.fit_fb == fb and eng.fit_path == 'fused'
+    np.testing.assert_allclose(losses, ref_losses, rtol=1e-4)
+    bad = []
+    for k in O.ens_param_keys(P_after, ''):
+        got = m.group.view(k, m.optimizer.m).cpu().numpy()
+        exp = opt[k]['m'].numpy()
+        tol = 1e-5 * np.abs(exp).max() + 1e-3 * np.abs(exp)
+        if (np.abs(got - exp) > tol).any():
+            bad.append((k, float(np.abs(got - exp).max()), float(np.abs(exp).max())))
+    assert not bad, bad
+    for k in ('min_log_var', 'max_log_var'):
+        assert np.abs(opt[k]['m'].numpy()).min() > 0
+
+
 @pytest.mark.parametrize('c', [2])
 def test_multiplier_post_chain_matches_separate_launch(c):
     """The MLPMultiplier forward chained behind the constraint bound in the same
