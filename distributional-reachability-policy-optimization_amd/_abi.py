@@ -52,6 +52,11 @@ class RolloutShield(ctypes.Structure):
                 ('interventions', P), ('certificate', P)]
 
 
+class RolloutLinear(ctypes.Structure):
+    """drpo_rollout_linear_t"""
+    _fields_ = [('candidates', c_int), ('blend', P)]
+
+
 ENV_PROGRAM = 4          # DRPO_ENV_PROGRAM
 PROG_AFFINE, PROG_BALLS = 0, 1
 PROG_MAX_ROWS = PROG_MAX_TERMS = PROG_MAX_CENTRES = PROG_MAX_BOX = 8
@@ -119,6 +124,8 @@ PROTOTYPES = {
     'drpo_rollout_trajectories_given': (c_int, [POINTER(RolloutDesc), POINTER(RolloutGiven), POINTER(RolloutTraj), P]),
     'drpo_rollout_trajectories_shielded': (c_int, [POINTER(RolloutDesc), POINTER(RolloutShield), POINTER(RolloutTraj),
                                                    P]),
+    'drpo_rollout_trajectories_linear': (c_int, [POINTER(RolloutDesc), POINTER(RolloutShield), POINTER(RolloutLinear),
+                                                 POINTER(RolloutTraj), P]),
     'drpo_env_constraints': (c_int, [c_int, c_int, c_int, c_double, c_double, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_constraints_program': (c_int, [P, c_int, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_program_check': (c_int, [POINTER(EnvProgram), c_int]),

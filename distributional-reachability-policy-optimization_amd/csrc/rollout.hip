@@ -67,6 +67,7 @@ extern "C" __attribute__((visibility("default"))) int drpo_debug_stamps_rollout(
 #include "env_constraints.hpp"
 #include "prp.hpp"
 #include "sac_rows.hpp"
+#include "shield_mix.hpp"
 
 using namespace drpo;
 
@@ -496,6 +497,11 @@ struct PersistArgs {
   float sh_ratio, sh_lmin, sh_lmax, sh_thr;
   uint8_t* sh_iv;     // [B][H] or null
   float* sh_cert;     // [B][H] or null
+  // the linear shield (src/sampling.py:430-437) on the same kernels: K candidates, 0: the
+  // threshold shield. sh_ab: float offset into the LDS of a_perf / a_safe, 2 x [ROWS][8],
+  // behind everything else (LDS-resident actor weights included).
+  int sh_lin_k, sh_ab;
+  uint8_t* sh_blend;  // [B][H] or null
 };
 
 typedef const __attribute__((address_space(4))) PersistArgs* PersistArgsK;   // scalar (constant) loads
@@ -760,6 +766,11 @@ constexpr int PERSIST_L2_LDS = 3;
 // certificate of (s, a) (cc_bound_row), the decision certificate > threshold, the safe
 // actor's mean action for the tiles with an intervening row, and the select into act /
 // xin. No draw is made or moved. Instantiations of their own once more.
+// The same kernels run the evaluation's linear shield (src/sampling.py:430-437,
+// drpo_rollout_trajectories_linear) on a kernarg, sh_lin_k = K candidates: rows whose
+// certificate fails try the blends j = 1 .. K-2 between the two actions one certificate
+// pass each, closest to the policy's first, and take the first that passes or, at K-1,
+// the safe action. The passes end as soon as no alive row of the tile is undecided.
 template <int RB, int NW, bool LW, int PM, bool PG = false, bool GA = false, bool SH = false>
 __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p) {
   constexpr int ROWS = RB * 16;
@@ -932,6 +943,19 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
         lds_barrier();   // act / xin[.., S + d] of every row; the sampling threads are done with red
         const int Hc = PARG(Hc), Cq = PARG(Cq);
         const bool dist = PARG(sh_dist) != 0;
+        // LK candidates (0: the threshold shield, one pass). Pass j scores candidate j of the
+        // rows still undecided (ivm; all rows at j = 0, where the candidate is the policy's
+        // action). Every exit below is on j, a kernarg or ivm: workgroup-uniform.
+        const int LK = PARG(sh_lin_k);
+        unsigned ivm = ~0u;
+        for (int j = 0;; ++j) {
+        // the LDS carve-up once more per pass, as at the top of the step and for its reason:
+        // the per-lane addresses of the unrolled layers must not be hoisted out of this loop
+        int zj = 0, ldxj = ldx, ldhj = ldh, ldmj = ldm;
+        asm volatile("" : "+s"(zj), "+s"(ldxj), "+s"(ldhj), "+s"(ldmj));
+        {
+        const int ldx = ldxj, ldh = ldhj, ldm = ldmj;
+        PERSIST_LDS_LAYOUT(zj, ldx, ldh, ldm, ldss)
         // 1. certificate: the constraint critic's trunk [S+A -> Hc -> Hc] (ReLU, ReLU
         //    output), the heads [Hc -> Hc -> Cq] (src/ssac.py:64-92)
         tile_dense<NW, RB, MAXC, ACT_RELU>(xin, ldx, S + A, step_opaque(PARG(cW1)), step_opaque(PARG(cb1)), Hc, h1,
@@ -968,27 +992,33 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
           lds_barrier();
         }
         // 2. decision (wave 0, one lane per row): the float comparison of
-        //    drpo_shield_select mode 1; the tile's intervening rows as a bit mask in LDS
+        //    drpo_shield_select mode 1 (linear: mode 2, a NaN does not qualify); the tile's
+        //    intervening (linear: undecided) rows as a bit mask in LDS
         if (tid < 64) {
           bool iv = false;
-          if (tid < ROWS && alive_cur[tid]) {
+          if (tid < ROWS && alive_cur[tid] && ((ivm >> tid) & 1u)) {
             const float* mu = dout + tid * ldm;
             const float* ls = lout + tid * ldm;
             const CcBound b = cc_bound_row([&](int c) { return mu[c]; }, [&](int c) { return ls[c]; }, Cq, dist,
                                            PARG(sh_ratio), PARG(sh_lmin), PARG(sh_lmax));
-            iv = b.best > PARG(sh_thr);
+            iv = LK ? !(b.best <= PARG(sh_thr)) : b.best > PARG(sh_thr);
             const size_t o = (size_t)(row0 + tid) * PARG(H) + t;   // alive: row0 + tid < B
-            if (PARG(sh_cert)) PARG(sh_cert)[o] = b.best;
-            if (PARG(sh_iv)) PARG(sh_iv)[o] = iv ? 1 : 0;
+            if (j == 0) {
+              if (PARG(sh_cert)) PARG(sh_cert)[o] = b.best;
+              if (PARG(sh_iv)) PARG(sh_iv)[o] = iv ? 1 : 0;
+            } else if (!iv && PARG(sh_blend)) {
+              PARG(sh_blend)[o] = (uint8_t)j;   // decided at j (0: the zero fill)
+            }
           }
           const uint64_t ivk = __ballot(iv);
           if (tid == 0) s_nalive[1] = (int)(uint32_t)ivk;   // ROWS <= 32
         }
         lds_barrier();
-        const unsigned ivm = (unsigned)__builtin_amdgcn_readfirstlane(s_nalive[1]);
+        ivm = (unsigned)__builtin_amdgcn_readfirstlane(s_nalive[1]);
+        if (ivm == 0u) break;
         // 3. safe actor (the actor's shape), only in a tile with an intervening row: the
         //    test is workgroup-uniform, so every barrier below is reached by all waves or none
-        if (ivm != 0u) {
+        if (j == 0) {
           tile_dense<NW, RB, MAXC, ACT_RELU>(xin, ldx, S, step_opaque(PARG(sW1)), step_opaque(PARG(sb1)), Ha, h1, ldh);
           lds_barrier();
           tile_dense<NW, RB, MAXC, ACT_RELU>(h1, ldh, Ha, step_opaque(PARG(sW2)), step_opaque(PARG(sb2)), Ha, h2, ldh);
@@ -1001,10 +1031,41 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
             const int r = tid / A, d = tid - r * A;
             if ((ivm >> r) & 1u) {
               const float a = fast_tanh(narrow_sum<NW, RB>(red, r, d) + bmu);
-              act[r * 8 + d] = a;
-              xin[r * ldx + S + d] = a;
+              if (LK) {
+                // linear: both ends of the blend stay in LDS for the passes to come (read
+                // back below by the thread that writes them)
+                float* ab = smem + PARG(sh_ab);
+                ab[r * 8 + d] = act[r * 8 + d];
+                ab[ROWS * 8 + r * 8 + d] = a;
+              } else {
+                act[r * 8 + d] = a;
+                xin[r * ldx + S + d] = a;
+              }
             }
           }
+          if (LK == 0) break;
+        }
+        // 5. the next candidate of the undecided rows into act / xin: blend j + 1 (mix_k of
+        //    drpo_shield_mix, k = LK-1 - (j+1)), or, at the last, the safe action itself,
+        //    whose certificate decides nothing and is not computed
+        const bool last = j + 1 >= LK - 1;
+        if (tid < ROWS * A) {
+          const int r = tid / A, d = tid - r * A;
+          if ((ivm >> r) & 1u) {
+            const float* ab = smem + PARG(sh_ab);
+            const float as = ab[ROWS * 8 + r * 8 + d];
+            const float a = last ? as : shield_mix_k(as, ab[r * 8 + d], LK, LK - 2 - j);
+            act[r * 8 + d] = a;
+            xin[r * ldx + S + d] = a;
+          }
+        }
+        if (last) {
+          if (tid < ROWS && ((ivm >> tid) & 1u) && PARG(sh_blend))   // undecided: alive
+            PARG(sh_blend)[(size_t)(row0 + tid) * PARG(H) + t] = (uint8_t)(LK - 1);
+          break;
+        }
+        lds_barrier();   // the candidates, before the next pass reads xin
+        }
         }
       }
       for (int e = tid; e < ROWS * S; e += NT) {
@@ -1518,6 +1579,9 @@ static size_t persist_lds_bytes(int S, int A, int Ha, int Hm, int rpt, int nw) {
                           (size_t)nw * (rpt / 16) * 256 + 256);
 }
 
+// The linear shield's share on top: a_perf and a_safe, [rpt][8] floats each.
+static size_t persist_linear_lds_bytes(int rpt) { return sizeof(float) * (size_t)rpt * 16; }
+
 // LDS bytes of rollout_step_kernel: per row xin, h1-h3, sraw, ao, dout, lout, act, rew,
 // hval, flags, srcrow; then the split-K partials, the scan partials, the previous step's
 // tile prefix and the normalizer / log-var vectors.
@@ -1561,9 +1625,11 @@ static void launch_persist(bool paired, bool pg, const PersistArgs& a, size_t ld
 // rollout_emit_self_kernel; without it the kernel touches neither the buffer nor its pointer.
 // given: actions for the first given->steps steps (nullptr or steps == 0: none).
 // shield: the safety shield inside the step (checked by the caller; not together with given).
+// linear: the shield is the linear one (with shield only; checked by the caller).
 static int persist_run(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt, int64_t rlen, bool self_emit,
                        const char* who, hipStream_t stream, PersistArgs& a,
-                       const drpo_rollout_given_t* given = nullptr, const drpo_rollout_shield_t* shield = nullptr) {
+                       const drpo_rollout_given_t* given = nullptr, const drpo_rollout_shield_t* shield = nullptr,
+                       const drpo_rollout_linear_t* linear = nullptr) {
   DRPO_REQUIRE(d->H <= PERSIST_MAX_H, "%s: engine 2 supports horizon <= %d", who, PERSIST_MAX_H);
   const int S = d->S, A = d->A, S1 = d->S + 1, B = d->B, H = d->H;
   fill_shared_args(a, d, rlen);
@@ -1598,12 +1664,19 @@ static int persist_run(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt
   }
 
   const size_t lds_bytes = persist_lds_bytes(S, A, Hw, d->Hm, rpt, 8);
-  DRPO_REQUIRE(lds_bytes <= 160 * 1024, "%s: LDS %zu too large", who, lds_bytes);
+  // the linear shield's a_perf / a_safe, behind everything else
+  const size_t lin_bytes = linear ? persist_linear_lds_bytes(rpt) : 0;
+  DRPO_REQUIRE(lds_bytes + lin_bytes <= 160 * 1024, "%s: LDS %zu too large", who, lds_bytes + lin_bytes);
   // LDS-resident actor weights (see rollout_persist_kernel) when they fit
   const size_t lw_bytes = sizeof(float) * (size_t)(32 + 16 * PERSIST_L2_LDS) * 256;
   // (not when every step's action is given: the actor never runs)
-  const bool lw = rpt == 16 && S <= 16 && d->Ha == 256 && 2 * A <= 16 && lds_bytes + lw_bytes <= 160 * 1024 &&
-                  a.n_given < H;
+  const bool lw = rpt == 16 && S <= 16 && d->Ha == 256 && 2 * A <= 16 &&
+                  lds_bytes + lw_bytes + lin_bytes <= 160 * 1024 && a.n_given < H;
+  if (linear) {
+    a.sh_lin_k = linear->candidates;
+    a.sh_ab = (int)((lds_bytes + (lw ? lw_bytes : 0)) / sizeof(float));
+    a.sh_blend = linear->blend;
+  }
   const bool paired = S1 <= 16 && d->Hm == 200;   // the kernel's PM specialisation
   const bool pg = d->env_id == DRPO_ENV_PROGRAM;
   if (self_emit) {
@@ -1616,11 +1689,12 @@ static int persist_run(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt
     const size_t BH = (size_t)B * H;
     if (shield->interventions) DRPO_CHECK_HIP(hipMemsetAsync(shield->interventions, 0, BH, stream));
     if (shield->certificate) DRPO_CHECK_HIP(hipMemsetAsync(shield->certificate, 0, BH * sizeof(float), stream));
+    if (linear && linear->blend) DRPO_CHECK_HIP(hipMemsetAsync(linear->blend, 0, BH, stream));
   }
   if (d->step_events) hipEventRecord((hipEvent_t)d->step_events[0], stream);
-  if (rpt == 32) launch_persist<2, false>(paired, pg, a, lds_bytes, stream);
-  else if (lw) launch_persist<1, true>(paired, pg, a, lds_bytes + lw_bytes, stream);
-  else launch_persist<1, false>(paired, pg, a, lds_bytes, stream);
+  if (rpt == 32) launch_persist<2, false>(paired, pg, a, lds_bytes + lin_bytes, stream);
+  else if (lw) launch_persist<1, true>(paired, pg, a, lds_bytes + lw_bytes + lin_bytes, stream);
+  else launch_persist<1, false>(paired, pg, a, lds_bytes + lin_bytes, stream);
   DRPO_LAUNCH_CHECK("rollout_persist");
   if (d->step_events) hipEventRecord((hipEvent_t)d->step_events[1], stream);
   return DRPO_OK;
@@ -1767,8 +1841,13 @@ DRPO_API int drpo_rollout(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
 // The fused engine's horizon kernel + the trajectory tail: the rollout per original row
 // (row identity) instead of into the virtual buffer, which it never touches.
 static int rollout_trajectories(const drpo_rollout_desc_t* d, const drpo_rollout_given_t* given,
-                                const drpo_rollout_shield_t* shield, const drpo_rollout_traj_t* out, const char* who,
-                                hipStream_t stream) {
+                                const drpo_rollout_shield_t* shield, const drpo_rollout_linear_t* linear,
+                                const drpo_rollout_traj_t* out, const char* who, hipStream_t stream) {
+  if (linear) {
+    DRPO_REQUIRE(shield, "%s: the linear shield needs the shield's networks (linear without shield)", who);
+    DRPO_REQUIRE(linear->candidates >= 2 && linear->candidates <= 32, "%s: linear shield candidates %d outside 2..32",
+                 who, linear->candidates);
+  }
   if (shield) {
     // the shapes the SH instantiations run; anything else is refused, never run another way
     const drpo_rollout_shield_t& s = *shield;
@@ -1786,7 +1865,8 @@ static int rollout_trajectories(const drpo_rollout_desc_t* d, const drpo_rollout
   // the wider of the actor's and the critic's hidden layers sizes the tile: an automatic
   // 32-row tile that no longer fits falls back to 16 rows (a requested one is refused below)
   if (shield && !d->rows_per_tile && rpt == 32 &&
-      persist_lds_bytes(d->S, d->A, d->Ha > shield->Hc ? d->Ha : shield->Hc, d->Hm, 32, 8) > 160 * 1024)
+      persist_lds_bytes(d->S, d->A, d->Ha > shield->Hc ? d->Ha : shield->Hc, d->Hm, 32, 8) +
+              (linear ? persist_linear_lds_bytes(32) : 0) > 160 * 1024)
     rpt = 16;
   DRPO_REQUIRE(d->engine != 1, "%s: runs the fused engine only (engine 0 or 2, not 1)", who);
   DRPO_REQUIRE(!(d->eps_a && d->eps_layout == 0),
@@ -1801,7 +1881,7 @@ static int rollout_trajectories(const drpo_rollout_desc_t* d, const drpo_rollout
   RolloutWs w;
   rollout_ws(d->B, d->S, d->H, reinterpret_cast<uintptr_t>(d->workspace), w);
   PersistArgs a{};
-  if (const int rc = persist_run(d, w, rpt, rlen, false, who, stream, a, given, shield)) return rc;
+  if (const int rc = persist_run(d, w, rpt, rlen, false, who, stream, a, given, shield, linear)) return rc;
   const TrajArgs ta{d->S, d->A, d->C, d->B, d->H, w.st_s, w.st_s2, w.st_a, w.st_r, w.st_h, w.st_dv, *out};
   rollout_traj_kernel<<<(d->B + TRAJ_ROWS - 1) / TRAJ_ROWS, TRAJ_NT, 0, stream>>>(ta);
   DRPO_LAUNCH_CHECK("rollout_traj");
@@ -1810,21 +1890,30 @@ static int rollout_trajectories(const drpo_rollout_desc_t* d, const drpo_rollout
 
 DRPO_API int drpo_rollout_trajectories(const drpo_rollout_desc_t* d, const drpo_rollout_traj_t* out,
                                        drpo_stream_t stream) {
-  return rollout_trajectories(d, nullptr, nullptr, out, "drpo_rollout_trajectories", (hipStream_t)stream);
+  return rollout_trajectories(d, nullptr, nullptr, nullptr, out, "drpo_rollout_trajectories", (hipStream_t)stream);
 }
 
 // The same under given actions: the first given->steps steps take their action from
 // memory instead of from the actor (the GA instantiations of rollout_persist_kernel).
 DRPO_API int drpo_rollout_trajectories_given(const drpo_rollout_desc_t* d, const drpo_rollout_given_t* given,
                                              const drpo_rollout_traj_t* out, drpo_stream_t stream) {
-  return rollout_trajectories(d, given, nullptr, out, "drpo_rollout_trajectories_given", (hipStream_t)stream);
+  return rollout_trajectories(d, given, nullptr, nullptr, out, "drpo_rollout_trajectories_given", (hipStream_t)stream);
 }
 
 // The same under the shielded controller (src/smbpo.py:124-136): the SH instantiations of
 // rollout_persist_kernel. shield == nullptr is drpo_rollout_trajectories.
 DRPO_API int drpo_rollout_trajectories_shielded(const drpo_rollout_desc_t* d, const drpo_rollout_shield_t* shield,
                                                 const drpo_rollout_traj_t* out, drpo_stream_t stream) {
-  return rollout_trajectories(d, nullptr, shield, out, "drpo_rollout_trajectories_shielded", (hipStream_t)stream);
+  return rollout_trajectories(d, nullptr, shield, nullptr, out, "drpo_rollout_trajectories_shielded",
+                              (hipStream_t)stream);
+}
+
+// The same under the evaluation's controller, the linear shield (src/sampling.py:430-437):
+// the SH instantiations with sh_lin_k candidates. linear == nullptr is the call above.
+DRPO_API int drpo_rollout_trajectories_linear(const drpo_rollout_desc_t* d, const drpo_rollout_shield_t* shield,
+                                              const drpo_rollout_linear_t* linear, const drpo_rollout_traj_t* out,
+                                              drpo_stream_t stream) {
+  return rollout_trajectories(d, nullptr, shield, linear, out, "drpo_rollout_trajectories_linear", (hipStream_t)stream);
 }
 
 __global__ void prp_kernel(int64_t* out, int64_t B, int64_t N, int hb, uint32_t k0, uint32_t k1, uint32_t k2,

@@ -14,6 +14,7 @@
 // Arithmetic matches PyTorch CPU fp32: the scalar ratios are rounded to float once
 // (tensor * python float), products and the sum are separately rounded (no FMA).
 #include "common.hpp"
+#include "shield_mix.hpp"
 
 namespace {
 
@@ -23,9 +24,7 @@ __global__ void shield_mix_kernel(const float* ap, const float* as, int64_t n, i
   if (i >= per * K) return;
   const int k = (int)(i / per);
   const int64_t j = i - (int64_t)k * per;
-  const double r = (double)(K - 1 - k) / (double)(K - 1);
-  const float rs = (float)r, rp = (float)(1.0 - r);
-  mixes[i] = __fadd_rn(__fmul_rn(as[j], rs), __fmul_rn(ap[j], rp));
+  mixes[i] = drpo::shield_mix_k(as[j], ap[j], K, k);
 }
 
 __device__ __forceinline__ float row_max(const float* q, int C) {

@@ -236,7 +236,12 @@ class ImaginedRollout:
     Under the shield (imagine(shield=)) three attributes are set, None otherwise:
       interventions [B, H] bool  the step took the safe actor's action
       certificate [B, H]         the constraint critic's certificate of the actor's action
-      shield_threshold           the threshold the certificate was compared with"""
+      shield_threshold           the threshold the certificate was compared with
+    Under the linear shield (imagine(shield='linear')) two more, None otherwise:
+      blend [B, H] uint8         j of the action taken: 0 the policy's, K-1 the safe actor's,
+                                 between them the blend with share blend / (K-1) of the safe
+                                 action; interventions is blend != 0
+      shield_candidates          K"""
     TENSORS = ('states', 'actions', 'rewards', 'constraint_values', 'dones', 'violations', 'lengths', 'returns',
                'max_constraint', 'first_violation', 'terminated')
 
@@ -245,6 +250,7 @@ class ImaginedRollout:
         self.members = members
         self.given_steps = given_steps
         self.interventions = self.certificate = self.shield_threshold = None
+        self.blend = self.shield_candidates = None
         self.__dict__.update(tensors)
 
     @property
@@ -260,6 +266,9 @@ class ImaginedRollout:
             out.interventions = torch.stack([r.interventions for r in runs])
             out.certificate = torch.stack([r.certificate for r in runs])
             out.shield_threshold = runs[0].shield_threshold
+        if runs[0].blend is not None:
+            out.blend = torch.stack([r.blend for r in runs])
+            out.shield_candidates = runs[0].shield_candidates
         return out
 
 
@@ -300,13 +309,13 @@ def _traj_static(alg, policy, B, H):
     return hit
 
 
-def _shield_desc(alg, policy, B, H, threshold):
-    """drpo_rollout_shield_t of alg's shield: alg.actor_safe, alg.constraint_critic (with
-    the solver's distributional_qc), fresh [B, H] outputs. Refuses what the kernels do not
-    run. Returns (descriptor, (interventions uint8, certificate))."""
+def _shield_desc(alg, policy, B, H, threshold, dist):
+    """drpo_rollout_shield_t of alg's shield: alg.actor_safe, alg.constraint_critic (dist:
+    its distributional bound; False: its mean, the log-std head left out), fresh [B, H]
+    outputs. Refuses what the kernels do not run. Returns (descriptor, (interventions
+    uint8, certificate))."""
     from ._abi import RolloutShield
     safe, cc = alg.actor_safe, alg.constraint_critic
-    dist = bool(alg.solver.distributional_qc)
     if safe.spec.dims != policy.spec.dims:
         raise ValueError(f'shield: the safe actor\'s layers {safe.spec.dims} are not the policy\'s {policy.spec.dims}')
     Hc, Cq = cc.hidden_dim, cc.output_dim
@@ -351,7 +360,8 @@ def _traj_members(model, members, H):
 
 
 def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, eps_a=None, eps_m=None, eps_layout=1,
-                         weights=None, out=None, horizon=None, ctr=None, actions=None, timer=None, shield=None):
+                         weights=None, out=None, horizon=None, ctr=None, actions=None, timer=None, shield=None,
+                         shield_candidates=None, shield_uncertainty=None):
     """One imagined rollout (src/smbpo.py:229-249) kept per trajectory: the fused horizon
     kernel and the trajectory tail (drpo_rollout_trajectories). Never touches
     alg.virt_buffer. Mirrors ``rollout``: the same start states, members and draws for
@@ -377,8 +387,17 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
     when the solver's distributional_qc is set, else its mean; the maximum over its
     outputs), and alg.actor_safe's mean action where it exceeds the threshold. The result
     carries interventions, certificate and shield_threshold. No draw is made or moved. Not
-    with ``actions`` or a recorded tape."""
-    from ._abi import RolloutGiven, RolloutTraj
+    with ``actions`` or a recorded tape.
+
+    shield_candidates: K, 2..32, with ``shield``: the evaluation's linear shield instead
+    (src/sampling.py:430-437, drpo_rollout_trajectories_linear): of the K blends between the
+    policy's action (j = 0) and the safe actor's (j = K-1), drpo_shield_mix's candidates,
+    the one closest to the policy's whose certificate is <= the threshold, the safe action
+    if none is. The result carries blend and shield_candidates too.
+    shield_uncertainty: whether the certificate is the critic's distributional bound.
+    Default: solver.distributional_qc for the threshold shield, False for the linear one
+    (the evaluation scores its candidates by the mean). True needs a distributional critic."""
+    from ._abi import RolloutGiven, RolloutLinear, RolloutTraj
     L = _lib.lib()
     dev = alg.device
     B = alg.rollout_batch_size
@@ -389,7 +408,6 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
     S1 = S + 1
     model = alg.model_ensemble
     rb = alg.replay_buffer._module
-    _lib.require_device(policy.group.data, model.group.data)
     if actions is not None and noise.parity:
         raise ValueError('actions with a recorded tape: a tape fixes the policy\'s draws')
     if shield is not None:
@@ -398,6 +416,15 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
                              'kernels are not built)')
         if noise.parity:
             raise ValueError('shield with a recorded tape: the reference rollout a tape records has no shield')
+        if shield_candidates is not None and not (isinstance(shield_candidates, (int, np.integer)) and
+                                                  not isinstance(shield_candidates, bool) and
+                                                  2 <= shield_candidates <= 32):
+            raise ValueError(f'shield_candidates: {shield_candidates!r} (an int, 2..32)')
+        if shield_uncertainty and not alg.solver.distributional_qc:
+            raise ValueError('shield_uncertainty: the constraint critic is not distributional')
+    elif shield_candidates is not None or shield_uncertainty is not None:
+        raise ValueError('shield_candidates / shield_uncertainty without shield')
+    _lib.require_device(policy.group.data, model.group.data)
 
     if initial_states is not None:
         src = initial_states.contiguous().float()
@@ -487,10 +514,22 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
     t.ret, t.hmax, t.first_violation, t.terminated = (res[k].data_ptr() for k in ('returns', 'max_constraint',
                                                                                   'first_violation', 'terminated'))
     if shield is not None:
-        sh, keep = _shield_desc(alg, policy, B, H, float(shield))
-        _lib.check(L.drpo_rollout_trajectories_shielded(ctypes.byref(d), ctypes.byref(sh), ctypes.byref(t),
-                                                        _lib.stream()), 'rollout_trajectories_shielded')
+        if shield_uncertainty is None:
+            dist = bool(alg.solver.distributional_qc) and shield_candidates is None
+        else:
+            dist = bool(shield_uncertainty)
+        sh, keep = _shield_desc(alg, policy, B, H, float(shield), dist)
         im = ImaginedRollout(mem, 0, **res)
+        if shield_candidates is None:
+            _lib.check(L.drpo_rollout_trajectories_shielded(ctypes.byref(d), ctypes.byref(sh), ctypes.byref(t),
+                                                            _lib.stream()), 'rollout_trajectories_shielded')
+        else:
+            lin = RolloutLinear()
+            im.blend = torch.empty(B, H, dtype=torch.uint8, device=dev)
+            lin.candidates, lin.blend = int(shield_candidates), im.blend.data_ptr()
+            im.shield_candidates = int(shield_candidates)
+            _lib.check(L.drpo_rollout_trajectories_linear(ctypes.byref(d), ctypes.byref(sh), ctypes.byref(lin),
+                                                          ctypes.byref(t), _lib.stream()), 'rollout_trajectories_linear')
         im.interventions, im.certificate, im.shield_threshold = keep[0].view(torch.bool), keep[1], float(shield)
         return im
     if K:

@@ -254,7 +254,8 @@ class SMBPO(Configurable, Module):
     IMAGINE_SALT = 0x1A6E
 
     def imagine(self, states=None, policy=None, horizon=None, *, members=None, deterministic=False,
-                model_noise=True, discount=None, noise=None, actions=None, shield=None):
+                model_noise=True, discount=None, noise=None, actions=None, shield=None,
+                shield_uncertainty=None):
         """What the model predicts happens from ``states`` under ``policy``: the rollout of
         src/smbpo.py:229-249 kept per trajectory (ops.ImaginedRollout: row i of every tensor
         is the trajectory from start state i), on the fused horizon kernel. Nothing of the
@@ -289,7 +290,25 @@ class SMBPO(Configurable, Module):
                    the kernel. The shield makes and moves no draw: with the same noise and
                    members the shielded and the unshielded run share every draw. The result
                    carries ``interventions``, ``certificate`` and ``shield_threshold``. Not
-                   with ``actions`` or a recorded tape (ValueError)."""
+                   with ``actions`` or a recorded tape (ValueError).
+                   'linear', ('linear', thr) or ('linear', thr, K): the controller every
+                   evaluation runs and every reported number comes from, the policy behind
+                   the linear shield (sample_episodes_batched, src/sampling.py:430-437), at
+                   self.safe_shield_threshold or thr, with K = 11 candidates or 2 <= K <= 32.
+                   Of the K blends between the policy's action (j = 0) and actor_safe's mean
+                   action (j = K-1) a step takes the one closest to the policy's whose
+                   certificate is <= the threshold, the safe action if none is, inside the
+                   kernel and as draw-free as the threshold shield. The result carries
+                   ``blend`` (j per step; blend / (K-1) is the safe action's share) and
+                   ``shield_candidates`` as well; ``certificate`` stays that of the policy's
+                   action and ``interventions`` is blend != 0. The evaluation's controller is
+                   imagine(shield='linear', deterministic=True): evaluate acts on the
+                   policy's mean. Refused like the other shields; an unknown string or K
+                   outside 2..32 is a ValueError.
+        shield_uncertainty   whether the certificate is the critic's distributional bound
+                   (needs a distributional critic). Default: solver.distributional_qc under
+                   the threshold shield, False under the linear one, whose candidates the
+                   evaluation scores by the critic's mean."""
         from . import ops
         from .rng import _mix64
         if self.env_params is None:
@@ -317,7 +336,20 @@ class SMBPO(Configurable, Module):
             raise ValueError(f"members: {members!r} (None, an int, {H} ints or 'each')")
         kw = {} if actions is None else {'actions': actions}
         if shield is not None and shield is not False:   # (with actions or a tape: refused by ops)
-            kw['shield'] = float(self.safe_shield_threshold if shield is True else shield)
+            if isinstance(shield, (str, tuple, list)):
+                from .sampling import LINEAR_SHIELD_CANDIDATES
+                kind, thr, K = (shield, None, None) if isinstance(shield, str) else (tuple(shield) + (None,) * 3)[:3]
+                if kind != 'linear' or (not isinstance(shield, str) and not 1 <= len(shield) <= 3):
+                    raise ValueError(f"shield: {shield!r} (True, a threshold, 'linear', ('linear', threshold) or "
+                                     "('linear', threshold, candidates))")
+                kw['shield'] = float(self.safe_shield_threshold if thr is None else thr)
+                kw['shield_candidates'] = LINEAR_SHIELD_CANDIDATES if K is None else K   # 2..32: checked by ops
+            else:
+                kw['shield'] = float(self.safe_shield_threshold if shield is True else shield)
+            if shield_uncertainty is not None:
+                kw['shield_uncertainty'] = shield_uncertainty
+        elif shield_uncertainty is not None:
+            raise ValueError('shield_uncertainty without shield')
         if each or deterministic or not model_noise:
             if noise.parity:
                 raise ValueError("a recorded tape fixes the members and the draws: no 'each', deterministic or "

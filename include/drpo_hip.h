@@ -234,6 +234,35 @@ int drpo_rollout_trajectories_shielded(const drpo_rollout_desc_t* d /* host */,
                                        const drpo_rollout_shield_t* shield /* host; NULL: none */,
                                        const drpo_rollout_traj_t* out /* host */, drpo_stream_t stream);
 
+/* The imagined rollout under the controller every evaluation runs: the actor behind the
+ * linear shield (sample_episodes_batched with shield_type 'linear', src/sampling.py:430-437).
+ * K candidates; blend j = 0 .. K-1 is candidate k = K-1-j of drpo_shield_mix, with its
+ * arithmetic: j = 0 the policy's action, j = K-1 the safe actor's tanh(mu_safe(s)). A row
+ * takes the smallest j < K-1 whose certificate (that of drpo_rollout_trajectories_shielded)
+ * is <= shield->threshold (the float comparison of drpo_shield_select mode 2: a NaN does
+ * not qualify), and j = K-1 if none is: the reference's "start from a_safe, later
+ * candidates override". The safe action's own certificate decides nothing and is not
+ * computed. One certificate pass per candidate tried, inside the fused horizon kernel; a
+ * tile's passes end when none of its alive rows is undecided, so a tile whose rows all
+ * pass at j = 0 costs what the threshold shield costs and never runs the safe actor.
+ *   - Everything of drpo_rollout_trajectories_shielded holds: its descriptors, outputs and
+ *     checks, no draw made or moved. shield->certificate stays the certificate of the
+ *     policy's action, shield->interventions is (j != 0). linear == NULL is that call.
+ *   - linear != NULL with shield == NULL, or candidates outside 2..32: DRPO_EINVAL before
+ *     any launch or memset. With candidates == 2 the controller is the threshold shield
+ *     (but for a NaN certificate, which intervenes here and not there).
+ *   - An automatic 32-row tile that no longer fits the LDS with the [rows][16] floats this
+ *     adds falls back to 16 rows. */
+typedef struct {
+  int candidates;      /* K, 2..32 (the reference: 11) */
+  uint8_t* blend;      /* device [B][H] or NULL: j of the action taken; 0 at and beyond a row's length */
+} drpo_rollout_linear_t;
+
+int drpo_rollout_trajectories_linear(const drpo_rollout_desc_t* d /* host */,
+                                     const drpo_rollout_shield_t* shield /* host */,
+                                     const drpo_rollout_linear_t* linear /* host; NULL: the threshold shield */,
+                                     const drpo_rollout_traj_t* out /* host */, drpo_stream_t stream);
+
 /* batched env constraint functions, e.g. PointRobot.get_constraint_values /
  * check_violation / check_done (src/env/point_robot.py:96-131); h is [n][C] */
 int drpo_env_constraints(int env_id, int tracking_surr_start, int tracking_n_surr, double env_thr0,

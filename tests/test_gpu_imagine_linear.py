@@ -1,0 +1,423 @@
+"""Imagined rollouts under the evaluation's controller, the linear shield
+(SMBPO.imagine(shield='linear'), ops.rollout_trajectories(shield_candidates=),
+drpo_rollout_trajectories_linear: the SH instantiations of rollout_persist_kernel with
+sh_lin_k candidates; the shield of src/sampling.py:430-437).
+
+The scene, the oracle helpers and the tolerances are test_gpu_imagine_shield.py's: B 72
+(16- and 32-row tiles and a partial one of 8), H 3, S 12, A 2, C 2, rows ending at steps 0,
+1 and 2. Between calls of the kernel everything is compared bit for bit; against the oracle
+and the stand-alone device path |d| <= 2e-4 + 2e-4 |ref|.
+
+Blend j = 0 .. K-1: j = 0 the policy's action, j = K-1 the safe actor's, between them
+a_safe * j/(K-1) + a_perf * (1 - j/(K-1)) (candidate K-1-j of drpo_shield_mix). A row takes
+the smallest j < K-1 whose certificate is <= the threshold, K-1 if none is.
+
+Tests 4 and 5 run a scene of their own, the same with the safe actor's mean shifted by
++0.25 before the tanh (_linear_scene): with the safe actor a copy of the actor, as the scene
+has it, the certificate moves by 0.015 along a row's blends and by 0.15 between rows, and 5 %
+of the alive (row, step) pairs end at an intermediate blend (CPU oracle, open loop); the
+conditions of test 4 ask for 10 %."""
+import pytest
+import torch
+
+import drpo_amd
+from drpo_amd import envs, ops, sampling
+from gpu_helpers import DEV
+from oracle import drpo_oracle as O
+from test_gpu_env_program import ProgramQuadrotor, _drifting_quadrotor_alg, _no_host_env  # noqa: F401
+from test_gpu_imagine import TENSORS, _assert_every_length, assert_same, bits
+from test_gpu_imagine_shield import (B, H, INF, MEMBER, PRE, SEED, _params, _scene, _teacher_inputs, _tol)
+from test_gpu_widths import _alg as _width_alg
+from test_gpu_configs import _fill
+
+pytestmark = pytest.mark.gpu
+
+K = sampling.LINEAR_SHIELD_CANDIDATES
+assert K == 11
+SAFE_SHIFT = 0.25
+
+_LIN = {}
+
+
+def _linear_scene():
+    """The 16-row scene with actor_safe's mean (pre-tanh) shifted by SAFE_SHIFT in every
+    action dimension: a scene of its own, the shared one is left as it is."""
+    if 'alg' not in _LIN:
+        alg = _drifting_quadrotor_alg(16)
+        alg.actor_safe.group.view('net.4.bias')[:alg.action_dim] += SAFE_SHIFT
+        _LIN['alg'] = alg
+    return _LIN['alg']
+
+
+def _imagine(alg, seed=SEED, **kw):
+    im = alg.imagine(noise=drpo_amd.DeviceNoise(seed), **kw)
+    torch.cuda.synchronize()
+    return im
+
+
+def assert_shield_same(a, b):
+    """Every tensor, the certificate and the interventions bit for bit."""
+    assert_same(a, b)
+    assert torch.equal(bits(a.certificate), bits(b.certificate))
+    assert torch.equal(a.interventions, b.interventions)
+
+
+def assert_consistent(im, thr):
+    """What the kernel's own outputs owe each other, exact, on every row."""
+    mask = im.mask
+    assert im.blend.dtype == torch.uint8 and im.blend.shape == im.rewards.shape
+    assert im.shield_candidates is not None and int(im.blend.max()) <= im.shield_candidates - 1
+    assert torch.equal(im.interventions, im.blend != 0)
+    assert torch.equal((im.certificate <= thr)[mask], (im.blend == 0)[mask])
+    assert not bool(im.blend[~mask].any()) and not bool(im.certificate[~mask].any())
+    assert not bool(im.interventions[~mask].any())
+
+
+# ------------------------------------------------------------------ 1. K = 2 is the threshold shield
+@pytest.mark.parametrize('rpt', [16, 32])
+def test_two_candidates_are_the_threshold_shield(rpt):
+    alg = _scene(rpt)
+    for unc in (False, True):
+        probe = _imagine(alg, shield=INF, shield_uncertainty=unc)
+        thr = float(probe.certificate[:, 0].median())
+        kw = dict(members=probe.members, shield_uncertainty=unc)
+        ts = _imagine(alg, shield=thr, **kw)
+        ln = _imagine(alg, shield=('linear', thr, 2), **kw)
+        assert ts.blend is None and ts.shield_candidates is None and ln.shield_candidates == 2
+        assert ln.shield_threshold == ts.shield_threshold == thr
+        assert_shield_same(ts, ln)
+        assert torch.equal(ln.blend, ln.interventions.to(torch.uint8))
+        assert_consistent(ln, thr)
+        n_iv = int(ln.interventions[:, 0].sum())
+        assert 0 < n_iv < B, n_iv                  # both branches ran
+        _assert_every_length(ln)
+
+
+# ------------------------------------------------------------------ 2 / 3. the two ends
+def check_linear_plus_inf(alg, unc=None, **kw):
+    """Every row passes at j = 0: the unshielded run bit for bit, the threshold shield's
+    certificate, no blend. Returns the linear run."""
+    base = _imagine(alg, **kw)
+    kw = dict({'members': base.members}, **kw)
+    ts = _imagine(alg, shield=INF, shield_uncertainty=bool(unc), **kw)
+    ln = _imagine(alg, shield=('linear', INF, K), shield_uncertainty=unc, **kw)
+    assert base.blend is None and ts.blend is None
+    assert ln.shield_candidates == K and ln.shield_threshold == INF
+    assert_same(base, ln)
+    assert torch.equal(bits(ts.certificate), bits(ln.certificate))
+    assert not bool(ln.blend.any()) and not bool(ln.interventions.any())
+    assert torch.equal(ln.certificate != 0, ln.mask)
+    assert_consistent(ln, INF)
+    return ln
+
+
+def check_linear_minus_inf(alg, unc=None, **kw):
+    """No candidate passes: K-1 everywhere alive, the replay of the run's own actions, and
+    the safe actor's action."""
+    im = _imagine(alg, shield=('linear', -INF, K), shield_uncertainty=unc, **kw)
+    assert torch.equal(im.blend, (K - 1) * im.mask.to(torch.uint8))
+    assert_consistent(im, -INF)
+    re = _imagine(alg, actions=im.actions, **dict({'members': im.members}, **kw))
+    assert re.given_steps == im.rewards.shape[1] and re.blend is None
+    assert_same(im, re)
+    for t in range(im.rewards.shape[1]):
+        live = im.mask[:, t]
+        ref = alg.actor_safe.act(im.states[:, t], eval=True)
+        err = (im.actions[:, t] - ref).abs()[live]
+        assert bool((err <= 1e-4 + 1e-4 * ref.abs()[live]).all()), (t, float(err.max()))
+    return im
+
+
+def oracle_qc(P, alg, s, a, unc=False):
+    cc = alg.constraint_critic
+    q = O.cons_critic(P, 'constraint_critic.', s, a, 'uncertainty' if unc else 'mean', std_ratio=cc.std_ratio,
+                      rng=O.LiveRNG(), lmin=cc.log_std_min, lmax=cc.log_std_max)
+    return O.get_qc(q, cc.output_dim)
+
+
+def check_certificate_at_step_0(alg, ln, unc=False):
+    """Of a run at +inf (its actions are the actor's): the oracle's certificate at the
+    kernel's own (states[:, 0], actions[:, 0])."""
+    q = oracle_qc(_params(alg), alg, ln.states[:, 0].cpu(), ln.actions[:, 0].cpu(), unc)
+    err = (ln.certificate[:, 0].cpu() - q).abs()
+    print(f'certificate at step 0: {float(q.min()):.4f} .. {float(q.max()):.4f}, max |d| {float(err.max()):.3g}')
+    assert bool((err <= _tol(q)).all()), float(err.max())
+
+
+@pytest.mark.parametrize('rpt', [16, 32])
+def test_threshold_plus_inf_is_the_unshielded_run_bit_for_bit(rpt):
+    ln = check_linear_plus_inf(_scene(rpt))
+    _assert_every_length(ln)
+    check_certificate_at_step_0(_scene(rpt), ln)
+
+
+@pytest.mark.parametrize('rpt', [16, 32])
+def test_threshold_minus_inf_takes_the_safe_action_everywhere(rpt):
+    im = check_linear_minus_inf(_scene(rpt))
+    _assert_every_length(im)
+
+
+# ------------------------------------------------------------------ 4. teacher-forced against the oracle
+def oracle_candidates(P, alg, s, eps_a_t, unc=False):
+    """(mixes [K, n, A], q [K, n]) in blend order j from states s under the recorded draws:
+    the reference's a_safe * ratio + a_perf * (1 - ratio), ratio = j / (K-1)."""
+    mu, std = O.policy_params(P, 'actor.net.', s)
+    a_perf = torch.tanh(mu + std * eps_a_t)
+    a_safe = O.policy_mean(P, 'actor_safe.net.', s)
+    mixes = torch.stack([a_safe * (j / (K - 1)) + a_perf * (1 - j / (K - 1)) for j in range(K)])
+    return mixes, torch.stack([oracle_qc(P, alg, s, m, unc) for m in mixes])
+
+
+def first_passing(q, thr):
+    """The smallest j < K-1 with q[j] <= thr per row, K-1 if none (K = len(q))."""
+    K = len(q)
+    ok = q[:K - 1] <= thr
+    return torch.where(ok.any(0), ok.float().argmax(0), torch.tensor(K - 1))
+
+
+def oracle_open_loop_linear(P, alg, s, eps_a, eps_m, thr):
+    """The oracle alone, open loop: policy -> 11 candidates -> certificates -> choice ->
+    ens_forward1 -> env functions. Returns (histogram of j over the alive (row, step) pairs,
+    rows that ended before the horizon)."""
+    fn = O.env_fns('quadrotor')
+    alive = torch.ones(len(s), dtype=torch.bool)
+    hist = torch.zeros(K, dtype=torch.int64)
+    for t in range(H):
+        mixes, q = oracle_candidates(P, alg, s, eps_a[t])
+        j = first_passing(q, thr)
+        hist += torch.bincount(j[alive], minlength=K)
+        mean, lv = O.ens_forward1(P, PRE, s, mixes[j, torch.arange(len(s))], MEMBER)
+        s = (mean + torch.exp(lv).sqrt() * eps_m[t])[:, :-1]
+        alive = alive & ~torch.as_tensor(fn(s)[0]).reshape(-1).bool()
+    return hist, int((~alive).sum())
+
+
+def assert_choice(j_k, q, thr, live, t):
+    """The kernel's j against reference certificates q [K, n] of the K blends, no row left
+    out: the chosen blend passes and none before it does, each within its tolerance."""
+    K, n = q.shape
+    chosen = q[j_k.long(), torch.arange(n)]
+    taken = live & (j_k < K - 1)
+    bad = taken & ~(chosen <= thr + _tol(chosen))
+    assert not bool(bad.any()), (t, 'chosen blend fails', bad.nonzero().flatten().tolist())
+    before = torch.arange(K).unsqueeze(1) < j_k.long().unsqueeze(0)
+    bad = (before & ~(q > thr - _tol(q))).any(0) & live
+    assert not bool(bad.any()), (t, 'an earlier blend passes', bad.nonzero().flatten().tolist())
+
+
+def class_counts(j, n):
+    return int((j == 0).sum()), int(((j > 0) & (j < K - 1)).sum()), int((j == K - 1).sum()), n
+
+
+def test_inside_the_range_teacher_forced_against_the_oracle():
+    """K = 11, recorded draws (eps_layout 1), member 3, the mean certificate, thr = the median
+    over the 72 start states of the oracle's step-0 certificate of the policy's action; every
+    step checked from the kernel's own states.
+
+    The conditions on the inputs, by the CPU oracle alone, open loop, on _linear_scene (the
+    scene as it is gives 80 / 10 / 102 of 192 alive pairs: 5 % intermediate): thr 0.02462,
+    the step-0 certificate spans -0.057 .. 0.095; j histogram over the 192 alive pairs
+    [80, 2, 5, 5, 4, 7, 5, 16, 10, 16, 42]: 80 at j = 0 (42 %), 70 at the nine intermediate
+    blends (36 %), 42 at j = K-1 (22 %); 24 rows end before the horizon."""
+    alg = _linear_scene()
+    P = _params(alg)
+    s, eps_a, eps_m = _teacher_inputs(alg)
+    thr = float(oracle_candidates(P, alg, s, eps_a[0])[1][0].median())
+    hist, ended = oracle_open_loop_linear(P, alg, s, eps_a, eps_m, thr)
+    n = int(hist.sum())
+    print('oracle open loop: thr', thr, 'j histogram', hist.tolist(), 'ended early', ended)
+    assert hist[0] >= 0.1 * n and hist[1:K - 1].sum() >= 0.1 * n and hist[K - 1] >= 0.1 * n, hist.tolist()
+    assert int((hist[1:K - 1] > 0).sum()) >= 3, hist.tolist()
+    assert ended >= 1
+
+    im = ops.rollout_trajectories(alg, alg.actor, s.to(DEV), drpo_amd.DeviceNoise(5), members=MEMBER,
+                                  eps_a=eps_a.to(DEV).contiguous(), eps_m=eps_m.to(DEV).contiguous(), eps_layout=1,
+                                  shield=thr, shield_candidates=K)
+    torch.cuda.synchronize()
+    assert im.shield_threshold == thr and im.shield_candidates == K
+    assert_consistent(im, thr)
+    cert, blend, acts, mask = im.certificate.cpu(), im.blend.cpu(), im.actions.cpu(), im.mask.cpu()
+    for t in range(H):
+        live = mask[:, t]
+        mixes, q = oracle_candidates(P, alg, im.states[:, t].cpu(), eps_a[t])
+        err = (cert[:, t] - q[0]).abs()[live]
+        assert bool((err <= _tol(q[0])[live]).all()), (t, float(err.max()))
+        assert_choice(blend[:, t], q, thr, live, t)
+        ref = mixes[blend[:, t].long(), torch.arange(B)]
+        aerr = (acts[:, t] - ref).abs()[live]
+        print(f'step {t}: alive {int(live.sum())}, j histogram '
+              f'{torch.bincount(blend[:, t][live].long(), minlength=K).tolist()}, certificate max |d| '
+              f'{float(err.max()):.3g}, action max |d| {float(aerr.max()):.3g}')
+        assert bool((aerr <= _tol(ref)[live]).all()), (t, float(aerr.max()))
+    c0, cmid, clast, n_k = class_counts(blend[mask], int(mask.sum()))
+    assert min(c0, cmid, clast) >= 0.1 * n_k, (c0, cmid, clast, n_k)
+    assert int((im.lengths < H).sum()) >= 1, 'no row ended before the horizon'
+
+
+# ------------------------------------------------------------------ 5. the evaluation's own device path
+def device_candidates(alg, states, K=K):
+    """q [K, n] in blend order j from the stand-alone ops the evaluation runs
+    (sampling.shielded_actions): shield_mix + one constraint-critic forward over K * n rows."""
+    a_perf = alg.solver.act(states, eval=True)
+    a_safe = alg.actor_safe.act(states, eval=True)
+    mixes = ops.shield_mix(a_perf, a_safe, K)                      # candidate k = K-1 - j
+    q = ops.constraint_critic_forward(alg.constraint_critic, states, mixes.reshape(K * len(states), -1), repeat=K)
+    q = q.reshape(K, len(states), -1).max(-1)[0]
+    return q.flip(0).cpu()
+
+
+def near_threshold(q, thr):
+    """Rows one of whose deciding certificates lies within 2 * tol of thr."""
+    K = len(q)
+    return ((q[:K - 1] - thr).abs() <= 2 * _tol(q[:K - 1])).any(0)
+
+
+def test_deterministic_against_the_evaluations_device_path():
+    """imagine(shield='linear', deterministic=True), the evaluation's controller, against
+    sampling.shielded_actions at the kernel's states of each step. Rows with a deciding
+    certificate within 2 * tol of thr may take a neighbouring blend and are compared through
+    the choice check only; they may be at most 20 % of the alive pairs (a condition: the
+    candidates of a crossing row lie 0.003 apart, 2 * tol is 0.0004 each side; the stand-alone
+    path counts 10 of the 72 start states and 24 of the 192 alive pairs)."""
+    alg = _linear_scene()
+    s = _teacher_inputs(alg)[0].to(DEV)
+    q0 = device_candidates(alg, s)
+    thr = float(q0[0].median())
+    assert int(near_threshold(q0, thr).sum()) <= 0.2 * B            # the inputs, by the stand-alone path alone
+    im = alg.imagine(s, shield=('linear', thr, K), deterministic=True, members=MEMBER, noise=drpo_amd.DeviceNoise(5))
+    torch.cuda.synchronize()
+    assert_consistent(im, thr)
+    blend, mask = im.blend.cpu(), im.mask.cpu()
+    unclear = 0
+    for t in range(H):
+        live = mask[:, t]
+        states_t = im.states[:, t].contiguous()
+        q = device_candidates(alg, states_t)
+        err = (im.certificate[:, t].cpu() - q[0]).abs()[live]
+        assert bool((err <= _tol(q[0])[live]).all()), (t, float(err.max()))
+        assert_choice(blend[:, t], q, thr, live, t)
+        clear = live & ~near_threshold(q, thr)
+        unclear += int((live & ~clear).sum())
+        ref = sampling.shielded_actions(alg.solver, states_t, True, thr, 'linear').cpu()
+        aerr = (im.actions[:, t].cpu() - ref).abs()[clear]
+        print(f'step {t}: alive {int(live.sum())}, compared {int(clear.sum())}, j histogram '
+              f'{torch.bincount(blend[:, t][live].long(), minlength=K).tolist()}, action max |d| {float(aerr.max()):.3g}')
+        assert bool((aerr <= _tol(ref)[clear]).all()), (t, float(aerr.max()))
+        assert torch.equal(blend[:, t][clear].long(), first_passing(q, thr)[clear]), t
+    assert unclear <= 0.2 * int(mask.sum()), (unclear, int(mask.sum()))
+    c0, cmid, clast, n_k = class_counts(blend[mask], int(mask.sum()))
+    assert c0 > 0 and cmid > 0 and clast > 0, (c0, cmid, clast, n_k)
+
+
+@pytest.mark.parametrize('k', [3, 32])
+def test_other_candidate_counts_against_the_device_path(k):
+    """K = 3 (one blend between the two actions) and K = 32 (the most): step 0 of the
+    deterministic run against the stand-alone path's K candidates, as in the test above."""
+    alg = _linear_scene()
+    s = _teacher_inputs(alg)[0].to(DEV)
+    q = device_candidates(alg, s, k)
+    thr = float(q[0].median())
+    im = alg.imagine(s, shield=('linear', thr, k), deterministic=True, members=MEMBER, noise=drpo_amd.DeviceNoise(5))
+    torch.cuda.synchronize()
+    assert im.shield_candidates == k
+    assert_consistent(im, thr)
+    blend = im.blend[:, 0].cpu()
+    live = torch.ones(B, dtype=torch.bool)
+    assert_choice(blend, q, thr, live, 0)
+    clear = ~near_threshold(q, thr)
+    # a condition on the inputs: half the rows cross, 32 candidates lie 0.001 apart and the
+    # window is 0.0008 wide, so up to 0.8 * 0.5 of the rows may be near thr
+    assert int(clear.sum()) >= 0.5 * B, int(clear.sum())
+    assert torch.equal(blend[clear].long(), first_passing(q, thr)[clear])
+    mixes = ops.shield_mix(alg.solver.act(s, eval=True), alg.actor_safe.act(s, eval=True), k).flip(0).cpu()
+    ref = mixes[blend.long(), torch.arange(B)]
+    aerr = (im.actions[:, 0].cpu() - ref).abs()
+    print(f'K {k}: j histogram {torch.bincount(blend.long(), minlength=k).tolist()}, compared {int(clear.sum())}, '
+          f'action max |d| {float(aerr.max()):.3g}')
+    assert bool((aerr <= _tol(ref)).all()), float(aerr.max())
+    assert int(blend.max()) == k - 1 and bool(((blend > 0) & (blend < k - 1)).any())
+
+
+# ------------------------------------------------------------------ 6. the other paths
+def test_constraint_program_env(monkeypatch):
+    """PG x SH: the quadrotor through its constraint program (env id 4)."""
+    _no_host_env(monkeypatch)
+    with monkeypatch.context() as mp:
+        mp.setattr(envs, 'ShapeEnv', ProgramQuadrotor)
+        alg = _drifting_quadrotor_alg(16)
+    assert alg.env_params['env_id'] == 4
+    ln = check_linear_plus_inf(alg)
+    _assert_every_length(ln)
+    check_certificate_at_step_0(alg, ln)
+    check_linear_minus_inf(alg)
+
+
+def test_generic_widths():
+    """Actor, critic and model 64 wide on the point robot (C = 1): the runtime-K layers,
+    neither the paired heads nor the LDS-resident actor; 40 start states (two full tiles
+    and one of 8)."""
+    alg = _width_alg('point-robot', 64, 64)
+    rep = _fill(alg, 'point-robot', 8000, 3)
+    m = alg.model_ensemble
+    mean, std = O.normalizer_fit(torch.from_numpy(rep['states']))
+    m.state_normalizer.mean.copy_(mean)
+    m.state_normalizer.std.copy_(std)
+    m._elite_inds = [2, 0, 1]
+    cc = alg.constraint_critic
+    assert cc.hidden_dim != 256 and cc.output_dim == 1
+    assert m.hidden_dim != 200 and alg.actor.spec.dims[1] != 256
+    s40 = alg.replay_buffer.get('states')[::200].clone()
+    assert len(s40) == 40
+    ln = check_linear_plus_inf(alg, states=s40)
+    assert ln.blend.shape == (40, alg.horizon)
+    check_certificate_at_step_0(alg, ln)
+    check_linear_minus_inf(alg, states=s40)
+
+
+def test_distributional_certificate():
+    """shield_uncertainty=True: the certificate is the quantile bound, above the mean on
+    every alive row, so no row blends less than under the mean at the same threshold."""
+    alg = _scene(16)
+    assert alg.solver.distributional_qc
+    ln = check_linear_plus_inf(alg, unc=True)
+    check_certificate_at_step_0(alg, ln, unc=True)
+    check_linear_minus_inf(alg, unc=True)
+    mean = _imagine(alg, shield=('linear', INF, K), members=ln.members)
+    live = ln.mask
+    assert bool((ln.certificate[live] > mean.certificate[live]).all())
+    thr = float(mean.certificate[:, 0].median())
+    lo = _imagine(alg, shield=('linear', thr, K), members=ln.members)
+    hi = _imagine(alg, shield=('linear', thr, K), members=ln.members, shield_uncertainty=True)
+    assert_consistent(lo, thr)
+    assert_consistent(hi, thr)
+    assert bool((hi.blend[:, 0] >= lo.blend[:, 0]).all())
+    assert 0 < int((lo.blend[:, 0] != 0).sum()) < B
+
+
+def test_members_each():
+    """members='each': one launch per elite member with common draws, stacked, blend too;
+    each slice is the single-member call."""
+    alg = _linear_scene()
+    probe = _imagine(alg, 77, shield=('linear', INF, K), members=MEMBER)
+    check_certificate_at_step_0(alg, probe)
+    thr = float(probe.certificate[:, 0].median())
+    E = len(alg.model_ensemble._elite_inds)
+    for th in (INF, -INF, thr):
+        each = _imagine(alg, 77, members='each', shield=('linear', th, K))
+        assert each.states.shape == (E, B, H + 1, alg.state_dim)
+        assert each.blend.shape == each.interventions.shape == each.certificate.shape == (E, B, H)
+        assert each.blend.dtype == torch.uint8 and each.shield_candidates == K and each.shield_threshold == th
+        if th == INF:
+            assert not bool(each.blend.any())
+        if th == -INF:
+            assert torch.equal(each.blend, (K - 1) * each.mask.to(torch.uint8))
+        for k, member in enumerate(alg.model_ensemble._elite_inds):
+            one = _imagine(alg, 77, members=int(member), shield=('linear', th, K))
+            for name in TENSORS:
+                assert torch.equal(bits(getattr(each, name)[k]), bits(getattr(one, name))), (k, name)
+            assert torch.equal(each.blend[k], one.blend)
+            assert torch.equal(each.interventions[k], one.interventions)
+            assert torch.equal(bits(each.certificate[k]), bits(one.certificate))
+            if th == thr:
+                assert_consistent(one, thr)
+                assert 0 < int((one.blend[:, 0] != 0).sum()) < B, k
