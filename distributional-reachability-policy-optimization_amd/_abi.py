@@ -111,6 +111,13 @@ class EnsUpstream(ctypes.Structure):
                 ('b', c_int64), ('S', c_int), ('Z', c_int), ('minlv', P), ('maxlv', P), ('gscale', P), ('part', P)]
 
 
+class EnsSpread(ctypes.Structure):
+    """drpo_ens_spread_t"""
+    _fields_ = [('D', P), ('LVR', P), ('s', P), ('n', c_int64), ('S', c_int), ('Z', c_int), ('minlv', P), ('maxlv', P),
+                ('zsel', P), ('M', c_int), ('scale', P), ('mean', P), ('epistemic_std', P), ('aleatoric_std', P),
+                ('disagreement', P), ('epistemic', P), ('aleatoric', P)]
+
+
 # name -> (restype, argtypes)
 PROTOTYPES = {
     'drpo_version': (c_int, []),
@@ -150,6 +157,7 @@ PROTOTYPES = {
                                       c_int, c_int, P, P, P, P]),
     'drpo_ens_head': (c_int, [P, P, P, c_int64, c_int64, c_int, c_int, P, P, P, P, c_uint64, c_uint64, P, P, P, P,
                               P]),
+    'drpo_ens_spread': (c_int, [POINTER(EnsSpread), P]),
     'drpo_ens_loss_workspace_size': (c_size_t, [c_int64, c_int, c_int]),
     'drpo_ens_loss': (c_int, [POINTER(EnsUpstream), POINTER(EnsReduce), P, P, POINTER(EnsReduce), P]),
 }

@@ -8,6 +8,10 @@
 //  drpo_ens_head    Gaussian head: mu = diff + [s, 0], the soft log-var clamp, and
 //                   optionally a sample mu + sqrt(exp(lv)) * eps split into (s', r)
 //                   (src/dynamics.py:112-134,198-234)
+//  drpo_ens_spread  the statistics ACROSS members of an all-member forward on shared rows:
+//                   mean prediction, std of the members' means, root mean predicted
+//                   variance, largest pair distance (extends means / mean / elite_samples,
+//                   src/dynamics.py:206-234, which leave the reduction to the caller)
 //  drpo_ens_loss    heteroscedastic NLL per member + log-var bound term, and its
 //                   gradients w.r.t. the head outputs and min/max_log_var
 //                   (src/dynamics.py:143-153,236-253)
@@ -142,6 +146,167 @@ DRPO_API int drpo_ens_head(const float* D, const float* LVR, const float* s, int
   ens_head_kernel<<<grid, 256, 0, stream>>>(D, LVR, s, s_zstride, n, S, minlv, maxlv, zsel, eps, seed, ctr, mu, lv, s2,
                                             r);
   DRPO_LAUNCH_CHECK("ens_head");
+  return DRPO_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Spread of the members' predictions (the reduction across members)
+// ---------------------------------------------------------------------------
+// The split of ens_loss_kernel: thread t owns column lane k = t % KP of row r0 + t / KP (KP =
+// S+1 rounded up to a power of two in 16..256), so a block is 256 / KP whole rows and reads
+// 256 / KP * (S+1) consecutive floats of each member. Per chunk of KP columns (one chunk
+// unless S+1 > 256):
+//   1. the column's M values go to LDS (xd[m][t]) and into a sum, in list order; a second
+//      pass over the thread's own LDS slots forms the variance about their mean. Only D is
+//      read: the residual s is common to the members and would cost the difference its bits
+//      (s ~ 1e4, D ~ 1e-3). The mean predicted variance is a third loop, over LVR.
+//   2. the M (M-1) / 2 member pairs of a row are dealt to the row's KP lanes. A lane walks
+//      the columns of its pair in column order through LDS, so a pair's sum does not depend
+//      on which lane took it or on the order of the two members: (a - b)^2 == (b - a)^2.
+// The per-row sums and the pair maximum are then reduced over the row's lanes (shuffles, and
+// through LDS in wave order where a row spans waves): shapes that depend on S alone, so a
+// row's results do not depend on n or on the row's place in a block. No atomics and no
+// hand-off between workgroups.
+constexpr int SPREAD_MAX_M = 32;
+constexpr int SPREAD_LDM = 257;   // xd member stride: the pair loop's lanes differ in member, 257 = 1 (mod 64) spreads them over banks
+
+inline int spread_kp(int S1) { return S1 > 256 ? 256 : loss_kp(S1); }
+
+namespace {
+
+// sum / max of v over the KP lanes of a row; every thread of the block calls it
+template <bool MAX>
+__device__ __forceinline__ float spread_row_reduce(float v, int KP, float* red, int tid) {
+  const int w = KP < 64 ? KP : 64;
+  for (int o = w >> 1; o > 0; o >>= 1) {
+    const float u = __shfl_xor(v, o, 64);
+    v = MAX ? fmaxf(v, u) : v + u;
+  }
+  if (KP <= 64) return v;
+  __syncthreads();                      // red is free again
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  const int nw = KP >> 6, w0 = (tid >> 6) & ~(nw - 1);   // the row's waves, in order
+  float t = red[w0];
+  for (int i = 1; i < nw; ++i) t = MAX ? fmaxf(t, red[w0 + i]) : t + red[w0 + i];
+  return t;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void ens_spread_kernel(drpo_ens_spread_t a, int KP) {
+  extern __shared__ float spread_lds[];
+  const int M = a.M, S = a.S, S1 = S + 1;
+  float* xd = spread_lds;               // [M][SPREAD_LDM]: this chunk's d, by member and thread
+  float* wl = xd + M * SPREAD_LDM;      // [256]: this chunk's column weights
+  float* red = wl + 256;                // [4]
+  const int tid = threadIdx.x, lane = tid % KP, rl = tid / KP, RP = 256 / KP;
+  const int64_t row = (int64_t)blockIdx.x * RP + rl;
+  const int64_t zs = a.n * S1;          // member stride of D, LVR
+  const bool live = row < a.n;
+  const bool wide = S1 > KP;            // several chunks (KP == 256, one row per block)
+  const int P = M * (M - 1) / 2;
+  const float fM = (float)M;
+  float epi = 0.f, ale = 0.f, best = 0.f;
+  float acc0 = 0.f, acc1 = 0.f;         // wide: the sums of this lane's (at most two) pairs over the chunks so far
+  for (int c0 = 0; c0 < S1; c0 += KP) {
+    const int k = c0 + lane;
+    const float wk = k < S1 ? (a.scale ? a.scale[k] : 1.f) : 0.f;
+    if (c0 > 0) __syncthreads();        // the previous chunk's pair loop is through with xd, wl
+    if (rl == 0) wl[lane] = wk;
+    if (live && k < S1) {
+      const int64_t o = row * S1 + k;
+      float sum = 0.f;
+#pragma unroll 4
+      for (int m = 0; m < M; ++m) {
+        const float d = a.D[(int64_t)(a.zsel ? a.zsel[m] : m) * zs + o];
+        xd[m * SPREAD_LDM + tid] = d;
+        sum += d;
+      }
+      const float dbar = sum / fM;
+      float var = 0.f;
+      for (int m = 0; m < M; ++m) {
+        const float c = xd[m * SPREAD_LDM + tid] - dbar;
+        var += c * c;
+      }
+      var /= fM;
+      if (a.mean) a.mean[o] = (k < S ? a.s[row * S + k] : 0.f) + dbar;
+      if (a.epistemic_std) a.epistemic_std[o] = sqrtf(var);
+      epi += wk * wk * var;
+      if (a.aleatoric_std || a.aleatoric) {
+        const float lo = a.minlv[k], hi = a.maxlv[k];
+        float av = 0.f;
+#pragma unroll 4
+        for (int m = 0; m < M; ++m)
+          av += expf(lv_clamp(a.LVR[(int64_t)(a.zsel ? a.zsel[m] : m) * zs + o], lo, hi));
+        av /= fM;
+        if (a.aleatoric_std) a.aleatoric_std[o] = sqrtf(av);
+        ale += wk * wk * av;
+      }
+    }
+    if (a.disagreement && P > 0) {
+      __syncthreads();
+      const int kc = min(KP, S1 - c0);
+      if (live) {
+        int j = 0;
+        for (int p = lane; p < P; p += KP, ++j) {
+          int m1 = 0, rem = p;          // pair p -> members m1 < m2 of the list
+          while (rem >= M - 1 - m1) {
+            rem -= M - 1 - m1;
+            ++m1;
+          }
+          const float* x1 = xd + m1 * SPREAD_LDM + rl * KP;
+          const float* x2 = xd + (m1 + 1 + rem) * SPREAD_LDM + rl * KP;
+          float q = wide ? (j == 0 ? acc0 : acc1) : 0.f;
+          for (int kk = 0; kk < kc; ++kk) {
+            const float t = wl[kk] * (x1[kk] - x2[kk]);
+            q += t * t;
+          }
+          if (!wide) best = fmaxf(best, q);
+          else if (j == 0) acc0 = q;
+          else acc1 = q;
+        }
+      }
+    }
+  }
+  if (wide) best = fmaxf(acc0, acc1);
+  // sqrt is monotone: the root of the largest squared distance is the largest distance
+  if (a.disagreement) {
+    best = spread_row_reduce<true>(best, KP, red, tid);
+    if (live && lane == 0) a.disagreement[row] = sqrtf(best);
+  }
+  if (a.epistemic) {
+    epi = spread_row_reduce<false>(epi, KP, red, tid);
+    if (live && lane == 0) a.epistemic[row] = sqrtf(epi);
+  }
+  if (a.aleatoric) {
+    ale = spread_row_reduce<false>(ale, KP, red, tid);
+    if (live && lane == 0) a.aleatoric[row] = sqrtf(ale);
+  }
+}
+
+DRPO_API int drpo_ens_spread(const drpo_ens_spread_t* a, drpo_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  DRPO_REQUIRE(a, "drpo_ens_spread: null descriptor");
+  const bool alea = a->aleatoric_std || a->aleatoric;
+  DRPO_REQUIRE(a->mean || a->epistemic_std || a->disagreement || a->epistemic || alea,
+               "drpo_ens_spread: no output requested");
+  DRPO_REQUIRE(a->D, "drpo_ens_spread: null D");
+  DRPO_REQUIRE(a->s || !a->mean, "drpo_ens_spread: mean needs s");
+  DRPO_REQUIRE(a->LVR || !alea, "drpo_ens_spread: an aleatoric output needs LVR");
+  DRPO_REQUIRE((a->minlv && a->maxlv) || !alea, "drpo_ens_spread: an aleatoric output needs minlv and maxlv");
+  DRPO_REQUIRE(a->n >= 0 && a->S >= 1 && a->Z >= 1, "drpo_ens_spread: n=%lld S=%d Z=%d out of range", (long long)a->n,
+               a->S, a->Z);
+  DRPO_REQUIRE(a->M >= 1 && a->M <= SPREAD_MAX_M, "drpo_ens_spread: members M outside 1..32");
+  DRPO_REQUIRE(a->zsel || a->Z <= SPREAD_MAX_M, "drpo_ens_spread: zsel NULL with Z=%d > 32", a->Z);
+  DRPO_REQUIRE(a->zsel || a->M == a->Z, "drpo_ens_spread: zsel NULL means members 0..Z-1: M=%d, Z=%d", a->M, a->Z);
+  if (a->n == 0) return DRPO_OK;
+  const int KP = spread_kp(a->S + 1), RP = 256 / KP;
+  const int64_t nb = (a->n + RP - 1) / RP;
+  DRPO_REQUIRE(nb <= 0x7fffffff, "drpo_ens_spread: %lld rows", (long long)a->n);
+  const size_t lds = sizeof(float) * ((size_t)a->M * SPREAD_LDM + 256 + 4);
+  ens_spread_kernel<<<(unsigned)nb, 256, lds, stream>>>(*a, KP);
+  DRPO_LAUNCH_CHECK("ens_spread");
   return DRPO_OK;
 }
 

@@ -148,6 +148,39 @@ class BatchedGaussianEnsemble(Configurable, Module):
     def elite_samples(self, states, actions, noise=None):
         return self.engine.elite_samples(states, actions, list(self._elite_inds), noise)
 
+    def disagreement(self, states, actions, members=None, scale=None):
+        """Where the model does not know: how far the members' predictions for each row
+        (s, a) are apart (ops.EnsembleSpread), from one all-member forward and one reduction
+        launch (drpo_ens_spread); no per-member output is made.
+
+        members   None: the elites (_elite_inds, the members rollouts draw from); 'all':
+                  every member; or a sequence of 1..32 member indices (repeats allowed).
+        scale     column weights of the per-row numbers. None: the model's own normalised
+                  state units, 1 / (state_normalizer.std + epsilon) on the state columns and
+                  0 on the reward, so they read "in standard deviations of the state". A
+                  tensor [S] (reward weight 0) or [S+1]."""
+        E, S = self.ensemble_size, self.state_dim
+        if members is None:
+            members = self.__dict__.get('_elite_inds')
+            if not members:
+                raise ValueError('disagreement: the model has no elites before its first fit; pass members=')
+        elif isinstance(members, str):
+            if members != 'all':
+                raise ValueError(f"disagreement: members {members!r} (None, 'all' or member indices)")
+            members = range(E)
+        members = [int(m) for m in members]
+        if not 1 <= len(members) <= 32:
+            raise ValueError(f'disagreement: {len(members)} members (1..32)')
+        if any(not 0 <= m < E for m in members):
+            raise ValueError(f'disagreement: members {members} of an ensemble of {E}')
+        if scale is not None:
+            scale = torch.as_tensor(scale, dtype=torch.float32).reshape(-1)
+            if scale.numel() == S:
+                scale = torch.cat([scale, scale.new_zeros(1)])
+            if scale.numel() != S + 1:
+                raise ValueError(f'disagreement: scale has {scale.numel()} entries, not {S} or {S + 1}')
+        return self.engine.spread(states, actions, members, scale)
+
     def compute_loss(self, states, actions, targets):
         from .ensemble_engine import EnsembleLoss
         anchor = self.__dict__.get('_anchor')

@@ -7,6 +7,8 @@ small row-wise kernels (csrc/ensemble.hip):
 
   forward     drpo_mlp_forward (trunk + diff head + log-var head in one launch)
               -> drpo_ens_head (residual mean, soft log-var clamp [, sample])
+  spread      forward of every member on shared rows (member stride 0) -> drpo_ens_spread
+              (the statistics across members; no per-member output)
   holdout     drpo_ens_gather_steps -> forward with member stride 0 (the reference's
               .repeat(E, 1) without the copy) -> drpo_ens_loss (no grads)
   fit         drpo_ens_gather_steps once per chunk of steps (every step's minibatch in one
@@ -47,7 +49,7 @@ from . import _lib
 from .optim import OPT_MAXSEG, fused_step
 from .rng import DeviceNoise
 from .mlp_desc import ACT_ID, Net, fill_bwd, fill_fwd, wgrad_workspace
-from ._abi import EnsReduce, EnsUpstream, WgradItem
+from ._abi import EnsReduce, EnsSpread, EnsUpstream, WgradItem
 
 
 # Forward: one workgroup per (row tile, head) when the plain grid (16-row tiles x
@@ -121,6 +123,7 @@ class EnsembleEngine:
         self.fit_fb_enabled = True   # forward + NLL + backward-data as one launch (drpo_ens_fit_fb)
         self.ws = {}
         self.wg_ws = {}
+        self._zsel = {}
         self.noise = None
         self.dev = model.group.data.device
         from .distributed import GradReducer
@@ -276,6 +279,51 @@ class EnsembleEngine:
         o = self._head(nets[1].sy[-1], nets[2].sy[-1], s, 0, n, len(elites), zsel=elites, eps=eps, noise=noise,
                        outputs=('s2',))
         return o['s2'], o['r']
+
+    # rows per forward + reduction of spread(): bounds the [E, rows, S+1] head-output workspace
+    spread_chunk_rows = 65536
+
+    def spread(self, s, a, members, scale):
+        """BatchedGaussianEnsemble.disagreement: per chunk of rows one all-member forward on
+        shared rows (as elite_samples) and drpo_ens_spread over its raw head outputs. Rows are
+        independent, so the chunk size does not change a bit of the result. scale None: the
+        model's normalised state units. What the reduction alone needs (outputs, member list,
+        weights) is made after the first forward is under way, not in front of it."""
+        from .ops import EnsembleSpread
+        m = self.m
+        S, A, E = m.state_dim, m.action_dim, m.ensemble_size
+        s, a = self._prep(s.reshape(-1, S), a.reshape(-1, A))
+        n, S1 = len(s), S + 1
+        if n == 0:
+            return EnsembleSpread(list(members), *(s.new_empty(0, S1) for _ in range(3)),
+                                  *(s.new_empty(0) for _ in range(3)))
+        out = EnsembleSpread(list(members), *[None] * 6)
+        d = EnsSpread()
+        d.S, d.Z, d.M = S, E, len(out.members)
+        d.minlv, d.maxlv = m.min_log_var.data_ptr(), m.max_log_var.data_ptr()
+        chunk = max(1, int(self.spread_chunk_rows))
+        for r0 in range(0, n, chunk):
+            c = min(chunk, n - r0)
+            nets, _, _ = self._forward(s[r0:r0 + c], a[r0:r0 + c], c, E, 0, 0)
+            if r0 == 0:
+                for k in EnsembleSpread.TENSORS[:3]:
+                    setattr(out, k, torch.empty(n, S1, device=self.dev))
+                for k in EnsembleSpread.TENSORS[3:]:
+                    setattr(out, k, torch.empty(n, device=self.dev))
+                zsel = self._zsel.get(tuple(out.members))       # device copies of the member lists seen
+                if zsel is None:
+                    zsel = self._zsel[tuple(out.members)] = torch.tensor(out.members, dtype=torch.int32,
+                                                                         device=self.dev)
+                if scale is None:
+                    norm = m.state_normalizer
+                    scale = torch.nn.functional.pad(1.0 / (norm.std + norm.epsilon), (0, 1))
+                scale = scale.to(self.dev).contiguous().float()
+                d.zsel, d.scale = zsel.data_ptr(), scale.data_ptr()
+            d.D, d.LVR, d.s, d.n = nets[1].sy[-1].data_ptr(), nets[2].sy[-1].data_ptr(), s[r0:].data_ptr(), c
+            for k in EnsembleSpread.TENSORS:
+                setattr(d, k, getattr(out, k)[r0:].data_ptr())
+            _lib.check(_lib.lib().drpo_ens_spread(ctypes.byref(d), _lib.stream()), 'ens_spread')
+        return out
 
     # ------------------------------------------------------------------ loss / grads
     def _loss_ws(self, tag, b, Z):

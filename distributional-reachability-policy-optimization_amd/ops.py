@@ -241,9 +241,14 @@ class ImaginedRollout:
       blend [B, H] uint8         j of the action taken: 0 the policy's, K-1 the safe actor's,
                                  between them the blend with share blend / (K-1) of the safe
                                  action; interventions is blend != 0
-      shield_candidates          K"""
+      shield_candidates          K
+    With imagine(uncertainty=) four more, None otherwise (EnsembleSpread's per-row numbers
+    at (states[i, t], actions[i, t]), in the model's normalised state units):
+      disagreement, epistemic, aleatoric [B, H]   zero at and beyond a row's length
+      max_disagreement [B]       the largest disagreement over the row's steps"""
     TENSORS = ('states', 'actions', 'rewards', 'constraint_values', 'dones', 'violations', 'lengths', 'returns',
                'max_constraint', 'first_violation', 'terminated')
+    UNCERTAINTY = ('disagreement', 'epistemic', 'aleatoric', 'max_disagreement')
 
     def __init__(self, members, given_steps=0, **tensors):
         assert set(tensors) == set(self.TENSORS)
@@ -251,12 +256,22 @@ class ImaginedRollout:
         self.given_steps = given_steps
         self.interventions = self.certificate = self.shield_threshold = None
         self.blend = self.shield_candidates = None
+        self.disagreement = self.epistemic = self.aleatoric = self.max_disagreement = None
         self.__dict__.update(tensors)
 
     @property
     def mask(self):
         H = self.rewards.shape[-1]
         return torch.arange(H, device=self.lengths.device) < self.lengths.unsqueeze(-1)
+
+    def first_uncertain(self, threshold):
+        """[B] int32: the first step of the row's life whose disagreement exceeds
+        ``threshold``, -1 if none (first_violation's counterpart; needs uncertainty=)."""
+        if self.disagreement is None:
+            raise ValueError('first_uncertain needs imagine(uncertainty=)')
+        over = (self.disagreement > threshold) & self.mask
+        first = over.to(torch.int32).argmax(dim=-1).to(torch.int32)
+        return torch.where(over.any(dim=-1), first, torch.full_like(first, -1))
 
     @classmethod
     def stack(cls, runs):
@@ -269,7 +284,31 @@ class ImaginedRollout:
         if runs[0].blend is not None:
             out.blend = torch.stack([r.blend for r in runs])
             out.shield_candidates = runs[0].shield_candidates
+        if runs[0].disagreement is not None:
+            for k in cls.UNCERTAINTY:
+                setattr(out, k, torch.stack([getattr(r, k) for r in runs]))
         return out
+
+
+class EnsembleSpread:
+    """How far the ensemble members' predictions for n rows (s, a) are apart
+    (BatchedGaussianEnsemble.disagreement, drpo_ens_spread), over the member list
+    ``members``. Per column k of [next state | reward]:
+
+      mean [n, S+1]            the mean prediction over the members
+      epistemic_std [n, S+1]   population std of the members' means
+      aleatoric_std [n, S+1]   root of the mean predicted variance; the squares of the two
+                               stds add up to the mixture's predictive variance
+    and per row, with the column weights ``scale`` of the call:
+      disagreement [n]         the largest distance between two members' predictions (0 for one member)
+      epistemic [n]            sqrt(sum_k scale_k^2 epistemic_std_k^2)
+      aleatoric [n]            sqrt(sum_k scale_k^2 aleatoric_std_k^2)"""
+    TENSORS = ('mean', 'epistemic_std', 'aleatoric_std', 'disagreement', 'epistemic', 'aleatoric')
+
+    def __init__(self, members, mean, epistemic_std, aleatoric_std, disagreement, epistemic, aleatoric):
+        self.members = members
+        self.mean, self.epistemic_std, self.aleatoric_std = mean, epistemic_std, aleatoric_std
+        self.disagreement, self.epistemic, self.aleatoric = disagreement, epistemic, aleatoric
 
 
 class ModelRolloutError:
@@ -281,12 +320,17 @@ class ModelRolloutError:
       state_error [n, k]     || (imagined.states[:, t+1] - real next_states[starts+t]) / (state_std + 1e-7) ||_2
       reward_error [n, k]    | imagined.rewards[:, t] - real rewards[starts+t] |
       alive [n, k] bool      the imagined mask; both errors are NaN where it is False
+    With uncertainty=True, None otherwise:
+      disagreement, epistemic [n, k]   EnsembleSpread's over the elites at (imagined.states[:, t],
+                             actions[:, t]) with the weights 1 / (state_std + 1e-7) of state_error
+                             (reward weight 0), so in its units; NaN where alive is False
 
     members='each' adds a leading elite axis to everything but ``starts``."""
 
-    def __init__(self, starts, imagined, state_error, reward_error, alive):
+    def __init__(self, starts, imagined, state_error, reward_error, alive, disagreement=None, epistemic=None):
         self.starts, self.imagined = starts, imagined
         self.state_error, self.reward_error, self.alive = state_error, reward_error, alive
+        self.disagreement, self.epistemic = disagreement, epistemic
 
     def deciles(self, t):
         """Deciles (0, 10, .., 100 %) of state_error[..., t] over the rows alive at step t."""

@@ -255,7 +255,7 @@ class SMBPO(Configurable, Module):
 
     def imagine(self, states=None, policy=None, horizon=None, *, members=None, deterministic=False,
                 model_noise=True, discount=None, noise=None, actions=None, shield=None,
-                shield_uncertainty=None):
+                shield_uncertainty=None, uncertainty=None):
         """What the model predicts happens from ``states`` under ``policy``: the rollout of
         src/smbpo.py:229-249 kept per trajectory (ops.ImaginedRollout: row i of every tensor
         is the trajectory from start state i), on the fused horizon kernel. Nothing of the
@@ -308,7 +308,15 @@ class SMBPO(Configurable, Module):
         shield_uncertainty   whether the certificate is the critic's distributional bound
                    (needs a distributional critic). Default: solver.distributional_qc under
                    the threshold shield, False under the linear one, whose candidates the
-                   evaluation scores by the critic's mean."""
+                   evaluation scores by the critic's mean.
+        uncertainty   None / False: nothing more. True: where the model does not know along
+                   the trajectories, the ensemble's spread over the elites at every
+                   (states[i, t], actions[i, t]) (model_ensemble.disagreement, one pass over
+                   the B * H rows after the rollout): the result carries ``disagreement``,
+                   ``epistemic``, ``aleatoric`` and ``max_disagreement``, and
+                   first_uncertain(threshold) reads them. 'all': over every member. A
+                   post-pass: it works with every other argument, makes no draw, moves no
+                   counter and changes no other tensor of the result."""
         from . import ops
         from .rng import _mix64
         if self.env_params is None:
@@ -318,6 +326,8 @@ class SMBPO(Configurable, Module):
         H = self.horizon if horizon is None else int(horizon)
         if not 1 <= H <= ops.TRAJ_MAX_H:
             raise ValueError(f'horizon {H}: imagine runs the fused engine, 1 <= horizon <= {ops.TRAJ_MAX_H}')
+        if not (uncertainty is None or isinstance(uncertainty, bool) or uncertainty == 'all'):
+            raise ValueError(f"uncertainty: {uncertainty!r} (None, True or 'all')")
         policy = self.actor if policy is None else policy
         if noise is None:
             if self.__dict__.get('_imagine_noise') is None:
@@ -370,8 +380,22 @@ class SMBPO(Configurable, Module):
         def run(m):
             return ops.rollout_trajectories(self, policy, states, noise, members=m, weights=weights, horizon=H, **kw)
         if each:
-            return ops.ImaginedRollout.stack([run(int(m)) for m in self.model_ensemble._elite_inds])
-        return run(members)
+            im = ops.ImaginedRollout.stack([run(int(m)) for m in self.model_ensemble._elite_inds])
+        else:
+            im = run(members)
+        if uncertainty:
+            self._imagined_uncertainty(im, None if uncertainty is True else 'all')
+        return im
+
+    def _imagined_uncertainty(self, im, members, scale=None):
+        """The ensemble's spread at every step of imagined trajectories (imagine(uncertainty=)):
+        fills im.disagreement, epistemic, aleatoric and max_disagreement."""
+        sp = self.model_ensemble.disagreement(im.states[..., :-1, :], im.actions, members=members, scale=scale)
+        mask = im.mask
+        for k in ('disagreement', 'epistemic', 'aleatoric'):
+            v = getattr(sp, k).reshape(mask.shape)
+            setattr(im, k, torch.where(mask, v, torch.zeros_like(v)))
+        im.max_disagreement = im.disagreement.max(dim=-1).values    # >= 0, and 0 beyond a row's length
 
     def update_models(self, model_steps, noise=None):
         """src/smbpo.py:214-227."""
@@ -464,14 +488,17 @@ class SMBPO(Configurable, Module):
             errors = torch.norm((predicted[i] - next_states) / (state_std + 1e-7), dim=1)
             log.message(f'Model {i + 1} error deciles: {deciles(errors)}')
 
-    def model_rollout_error(self, horizon, *, max_segments=None, members=None, model_noise=False, noise=None):
+    def model_rollout_error(self, horizon, *, max_segments=None, members=None, model_noise=False, noise=None,
+                            uncertainty=False):
         """The k-step open-loop model error on the real buffer (k = ``horizon``): the model
         rolled forward from the first state of a real episode segment under the actions
         the episode actually took, against the states it actually reached. One ``imagine``
         call (given actions at every step, so the policy never runs) over at most
         ``max_segments`` (default rollout_batch_size) of the buffer's k-step segments,
         evenly spaced over their chronological list (no RNG). Returns an
-        ops.ModelRolloutError. Changes nothing of the training state and logs nothing."""
+        ops.ModelRolloutError. Changes nothing of the training state and logs nothing.
+        uncertainty=True adds the elites' ``disagreement`` and ``epistemic`` along the imagined
+        segments in the units of ``state_error``: does disagreement predict the real error?"""
         from . import ops
         from .sampling import episode_segments
         k = int(horizon)
@@ -495,7 +522,12 @@ class SMBPO(Configurable, Module):
         nan = torch.full((), float('nan'), device=self.device)
         se = torch.norm((im.states[..., 1:, :] - s2[rows]) / (state_std + 1e-7), dim=-1)
         re = (im.rewards - r[rows].reshape(len(starts), k)).abs()
-        return ops.ModelRolloutError(starts, im, torch.where(alive, se, nan), torch.where(alive, re, nan), alive)
+        out = ops.ModelRolloutError(starts, im, torch.where(alive, se, nan), torch.where(alive, re, nan), alive)
+        if uncertainty:
+            self._imagined_uncertainty(im, None, scale=1.0 / (state_std + 1e-7))
+            out.disagreement = torch.where(alive, im.disagreement, nan)
+            out.epistemic = torch.where(alive, im.epistemic, nan)
+        return out
 
     def _consume_chunk_draws(self, n, noise):
         """The reference's constraint_critic(sample=True) draws one randn_like per

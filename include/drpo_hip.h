@@ -692,6 +692,41 @@ int drpo_ens_gather_steps(const float* states, const float* actions, const float
 int drpo_ens_head(const float* D, const float* LVR, const float* s, int64_t s_zstride, int64_t n, int S, int nz_out,
                   const float* minlv, const float* maxlv, const int* zsel, const float* eps, uint64_t seed,
                   uint64_t ctr, float* mu, float* lv, float* s2, float* r, drpo_stream_t stream);
+/* How far the members' predictions for one (s, a) are apart: the reduction ACROSS members of
+ * an all-member forward's raw head outputs (the inputs of drpo_ens_head, shared rows), in
+ * one row-wise launch. It extends means / mean / elite_samples (src/dynamics.py:206-234),
+ * which hand the E member predictions back for the caller to reduce, with the statistics
+ * themselves, so that no [E][n][S+1] output is written. Over the member list z_0..z_{M-1}
+ * (zsel; members may repeat, the order is free), with d_m = D[z_m][r][k] and l_m the soft-
+ * clamped log-variance of LVR[z_m][r][k] (drpo_ens_head's clamp), per column k = 0..S:
+ *   mean           (k < S ? s[r][k] : 0) + (1/M) sum_m d_m
+ *   epistemic_std  sqrt((1/M) sum_m (d_m - mean_m d)^2), two passes over D: the residual s
+ *                  is the same for every member and never enters
+ *   aleatoric_std  sqrt((1/M) sum_m exp(l_m))
+ * and per row, with the column weights w = scale:
+ *   disagreement   max over member pairs of sqrt(sum_k (w_k (d_m,k - d_m',k))^2); 0 at M = 1
+ *   epistemic      sqrt(sum_k w_k^2 epistemic_std_k^2)
+ *   aleatoric      sqrt(sum_k w_k^2 aleatoric_std_k^2)
+ * Every output pointer is optional (NULL: not computed); at least one is needed. */
+typedef struct drpo_ens_spread_s {
+  const float* D;              /* [Z][n][S+1] diff-head outputs, member-major */
+  const float* LVR;            /* [Z][n][S+1] raw log-variances; NULL without an aleatoric output */
+  const float* s;              /* [n][S] states, shared by all members; NULL without mean */
+  int64_t n;
+  int S, Z;
+  const float* minlv;          /* [S+1] log-variance bounds; NULL without an aleatoric output */
+  const float* maxlv;
+  const int* zsel;             /* device int[M]; NULL: members 0..Z-1 (M == Z <= 32) */
+  int M;                       /* 1..32 */
+  const float* scale;          /* [S+1] column weights of the per-row outputs; NULL: all ones */
+  float* mean;                 /* [n][S+1] */
+  float* epistemic_std;        /* [n][S+1] */
+  float* aleatoric_std;        /* [n][S+1] */
+  float* disagreement;         /* [n] */
+  float* epistemic;            /* [n] */
+  float* aleatoric;            /* [n] */
+} drpo_ens_spread_t;
+int drpo_ens_spread(const drpo_ens_spread_t* desc /* host */, drpo_stream_t stream);
 /* per-member NLL (_mse_loss, src/dynamics.py:236-253), total compute_loss (:143-153)
  * and, when gD != NULL, its gradients (scaled by *up->gscale if given; gmin / gmax are
  * accumulated into). up: the head outputs, rows, bounds and the workspace
