@@ -22,8 +22,8 @@ def _dev(x, device, dtype=None):
 # rollout (src/smbpo.py:229-249)
 # ---------------------------------------------------------------------------
 def _tape_rollout_noise(noise, H, B, A, S1):
-    """Parity mode: pull the reference's rollout draws from the tape. Returns
-    (init_idx, members, eps_a [H,B,A], eps_m [H,B,S1], per-step row counts)."""
+    """Parity mode: pull the reference's rollout draws from the tape. Returns (elite picks,
+    per-step row counts, eps_a [H,B,A], eps_m [H,B,S1])."""
     eps_a = np.zeros((H, B, A), np.float32)
     eps_m = np.zeros((H, B, S1), np.float32)
     ks, ns = [], []
@@ -69,31 +69,39 @@ _VB_FIELDS = ('_states', '_actions', '_next_states', '_rewards', '_constraint_va
 _ROLLOUT_CACHE_MAX = 8
 
 
-def _rollout_static(alg, policy, B, H):
-    """The per-(shapes, parameter groups, buffers) part of the rollout descriptor: the
-    packed-mirror and bias pointers, env parameters, normalizer / log-var bound and
-    virtual-buffer pointers, and the workspace. Built once and cached on ``alg``; per
-    call only the members, the noise, the initial-state source and the events change.
-    (Building it took ~20 tensor views per call: most of the call's host time.)"""
-    vb = alg.virt_buffer._module
+def _rollout_static(alg, policy, B, H, buffer):
+    """The per-(shapes, parameter groups, buffers) part of a rollout descriptor: the
+    packed-mirror and bias pointers, env parameters, normalizer / log-var bound and the
+    workspace. Built once and cached on ``alg``; per call only the members, the noise, the
+    initial-state source and the events change (_fill_call). (Building it took ~20 tensor
+    views per call: most of the call's host time.)
+    buffer=True, drpo_rollout's entry: with the virtual-buffer pointers, which are part of
+    the key, and the workspace's row count. buffer=False, the drpo_rollout_trajectories*
+    calls' entry: a cache, descriptor and workspace of its own (never the one drpo_rollout's
+    pointers live in), the virtual-buffer fields NULL, no count. Returns (descriptor, its
+    members array, the count or None, the uploaded program or None: kept alive here)."""
     # every device pointer the descriptor stores is part of the key (a buffer reallocated
     # under one of them must never leave a stale pointer behind)
-    key = _rollout_key(alg, policy, B, H) + (vb.capacity,) + tuple(getattr(vb, f).data_ptr() for f in _VB_FIELDS)
-    cache = alg.__dict__.setdefault('_rollout_desc_cache', {})
+    key = _rollout_key(alg, policy, B, H)
+    if buffer:
+        vb = alg.virt_buffer._module
+        key += (vb.capacity,) + tuple(getattr(vb, f).data_ptr() for f in _VB_FIELDS)
+    cache = alg.__dict__.setdefault('_rollout_desc_cache' if buffer else '_rollout_traj_desc_cache', {})
     hit = cache.get(key)
     if hit is not None:
         return hit
     if len(cache) >= _ROLLOUT_CACHE_MAX:   # (B, H) or buffers changed: drop the old entries
         cache.clear()
-    L = _lib.lib()
-    d, members, ws, prog = _rollout_desc(alg, policy, B, H, f'rollout.{B}.{H}')
-    d.vs, d.va, d.vs2, d.vr = vb._states.data_ptr(), vb._actions.data_ptr(), vb._next_states.data_ptr(), \
-        vb._rewards.data_ptr()
-    d.vh, d.vd, d.vv = vb._constraint_values.data_ptr(), vb._dones.data_ptr(), vb._violations.data_ptr()
-    d.vptr, d.vcap = vb._pointer.data_ptr(), vb.capacity
-    off = L.drpo_rollout_count_offset(B, alg.state_dim, H)
-    count = ws[off:off + 8].view(torch.int64)[0]
-    hit = cache[key] = (d, members, count, prog)   # prog: keeps the uploaded program alive
+    d, members, ws, prog = _rollout_desc(alg, policy, B, H, f'rollout.{B}.{H}' if buffer else f'rollout_traj.{B}.{H}')
+    count = None
+    if buffer:
+        d.vs, d.va, d.vs2, d.vr = vb._states.data_ptr(), vb._actions.data_ptr(), vb._next_states.data_ptr(), \
+            vb._rewards.data_ptr()
+        d.vh, d.vd, d.vv = vb._constraint_values.data_ptr(), vb._dones.data_ptr(), vb._violations.data_ptr()
+        d.vptr, d.vcap = vb._pointer.data_ptr(), vb.capacity
+        off = _lib.lib().drpo_rollout_count_offset(B, alg.state_dim, H)
+        count = ws[off:off + 8].view(torch.int64)[0]
+    hit = cache[key] = (d, members, count, prog)
     return hit
 
 
@@ -144,6 +152,83 @@ def _rollout_desc(alg, policy, B, H, ws_name):
     return d, members, ws, prog
 
 
+def _start_states(alg, initial_states, noise, dev):
+    """Where a rollout starts: the given rows (the reference rolls out exactly
+    len(initial_states) rows, src/smbpo.py:230-233), else rollout_batch_size chronological
+    replay indices (np.random.choice without replacement; None from a device noise, whose
+    kernel draws them). Returns (source tensor, src_ptr, src_cap, init_idx, B)."""
+    if initial_states is not None:
+        src = initial_states.contiguous().float()
+        assert src.dim() == 2 and src.shape[1] == alg.state_dim, 'initial_states must be [n, state_dim]'
+        B = len(src)
+        return src, B, B, torch.arange(B, device=dev, dtype=torch.int64), B
+    rb, B = alg.replay_buffer._module, alg.rollout_batch_size
+    ptr, cap = rb.pointer, rb.capacity
+    idx = noise.np_choice(min(ptr, cap), B)
+    return rb._states, ptr, cap, None if idx is None else _dev(idx, dev, torch.int64), B
+
+
+def _members_and_draws(model, noise, H, B, A, S1, dev, members=None, eps_a=None, eps_m=None):
+    """The ensemble member of each step and the recorded draws of a rollout. Returns (the H
+    members, the tape's per-step row counts or None, eps_a [H, B, A] and eps_m [H, B, S1] on
+    ``dev`` or None for both: the kernel draws).
+
+    A tape supplies its own (_tape_rollout_noise), rows beyond a step's count and steps beyond
+    the tape zero (member 0). Otherwise ``members`` (an int or H ints), else one random elite
+    per step, checked, and the caller's eps_a / eps_m, checked.
+
+    The order in which a rollout consumes its noise object. rollout(noise=n) and
+    imagine(noise=n) are equal row for row because both keep it:
+      1. _start_states: np_choice, only when no start states were given;
+      2. here: the tape reads, or H times choice(len(elites)), those only when ``members`` is None;
+      3. the caller: next(), only when no ``ctr`` was given.
+    SMBPO.imagine takes its next() for members='each', deterministic and model_noise=False
+    before any of these."""
+    if noise.parity:
+        assert members is None and eps_a is None and eps_m is None, 'a tape supplies its own members and draws'
+        ks, ns, ea, em = _tape_rollout_noise(noise, H, B, A, S1)
+        return [model._elite_inds[k] for k in ks] + [0] * (H - len(ks)), ns, _dev(ea, dev), _dev(em, dev)
+    if members is None:
+        elites = model._elite_inds
+        members = [elites[noise.choice(len(elites))] for _ in range(H)]
+    assert (eps_a is None) == (eps_m is None), 'eps_a and eps_m go together'
+    if eps_a is not None:
+        assert eps_a.dtype == eps_m.dtype == torch.float32 and eps_a.is_contiguous() and eps_m.is_contiguous() \
+            and eps_a.shape == (H, B, A) and eps_m.shape == (H, B, S1), 'eps_a [H, B, A] / eps_m [H, B, S+1] float32'
+    return _traj_members(model, members, H), None, eps_a, eps_m
+
+
+def _traj_members(model, members, H):
+    """members as an int (every step) or a sequence of H ints, checked against the
+    ensemble size here: the descriptor does not carry it."""
+    mem = [members] * H if isinstance(members, (int, np.integer)) else list(members)
+    if len(mem) != H:
+        raise ValueError(f'members: {len(mem)} entries for horizon {H}')
+    E = model.ensemble_size
+    for m in mem:
+        if not isinstance(m, (int, np.integer)) or not 0 <= m < E:
+            raise ValueError(f'members: {m!r} is not a member index of an ensemble of {E}')
+    return [int(m) for m in mem]
+
+
+def _fill_call(d, marr, alg, noise, start, members, eps_a, eps_m, ctr, engine, eps_layout, timer):
+    """The per-call fields of a cached descriptor (_rollout_static), for drpo_rollout and the
+    drpo_rollout_trajectories* calls alike. ``start``: _start_states' tuple. ``timer``: an
+    EventTimer or None (engine 2 records one pair, around the fused kernel; engine 1 one per step)."""
+    src, src_ptr, src_cap, init_idx, _ = start
+    marr[:] = members
+    d.replay_states, d.replay_ptr, d.replay_cap = src.data_ptr(), src_ptr, src_cap
+    d.init_idx = 0 if init_idx is None else init_idx.data_ptr()
+    d.eps_a = 0 if eps_a is None else eps_a.data_ptr()
+    d.eps_m = 0 if eps_m is None else eps_m.data_ptr()
+    d.seed, d.ctr = noise.seed, ctr
+    d.rows_per_tile = getattr(alg, 'rows_per_tile', 0)
+    d.engine, d.eps_layout = engine, (eps_layout if eps_a is not None else 0)
+    d.step_events = timer.events if timer is not None else None
+    if timer is not None:
+        timer.pairs = 1 if engine == 2 else len(marr)
+
+
 def rollout(alg, policy, initial_states, noise, timer=None, eps_layout=0):
     """One imagined rollout (src/smbpo.py:229-249) into alg.virt_buffer.
 
@@ -152,67 +237,37 @@ def rollout(alg, policy, initial_states, noise, timer=None, eps_layout=0):
     draws, which are indexed by the compacted row of each step). ``eps_layout=1``
     marks a tape whose per-step draws are indexed by the original batch row
     ([B] rows every step), which drives engine 2 with recorded draws."""
-    L = _lib.lib()
-    dev = alg.device
-    B, H = alg.rollout_batch_size, alg.horizon
-    S, A = alg.state_dim, alg.action_dim
-    model = alg.model_ensemble
-    rb, vb = alg.replay_buffer._module, alg.virt_buffer._module
-    _lib.require_device(policy.group.data, model.group.data, vb._states)
-
-    # initial states: chronological replay indices (np.random.choice without replacement)
-    if initial_states is not None:
-        # the reference rolls out exactly len(initial_states) rows (src/smbpo.py:230-233)
-        src = initial_states.contiguous().float()
-        _lib.require_device(src)
-        B = len(src)
-        src_ptr = src_cap = B
-        init_idx = torch.arange(B, device=dev, dtype=torch.int64)
-    else:
-        src, src_ptr, src_cap = rb._states, rb.pointer, rb.capacity
-        n_real = min(src_ptr, src_cap)
-        idx = noise.np_choice(n_real, B)
-        init_idx = None if idx is None else _dev(idx, dev, torch.int64)
-
+    H, model, vb = alg.horizon, alg.model_ensemble, alg.virt_buffer._module
+    _lib.require_device(policy.group.data, model.group.data, vb._states, initial_states)
+    start = _start_states(alg, initial_states, noise, alg.device)
+    B = start[-1]
     assert B * H <= vb.capacity, 'We do not support extending by more than buffer capacity'
-    S1 = S + 1
-    if noise.parity:
-        ks, ns, eps_a, eps_m = _tape_rollout_noise(noise, H, B, A, S1)
-        members = [model._elite_inds[k] for k in ks] + [0] * (H - len(ks))
-        eps_a_t, eps_m_t = _dev(eps_a, dev), _dev(eps_m, dev)
-    else:
-        ns = None
-        elites = model._elite_inds
-        members = [elites[noise.choice(len(elites))] for _ in range(H)]
-        eps_a_t = eps_m_t = None
+    members, ns, eps_a, eps_m = _members_and_draws(model, noise, H, B, alg.action_dim, alg.state_dim + 1, alg.device)
     ctr = noise.next()
-
     start_ptr = vb.pointer if vb._host_ptr is not None else None
     policy.group.ensure_packed()
     model.group.ensure_packed()
-    d, marr, count = _rollout_static(alg, policy, B, H)[:3]
-    marr[:] = members
-    d.replay_states, d.replay_ptr, d.replay_cap = src.data_ptr(), src_ptr, src_cap
-    d.init_idx = 0 if init_idx is None else init_idx.data_ptr()
-    d.eps_a = 0 if eps_a_t is None else eps_a_t.data_ptr()
-    d.eps_m = 0 if eps_m_t is None else eps_m_t.data_ptr()
-    d.seed, d.ctr = noise.seed, ctr
-    d.rows_per_tile = getattr(alg, 'rows_per_tile', 0)
+    d, marr, count, _ = _rollout_static(alg, policy, B, H, buffer=True)
     engine = getattr(alg, 'rollout_engine', 0)
     if engine == 0:
         engine = 1 if (noise.parity and eps_layout == 0) or H > 128 else 2
-    d.engine, d.eps_layout = engine, (eps_layout if noise.parity else 0)
-    d.step_events = timer.events if timer is not None else None
-    if timer is not None:
-        timer.pairs = 1 if engine == 2 else H   # engine 2: one pair around the fused kernel
-    _lib.check(L.drpo_rollout(ctypes.byref(d), _lib.stream()), 'rollout')
+    _fill_call(d, marr, alg, noise, start, members, eps_a, eps_m, ctr, engine, eps_layout, timer)
+    _lib.check(_lib.lib().drpo_rollout(ctypes.byref(d), _lib.stream()), 'rollout')
     vb._device_advanced()
-    view = _RolloutResult(vb, start_ptr, count)
-    view.tape_counts = ns
-    return view
+    return _RolloutResult(vb, start_ptr, count, ns)
 
 
 TRAJ_MAX_H = 128    # the fused engine's horizon limit (PERSIST_MAX_H)
+
+
+def _traj_spec(B, H, S, A, C):
+    """ImaginedRollout's tensors as the kernel writes them: (name, shape, dtype, field of drpo_rollout_traj_t)."""
+    f32, i32, b8 = torch.float32, torch.int32, torch.bool
+    return (('states', (B, H + 1, S), f32, 'states'), ('actions', (B, H, A), f32, 'actions'),
+            ('rewards', (B, H), f32, 'rewards'), ('constraint_values', (B, H, C), f32, 'constraint_values'),
+            ('dones', (B, H), b8, 'dones'), ('violations', (B, H), b8, 'violations'), ('lengths', (B,), i32, 'len'),
+            ('returns', (B,), f32, 'ret'), ('max_constraint', (B, C), f32, 'hmax'),
+            ('first_violation', (B,), i32, 'first_violation'), ('terminated', (B,), b8, 'terminated'))
 
 
 class ImaginedRollout:
@@ -246,18 +301,24 @@ class ImaginedRollout:
     at (states[i, t], actions[i, t]), in the model's normalised state units):
       disagreement, epistemic, aleatoric [B, H]   zero at and beyond a row's length
       max_disagreement [B]       the largest disagreement over the row's steps"""
-    TENSORS = ('states', 'actions', 'rewards', 'constraint_values', 'dones', 'violations', 'lengths', 'returns',
-               'max_constraint', 'first_violation', 'terminated')
-    UNCERTAINTY = ('disagreement', 'epistemic', 'aleatoric', 'max_disagreement')
+    TENSORS = tuple(s[0] for s in _traj_spec(0, 0, 0, 0, 0))
+    # the optional groups: name -> (per-run tensors, which stack stacks; scalars, which it copies)
+    GROUPS = {'shield': (('interventions', 'certificate'), ('shield_threshold',)),
+              'linear': (('blend',), ('shield_candidates',)),
+              'uncertainty': (('disagreement', 'epistemic', 'aleatoric', 'max_disagreement'), ())}
+    _UNSET = dict.fromkeys(k for per_run, scalars in GROUPS.values() for k in per_run + scalars)
 
     def __init__(self, members, given_steps=0, **tensors):
         assert set(tensors) == set(self.TENSORS)
         self.members = members
         self.given_steps = given_steps
-        self.interventions = self.certificate = self.shield_threshold = None
-        self.blend = self.shield_candidates = None
-        self.disagreement = self.epistemic = self.aleatoric = self.max_disagreement = None
-        self.__dict__.update(tensors)
+        self.__dict__.update(self._UNSET, **tensors)
+
+    def set_group(self, group, **values):
+        """Set every attribute of one optional group."""
+        per_run, scalars = self.GROUPS[group]
+        assert set(values) == set(per_run + scalars), (group, sorted(values))
+        self.__dict__.update(values)
 
     @property
     def mask(self):
@@ -277,16 +338,10 @@ class ImaginedRollout:
     def stack(cls, runs):
         out = cls([r.members for r in runs], runs[0].given_steps,
                   **{k: torch.stack([getattr(r, k) for r in runs]) for k in cls.TENSORS})
-        if runs[0].interventions is not None:
-            out.interventions = torch.stack([r.interventions for r in runs])
-            out.certificate = torch.stack([r.certificate for r in runs])
-            out.shield_threshold = runs[0].shield_threshold
-        if runs[0].blend is not None:
-            out.blend = torch.stack([r.blend for r in runs])
-            out.shield_candidates = runs[0].shield_candidates
-        if runs[0].disagreement is not None:
-            for k in cls.UNCERTAINTY:
-                setattr(out, k, torch.stack([getattr(r, k) for r in runs]))
+        for group, (per_run, scalars) in cls.GROUPS.items():
+            if getattr(runs[0], per_run[0]) is not None:
+                out.set_group(group, **{k: torch.stack([getattr(r, k) for r in runs]) for k in per_run},
+                              **{k: getattr(runs[0], k) for k in scalars})
         return out
 
 
@@ -338,19 +393,27 @@ class ModelRolloutError:
         return torch.quantile(e, torch.linspace(0, 1, 11, device=e.device, dtype=e.dtype))
 
 
-def _traj_static(alg, policy, B, H):
-    """_rollout_static's counterpart for drpo_rollout_trajectories: a cache, descriptor and
-    workspace of its own (never the entry drpo_rollout's pointers live in), and the
-    virtual-buffer fields left NULL."""
-    key = _rollout_key(alg, policy, B, H)
-    cache = alg.__dict__.setdefault('_rollout_traj_desc_cache', {})
-    hit = cache.get(key)
-    if hit is None:
-        if len(cache) >= _ROLLOUT_CACHE_MAX:
-            cache.clear()
-        d, members, _, prog = _rollout_desc(alg, policy, B, H, f'rollout_traj.{B}.{H}')
-        hit = cache[key] = (d, members, prog)
-    return hit
+def _shield_request(alg, noise, actions, shield, candidates, uncertainty):
+    """Every refusal and default of rollout_trajectories' shield arguments (its docstring), before
+    anything touches a device. Returns None without a shield, else (threshold, the linear
+    shield's candidates or None, whether the certificate is the critic's distributional bound)."""
+    if shield is None:
+        if candidates is not None or uncertainty is not None:
+            raise ValueError('shield_candidates / shield_uncertainty without shield')
+        return None
+    if actions is not None:
+        raise ValueError('shield with actions: a given action is taken as it is (the shielded given-actions '
+                         'kernels are not built)')
+    if noise.parity:
+        raise ValueError('shield with a recorded tape: the reference rollout a tape records has no shield')
+    if candidates is not None and not (isinstance(candidates, (int, np.integer)) and
+                                       not isinstance(candidates, bool) and 2 <= candidates <= 32):
+        raise ValueError(f'shield_candidates: {candidates!r} (an int, 2..32)')
+    if uncertainty and not alg.solver.distributional_qc:
+        raise ValueError('shield_uncertainty: the constraint critic is not distributional')
+    if uncertainty is None:
+        uncertainty = alg.solver.distributional_qc and candidates is None
+    return float(shield), None if candidates is None else int(candidates), bool(uncertainty)
 
 
 def _shield_desc(alg, policy, B, H, threshold, dist):
@@ -390,17 +453,41 @@ def _shield_desc(alg, policy, B, H, threshold, dist):
     return sh, keep
 
 
-def _traj_members(model, members, H):
-    """members as an int (every step) or a sequence of H ints, checked against the
-    ensemble size here: the descriptor does not carry it."""
-    mem = [members] * H if isinstance(members, (int, np.integer)) else list(members)
-    if len(mem) != H:
-        raise ValueError(f'members: {len(mem)} entries for horizon {H}')
-    E = model.ensemble_size
-    for m in mem:
-        if not isinstance(m, (int, np.integer)) or not 0 <= m < E:
-            raise ValueError(f'members: {m!r} is not a member index of an ensemble of {E}')
-    return [int(m) for m in mem]
+def _given_actions(actions, B, H, A):
+    """rollout_trajectories' ``actions`` checked. Returns (actions [B, K, A] or None, K; 0 without)."""
+    if actions is None:
+        return None, 0
+    if not torch.is_tensor(actions) or actions.dtype != torch.float32 or not actions.is_contiguous():
+        raise ValueError('actions: a contiguous float32 tensor [B, K, A] (or [B, A])')
+    _lib.require_device(actions)
+    if actions.dim() == 2:
+        actions = actions.unsqueeze(1)
+    if actions.dim() != 3 or actions.shape[2] != A:
+        raise ValueError(f'actions: shape {tuple(actions.shape)} is not [B, K, {A}]')
+    if actions.shape[0] != B:
+        raise ValueError(f'actions: {actions.shape[0]} rows for {B} trajectories')
+    K = actions.shape[1]
+    if not 1 <= K <= H:
+        raise ValueError(f'actions: {K} given steps, need 1 <= K <= horizon {H}')
+    return actions, K
+
+
+def _traj_outputs(out, spec, dev):
+    """The tensors of ``spec`` (_traj_spec): those of ``out``, checked, and fresh ones for the rest."""
+    out = {} if out is None else dict(out)
+    names = set(ImaginedRollout.TENSORS)
+    assert set(out) <= names, f'out: unknown names {sorted(set(out) - names)}'
+    res = {}
+    for name, shape, dt, _ in spec:
+        t = out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dt, device=dev)
+        else:
+            _lib.require_device(t)
+            assert (t.dtype == dt or (dt == torch.bool and t.dtype == torch.uint8)) and tuple(t.shape) == shape and \
+                t.is_contiguous(), f'out[{name!r}]: need contiguous {dt} {shape}'
+        res[name] = t
+    return res
 
 
 def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, eps_a=None, eps_m=None, eps_layout=1,
@@ -442,149 +529,64 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
     Default: solver.distributional_qc for the threshold shield, False for the linear one
     (the evaluation scores its candidates by the mean). True needs a distributional critic."""
     from ._abi import RolloutGiven, RolloutLinear, RolloutTraj
-    L = _lib.lib()
     dev = alg.device
-    B = alg.rollout_batch_size
     H = alg.horizon if horizon is None else int(horizon)
     if not 1 <= H <= TRAJ_MAX_H:
         raise ValueError(f'horizon {H}: imagined trajectories run the fused engine, 1 <= horizon <= {TRAJ_MAX_H}')
-    S, A, C = alg.state_dim, alg.action_dim, alg.con_dim
-    S1 = S + 1
-    model = alg.model_ensemble
-    rb = alg.replay_buffer._module
+    S, A, C, model = alg.state_dim, alg.action_dim, alg.con_dim, alg.model_ensemble
+    # the requests, checked
     if actions is not None and noise.parity:
         raise ValueError('actions with a recorded tape: a tape fixes the policy\'s draws')
-    if shield is not None:
-        if actions is not None:
-            raise ValueError('shield with actions: a given action is taken as it is (the shielded given-actions '
-                             'kernels are not built)')
-        if noise.parity:
-            raise ValueError('shield with a recorded tape: the reference rollout a tape records has no shield')
-        if shield_candidates is not None and not (isinstance(shield_candidates, (int, np.integer)) and
-                                                  not isinstance(shield_candidates, bool) and
-                                                  2 <= shield_candidates <= 32):
-            raise ValueError(f'shield_candidates: {shield_candidates!r} (an int, 2..32)')
-        if shield_uncertainty and not alg.solver.distributional_qc:
-            raise ValueError('shield_uncertainty: the constraint critic is not distributional')
-    elif shield_candidates is not None or shield_uncertainty is not None:
-        raise ValueError('shield_candidates / shield_uncertainty without shield')
-    _lib.require_device(policy.group.data, model.group.data)
+    request = _shield_request(alg, noise, actions, shield, shield_candidates, shield_uncertainty)
+    _lib.require_device(policy.group.data, model.group.data, initial_states)
 
-    if initial_states is not None:
-        src = initial_states.contiguous().float()
-        _lib.require_device(src)
-        assert src.dim() == 2 and src.shape[1] == S, 'initial_states must be [n, state_dim]'
-        B = len(src)
-        src_ptr = src_cap = B
-        init_idx = torch.arange(B, device=dev, dtype=torch.int64)
-    else:
-        src, src_ptr, src_cap = rb._states, rb.pointer, rb.capacity
-        idx = noise.np_choice(min(src_ptr, src_cap), B)
-        init_idx = None if idx is None else _dev(idx, dev, torch.int64)
-
-    K = 0
-    if actions is not None:
-        if not torch.is_tensor(actions) or actions.dtype != torch.float32 or not actions.is_contiguous():
-            raise ValueError('actions: a contiguous float32 tensor [B, K, A] (or [B, A])')
-        _lib.require_device(actions)
-        if actions.dim() == 2:
-            actions = actions.unsqueeze(1)
-        if actions.dim() != 3 or actions.shape[2] != A:
-            raise ValueError(f'actions: shape {tuple(actions.shape)} is not [B, K, {A}]')
-        if actions.shape[0] != B:
-            raise ValueError(f'actions: {actions.shape[0]} rows for {B} trajectories')
-        K = actions.shape[1]
-        if not 1 <= K <= H:
-            raise ValueError(f'actions: {K} given steps, need 1 <= K <= horizon {H}')
-
-    if noise.parity:
-        assert members is None and eps_a is None and eps_m is None, 'a tape supplies its own members and draws'
-        ks, _, ea, em = _tape_rollout_noise(noise, H, B, A, S1)
-        mem = [model._elite_inds[k] for k in ks] + [0] * (H - len(ks))
-        eps_a, eps_m = _dev(ea, dev), _dev(em, dev)
-    else:
-        if members is None:
-            elites = model._elite_inds
-            members = [elites[noise.choice(len(elites))] for _ in range(H)]
-        mem = _traj_members(model, members, H)
-        assert (eps_a is None) == (eps_m is None), 'eps_a and eps_m go together'
-        if eps_a is not None:
-            _lib.require_device(eps_a, eps_m)
-            assert eps_a.dtype == eps_m.dtype == torch.float32 and eps_a.is_contiguous() and eps_m.is_contiguous() \
-                and eps_a.shape == (H, B, A) and eps_m.shape == (H, B, S1), 'eps_a [H, B, A] / eps_m [H, B, S+1] float32'
+    # inputs (the noise object is consumed here, in _members_and_draws' order)
+    start = _start_states(alg, initial_states, noise, dev)
+    B = start[-1]
+    actions, K = _given_actions(actions, B, H, A)
+    _lib.require_device(eps_a, eps_m)
+    mem, _, eps_a, eps_m = _members_and_draws(model, noise, H, B, A, S + 1, dev, members, eps_a, eps_m)
     ctr = noise.next() if ctr is None else ctr
-
     w = torch.ones(H, dtype=torch.float64, device=dev) if weights is None else \
         torch.as_tensor(weights, dtype=torch.float64).to(dev).contiguous()
     assert w.shape == (H,), 'weights: one float64 per step'
 
-    f32, i32, b8 = torch.float32, torch.int32, torch.bool
-    spec = {'lengths': ((B,), i32), 'states': ((B, H + 1, S), f32), 'actions': ((B, H, A), f32),
-            'rewards': ((B, H), f32), 'constraint_values': ((B, H, C), f32), 'dones': ((B, H), b8),
-            'violations': ((B, H), b8), 'returns': ((B,), f32), 'max_constraint': ((B, C), f32),
-            'first_violation': ((B,), i32), 'terminated': ((B,), b8)}
-    out = {} if out is None else dict(out)
-    assert set(out) <= set(spec), f'out: unknown names {sorted(set(out) - set(spec))}'
-    res = {}
-    for name, (shape, dt) in spec.items():
-        t = out.get(name)
-        if t is None:
-            t = torch.empty(shape, dtype=dt, device=dev)
-        else:
-            _lib.require_device(t)
-            assert (t.dtype == dt or (dt == b8 and t.dtype == torch.uint8)) and tuple(t.shape) == shape and \
-                t.is_contiguous(), f'out[{name!r}]: need contiguous {dt} {shape}'
-        res[name] = t
+    # outputs
+    spec = _traj_spec(B, H, S, A, C)
+    res = _traj_outputs(out, spec, dev)
+    im = ImaginedRollout(mem, K, **res)
 
+    # descriptors
     policy.group.ensure_packed()
     model.group.ensure_packed()
-    d, marr, _ = _traj_static(alg, policy, B, H)
-    marr[:] = mem
-    d.replay_states, d.replay_ptr, d.replay_cap = src.data_ptr(), src_ptr, src_cap
-    d.init_idx = 0 if init_idx is None else init_idx.data_ptr()
-    d.eps_a = 0 if eps_a is None else eps_a.data_ptr()
-    d.eps_m = 0 if eps_m is None else eps_m.data_ptr()
-    d.seed, d.ctr = noise.seed, ctr
-    d.rows_per_tile = getattr(alg, 'rows_per_tile', 0)
-    d.engine, d.eps_layout = 2, (eps_layout if eps_a is not None else 0)
-    d.step_events = timer.events if timer is not None else None
-    if timer is not None:
-        timer.pairs = 1
+    d, marr, _, _ = _rollout_static(alg, policy, B, H, buffer=False)
+    _fill_call(d, marr, alg, noise, start, mem, eps_a, eps_m, ctr, 2, eps_layout, timer)
     t = RolloutTraj()
-    t.len, t.states, t.actions, t.rewards = (res[k].data_ptr() for k in ('lengths', 'states', 'actions', 'rewards'))
-    t.constraint_values, t.dones, t.violations = (res[k].data_ptr() for k in ('constraint_values', 'dones',
-                                                                              'violations'))
+    for name, _, _, field in spec:
+        setattr(t, field, res[name].data_ptr())
     t.weights = w.data_ptr()
-    t.ret, t.hmax, t.first_violation, t.terminated = (res[k].data_ptr() for k in ('returns', 'max_constraint',
-                                                                                  'first_violation', 'terminated'))
-    if shield is not None:
-        if shield_uncertainty is None:
-            dist = bool(alg.solver.distributional_qc) and shield_candidates is None
-        else:
-            dist = bool(shield_uncertainty)
-        sh, keep = _shield_desc(alg, policy, B, H, float(shield), dist)
-        im = ImaginedRollout(mem, 0, **res)
-        if shield_candidates is None:
-            _lib.check(L.drpo_rollout_trajectories_shielded(ctypes.byref(d), ctypes.byref(sh), ctypes.byref(t),
-                                                            _lib.stream()), 'rollout_trajectories_shielded')
-        else:
-            lin = RolloutLinear()
-            im.blend = torch.empty(B, H, dtype=torch.uint8, device=dev)
-            lin.candidates, lin.blend = int(shield_candidates), im.blend.data_ptr()
-            im.shield_candidates = int(shield_candidates)
-            _lib.check(L.drpo_rollout_trajectories_linear(ctypes.byref(d), ctypes.byref(sh), ctypes.byref(lin),
-                                                          ctypes.byref(t), _lib.stream()), 'rollout_trajectories_linear')
-        im.interventions, im.certificate, im.shield_threshold = keep[0].view(torch.bool), keep[1], float(shield)
-        return im
+    entry, extra = 'rollout_trajectories', ()     # the entry point of csrc/rollout.hip and its own descriptors
     if K:
-        g = RolloutGiven()
-        g.actions, g.steps = actions.data_ptr(), K
-        _lib.check(L.drpo_rollout_trajectories_given(ctypes.byref(d), ctypes.byref(g), ctypes.byref(t), _lib.stream()),
-                   'rollout_trajectories_given')
-    else:
-        _lib.check(L.drpo_rollout_trajectories(ctypes.byref(d), ctypes.byref(t), _lib.stream()),
-                   'rollout_trajectories')
-    return ImaginedRollout(mem, K, **res)
+        given = RolloutGiven()
+        given.actions, given.steps = actions.data_ptr(), K
+        entry, extra = 'rollout_trajectories_given', (given,)
+    if request is not None:
+        threshold, candidates, dist = request
+        sh, (interventions, certificate) = _shield_desc(alg, policy, B, H, threshold, dist)
+        im.set_group('shield', interventions=interventions.view(torch.bool), certificate=certificate,
+                     shield_threshold=threshold)
+        entry, extra = 'rollout_trajectories_shielded', (sh,)
+        if candidates is not None:
+            lin = RolloutLinear()
+            blend = torch.empty(B, H, dtype=torch.uint8, device=dev)
+            lin.candidates, lin.blend = candidates, blend.data_ptr()
+            im.set_group('linear', blend=blend, shield_candidates=candidates)
+            entry, extra = 'rollout_trajectories_linear', (sh, lin)
+
+    # launch
+    launch = getattr(_lib.lib(), 'drpo_' + entry)
+    _lib.check(launch(ctypes.byref(d), *map(ctypes.byref, extra), ctypes.byref(t), _lib.stream()), entry)
+    return im
 
 
 def rollout_host_env(alg, policy, initial_states, noise):
@@ -633,9 +635,8 @@ def rollout_host_env(alg, policy, initial_states, noise):
 
 
 class _RolloutResult:
-    def __init__(self, vb, start_ptr, count):
-        self.vb, self._start, self._count = vb, start_ptr, count
-        self.tape_counts = None
+    def __init__(self, vb, start_ptr, count, tape_counts=None):
+        self.vb, self._start, self._count, self.tape_counts = vb, start_ptr, count, tape_counts
 
     def __len__(self):
         return int(self._count.item())

@@ -323,9 +323,7 @@ class SMBPO(Configurable, Module):
             raise NotImplementedError('imagine needs the constraint functions on the device: give the env a '
                                       'ConstraintProgram (drpo_constraint_program, see INTEGRATION.md); the host '
                                       'round trip of such envs is not supported here')
-        H = self.horizon if horizon is None else int(horizon)
-        if not 1 <= H <= ops.TRAJ_MAX_H:
-            raise ValueError(f'horizon {H}: imagine runs the fused engine, 1 <= horizon <= {ops.TRAJ_MAX_H}')
+        H = self.horizon if horizon is None else int(horizon)   # (its range: checked by ops)
         if not (uncertainty is None or isinstance(uncertainty, bool) or uncertainty == 'all'):
             raise ValueError(f"uncertainty: {uncertainty!r} (None, True or 'all')")
         policy = self.actor if policy is None else policy
@@ -344,22 +342,18 @@ class SMBPO(Configurable, Module):
         each = isinstance(members, str)
         if each and members != 'each':
             raise ValueError(f"members: {members!r} (None, an int, {H} ints or 'each')")
-        kw = {} if actions is None else {'actions': actions}
-        if shield is not None and shield is not False:   # (with actions or a tape: refused by ops)
-            if isinstance(shield, (str, tuple, list)):
-                from .sampling import LINEAR_SHIELD_CANDIDATES
-                kind, thr, K = (shield, None, None) if isinstance(shield, str) else (tuple(shield) + (None,) * 3)[:3]
-                if kind != 'linear' or (not isinstance(shield, str) and not 1 <= len(shield) <= 3):
-                    raise ValueError(f"shield: {shield!r} (True, a threshold, 'linear', ('linear', threshold) or "
-                                     "('linear', threshold, candidates))")
-                kw['shield'] = float(self.safe_shield_threshold if thr is None else thr)
-                kw['shield_candidates'] = LINEAR_SHIELD_CANDIDATES if K is None else K   # 2..32: checked by ops
-            else:
-                kw['shield'] = float(self.safe_shield_threshold if shield is True else shield)
-            if shield_uncertainty is not None:
-                kw['shield_uncertainty'] = shield_uncertainty
-        elif shield_uncertainty is not None:
-            raise ValueError('shield_uncertainty without shield')
+        # the shield's shorthand as ops' threshold and candidates; ops._shield_request refuses and defaults
+        kw = {'actions': actions, 'shield_uncertainty': shield_uncertainty}
+        if isinstance(shield, (str, tuple, list)):
+            from .sampling import LINEAR_SHIELD_CANDIDATES
+            kind, thr, K = (shield, None, None) if isinstance(shield, str) else (tuple(shield) + (None,) * 3)[:3]
+            if kind != 'linear' or (not isinstance(shield, str) and not 1 <= len(shield) <= 3):
+                raise ValueError(f"shield: {shield!r} (True, a threshold, 'linear', ('linear', threshold) or "
+                                 "('linear', threshold, candidates))")
+            kw['shield'] = float(self.safe_shield_threshold if thr is None else thr)
+            kw['shield_candidates'] = LINEAR_SHIELD_CANDIDATES if K is None else K
+        elif shield is not None and shield is not False:
+            kw['shield'] = float(self.safe_shield_threshold if shield is True else shield)
         if each or deterministic or not model_noise:
             if noise.parity:
                 raise ValueError("a recorded tape fixes the members and the draws: no 'each', deterministic or "
@@ -392,10 +386,10 @@ class SMBPO(Configurable, Module):
         fills im.disagreement, epistemic, aleatoric and max_disagreement."""
         sp = self.model_ensemble.disagreement(im.states[..., :-1, :], im.actions, members=members, scale=scale)
         mask = im.mask
-        for k in ('disagreement', 'epistemic', 'aleatoric'):
-            v = getattr(sp, k).reshape(mask.shape)
-            setattr(im, k, torch.where(mask, v, torch.zeros_like(v)))
-        im.max_disagreement = im.disagreement.max(dim=-1).values    # >= 0, and 0 beyond a row's length
+        vals = {k: getattr(sp, k).reshape(mask.shape) for k in ('disagreement', 'epistemic', 'aleatoric')}
+        vals = {k: torch.where(mask, v, torch.zeros_like(v)) for k, v in vals.items()}
+        # max_disagreement: >= 0, and 0 beyond a row's length
+        im.set_group('uncertainty', max_disagreement=vals['disagreement'].max(dim=-1).values, **vals)
 
     def update_models(self, model_steps, noise=None):
         """src/smbpo.py:214-227."""

@@ -50,7 +50,7 @@ def measure(B, H, reps):
     w = np.power(np.float64(0.99), np.arange(H, dtype=np.float64))
     im = ops.rollout_trajectories(alg, alg.actor, None, noise, weights=w)
     wdev = torch.as_tensor(w).to(DEV)
-    d = ops._traj_static(alg, alg.actor, B, H)[0]
+    d = ops._rollout_static(alg, alg.actor, B, H, buffer=False)[0]
     d.step_events = tmr.events
     full = _abi.RolloutTraj()
     full.len, full.states, full.actions, full.rewards = (x.data_ptr() for x in (im.lengths, im.states, im.actions,

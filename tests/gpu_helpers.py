@@ -1,8 +1,15 @@
 """Shared helpers for the GPU parity tests."""
+import itertools
+import random
+
 import numpy as np
+import pytest
 import torch
 
 import drpo_amd
+import env_programs as EP
+import fake_envs
+from drpo_amd import envs, ops
 from fake_envs import ENVS
 from oracle import drpo_oracle as O
 
@@ -56,6 +63,112 @@ def close(a, b, tol=1e-4, msg=''):
 
 
 # ---------------------------------------------------------------------------
+# scenes and tapes that more than one test module builds
+# ---------------------------------------------------------------------------
+def original_row_tape(entries, ref, B):
+    """Re-index the reference's per-step draws (row k of step t = k-th surviving row)
+    by original batch row: step t's arrays become [B, dim], row i = trajectory i
+    (zeros for rows already done). Survivors follow from the oracle's dones:
+    step t+1 keeps step t's rows with done == 0, in order (src/smbpo.py:243-246)."""
+    ids = np.arange(B)
+    out, off, t_rows = [], 0, None
+    dones = np.asarray(ref['dones']).astype(bool)
+    for kind, v in entries:
+        if kind == 'normal':               # eps_a of a step: [n_t, A]
+            n = v.shape[0]
+            assert n == len(ids)
+            full = np.zeros((B, v.shape[1]), np.float32)
+            full[ids] = v
+            out.append((kind, full))
+            t_rows = n
+        elif kind == 'randn_like':         # eps_m of the same step: [n_t, S+1]
+            full = np.zeros((B, v.shape[1]), np.float32)
+            full[ids] = v
+            out.append((kind, full))
+            ids = ids[~dones[off:off + t_rows]]
+            off += t_rows
+        else:
+            out.append((kind, v))
+    assert off == len(dones)
+    return out
+
+
+def _fill(alg, env, N, seed):
+    import bench
+    rep = bench.synth_replay(env, N, np.random.RandomState(seed))
+    alg.replay_buffer.extend(**{k: torch.from_numpy(v).to(DEV) for k, v in rep.items()})
+    return rep
+
+
+WIDTH_E, WIDTH_B, WIDTH_H = 3, 256, 4          # the shapes of test_gpu_widths.py
+
+
+def _width_alg(env, hid, mh, seed=5):
+    import bench
+    E, B, H = WIDTH_E, WIDTH_B, WIDTH_H
+    torch.manual_seed(seed)
+    extra = {'model_cfg': {'ensemble_size': E, 'num_elites': E, 'hidden_dim': mh},
+             'sac_cfg': {'hidden_dim': hid, 'critic_cfg': {'hidden_dim': hid},
+                         'constraint_critic_cfg': {'hidden_dim': hid}, 'mlp_multiplier_cfg': {'hidden_dim': hid}}}
+    alg = bench.make_alg(DEV, B, H, E, seed, bench.ENV_JSON[env], extra=extra, env=env)
+    sd = alg.state_dict()
+    assert alg.model_ensemble.hidden_dim == mh and alg.model_ensemble.ensemble_size == E
+    for k in ('solver.actor.net.0.weight', 'solver.critic.qs.0.0.weight', 'solver.constraint_critic.trunk.0.weight',
+              'solver.constraint_critic.mean_head.0.weight', 'solver.multiplier.lam.0.weight'):
+        assert sd[k].shape[0] == hid, (k, tuple(sd[k].shape))
+    return alg
+
+
+def _no_host_env(monkeypatch):
+    def refuse(*a, **k):
+        raise AssertionError('the host round trip ran for an env with a constraint program')
+    monkeypatch.setattr(ops, 'rollout_host_env', refuse)
+
+
+class ProgramQuadrotor(envs.ShapeEnv):
+    """ShapeEnv('quadrotor') without the built-in id: dims plus the program."""
+    drpo_constraint_program = staticmethod(EP.quadrotor_program)
+
+    def __init__(self, name, id=None):
+        super().__init__(name)
+        assert name == 'quadrotor'
+        del self.drpo_env_id
+
+
+def _drifting_quadrotor_alg(rpt):
+    """bench.make_alg quadrotor, E 7, B 72, H 3. The model is put in bench's steady
+    mode (next state = state + tiny noise) with a +0.1 per-step drift on z, and the
+    replay's z is spread over [0.6, 1.6]: rows leave the z <= 1.5 constraint at step 0,
+    1 and 2 by their starting height, the lower ones survive the horizon."""
+    import bench
+    random.seed(11)
+    alg = bench.make_alg(DEV, 72, 3, 7, 0, bench.QUAD_JSON)
+    rep = bench.synth_replay('quadrotor', 400, np.random.RandomState(0))
+    rep['states'][:, 2] = np.linspace(0.6, 1.6, 400, dtype=np.float32)
+    rep['states'][:, [0, 4]] *= 0.1            # well inside the x and pitch bounds
+    alg.replay_buffer.extend(**{k: torch.from_numpy(v).to(DEV) for k, v in rep.items()})
+    alg.model_ensemble.state_normalizer.fit(alg.replay_buffer.get('states'))
+    bench.steady_mode(alg)
+    _, diff, _ = alg.model_ensemble.views()
+    diff[-1][1][..., 2] = 0.1
+    alg.rollout_engine, alg.rows_per_tile = 2, rpt
+    return alg
+
+
+class CustomEnv(fake_envs._Env):
+    S, A, C, T = 9, 2, 3, 100
+    drpo_constraint_program = staticmethod(EP.custom_program)
+
+
+@pytest.fixture
+def custom_oracle_env():
+    prog = EP.custom_program()
+    O.ENV_CONSTRAINTS['_custom_program'] = prog.evaluate_numpy
+    yield '_custom_program'
+    del O.ENV_CONSTRAINTS['_custom_program']
+
+
+# ---------------------------------------------------------------------------
 # float64 comparisons under a per-element error model (tests/test_gpu_rowwise_*.py)
 # ---------------------------------------------------------------------------
 U32 = 2.0 ** -24        # unit roundoff of float32
@@ -105,3 +218,30 @@ def ulp32(x):
     a = np.abs(f64(x).numpy()).astype(np.float32)
     return torch.from_numpy(np.spacing(a).astype(np.float64))
 
+
+SPREAD_OUTPUTS = ('mean', 'epistemic_std', 'aleatoric_std', 'disagreement', 'epistemic', 'aleatoric')
+
+
+def spread_statistics(d, lv, exp_arg, s0, w, absd):
+    """drpo_ens_spread's float64 formulas over members [M, n, S+1] and their bounds' (terms,
+    exp_arg), as the docstring of test_gpu_ens_spread.py states them: d the members' differences
+    with absolute terms absd, lv their clamped log-variances with exp arguments exp_arg,
+    s0 = [s, 0], w the column weights."""
+    M, n, _ = d.shape
+    f = max(1.0, M / 8)
+    dbar = d.mean(0)
+    evar, avar = ((d - dbar) ** 2).mean(0), lv.exp().mean(0)
+    t_col = absd.max(0).values + f * absd.mean(0)
+    dis, t_dis = torch.zeros(n, dtype=torch.float64), torch.zeros(n, dtype=torch.float64)
+    for m1, m2 in itertools.combinations(range(M), 2):
+        dis = torch.maximum(dis, (w * (d[m1] - d[m2])).norm(dim=-1))
+        t_dis = torch.maximum(t_dis, (w * (absd[m1] + absd[m2])).norm(dim=-1))
+    ref = {'mean': s0 + dbar, 'epistemic_std': evar.sqrt(), 'aleatoric_std': avar.sqrt(), 'disagreement': dis,
+           'epistemic': (w * w * evar).sum(-1).sqrt(), 'aleatoric': (w * w * avar).sum(-1).sqrt()}
+    model = {'mean': (s0.abs() + f * absd.mean(0), None),
+             'epistemic_std': (t_col + ref['epistemic_std'], None),
+             'aleatoric_std': (ref['aleatoric_std'], exp_arg.max(0).values),
+             'disagreement': (t_dis + dis, None),
+             'epistemic': ((w * t_col).norm(dim=-1) + ref['epistemic'], None),
+             'aleatoric': (ref['aleatoric'], exp_arg.max(0).values.max(-1).values)}
+    return ref, model

@@ -44,9 +44,8 @@ import torch
 import bench
 import drpo_amd
 from fake_envs import ENVS
-from gpu_helpers import DEV, COMP
+from gpu_helpers import DEV, COMP, _fill, original_row_tape
 from oracle import drpo_oracle as O
-from test_gpu_rollout import original_row_tape
 
 pytestmark = pytest.mark.gpu
 
@@ -64,12 +63,6 @@ def _alg(c, B=None, seed=5):
 
 def _oracle_threads():
     torch.set_num_threads(max(4, min(16, torch.get_num_threads() * 4)))
-
-
-def _fill(alg, env, N, seed):
-    rep = bench.synth_replay(env, N, np.random.RandomState(seed))
-    alg.replay_buffer.extend(**{k: torch.from_numpy(v).to(DEV) for k, v in rep.items()})
-    return rep
 
 
 def _close(got, ref, tol, msg):

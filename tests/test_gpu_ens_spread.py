@@ -24,18 +24,16 @@ rounded up to a power of two in 16..256; S = 300 takes the kernel's second colum
 on both sides of its rows per block, 256 / KP (ROWS_PER_BLOCK). Measured error / bound per
 output: profiles/ens_spread/README.md."""
 import ctypes
-import itertools
 
 import pytest
 import torch
 
 from drpo_amd import _abi, _lib
-from gpu_helpers import C_LIBM, sp64, within
+from gpu_helpers import C_LIBM, SPREAD_OUTPUTS as OUTPUTS, sp64, spread_statistics as statistics, within
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda')
 
-OUTPUTS = ('mean', 'epistemic_std', 'aleatoric_std', 'disagreement', 'epistemic', 'aleatoric')
 ROWS_PER_BLOCK = {1: 16, 12: 16, 15: 16, 16: 8, 51: 4, 255: 1, 300: 1}
 SHAPES = sorted(ROWS_PER_BLOCK)
 # (Z, zsel): repeats and unordered; the quadrotor tests' elites; every member of the largest list; M = 1
@@ -99,30 +97,6 @@ def reference(D, LVR, s, lo, hi, zsel, scale):
     lv = lo64 + sp64(l1 - lo64)
     a_l = lo64.abs() + sp64(l1 - lo64) + torch.sigmoid(l1 - lo64) * (hi64.abs() + sp64(hi64 - raw))
     return statistics(d, lv, a_l / 2, s0, w, d.abs())
-
-
-def statistics(d, lv, exp_arg, s0, w, absd):
-    """The float64 formulas over members [M, n, S+1] and their bounds' (terms, exp_arg): d the
-    members' differences with absolute terms absd, lv their clamped log-variances with exp
-    arguments exp_arg, s0 = [s, 0], w the column weights."""
-    M, n, _ = d.shape
-    f = max(1.0, M / 8)
-    dbar = d.mean(0)
-    evar, avar = ((d - dbar) ** 2).mean(0), lv.exp().mean(0)
-    t_col = absd.max(0).values + f * absd.mean(0)
-    dis, t_dis = torch.zeros(n, dtype=torch.float64), torch.zeros(n, dtype=torch.float64)
-    for m1, m2 in itertools.combinations(range(M), 2):
-        dis = torch.maximum(dis, (w * (d[m1] - d[m2])).norm(dim=-1))
-        t_dis = torch.maximum(t_dis, (w * (absd[m1] + absd[m2])).norm(dim=-1))
-    ref = {'mean': s0 + dbar, 'epistemic_std': evar.sqrt(), 'aleatoric_std': avar.sqrt(), 'disagreement': dis,
-           'epistemic': (w * w * evar).sum(-1).sqrt(), 'aleatoric': (w * w * avar).sum(-1).sqrt()}
-    model = {'mean': (s0.abs() + f * absd.mean(0), None),
-             'epistemic_std': (t_col + ref['epistemic_std'], None),
-             'aleatoric_std': (ref['aleatoric_std'], exp_arg.max(0).values),
-             'disagreement': (t_dis + dis, None),
-             'epistemic': ((w * t_col).norm(dim=-1) + ref['epistemic'], None),
-             'aleatoric': (ref['aleatoric'], exp_arg.max(0).values.max(-1).values)}
-    return ref, model
 
 
 def bits(x):

@@ -9,8 +9,6 @@ same order). Where the program and a built-in id do the same double operations
 (quadrotor, cartpole) the outputs must be identical bit for bit; the point-robot
 built-in may contract dx*dx + dy*dy into a fused multiply-add, which the interpreter
 never does, hence atol 1e-6 there. Rollouts use the tolerances of the tests they mirror."""
-import random
-
 import numpy as np
 import pytest
 import torch
@@ -21,9 +19,9 @@ import fake_envs
 import pr_env
 from conftest import load_golden
 from drpo_amd import envs, ops
-from gpu_helpers import DEV, COMP, small_smbpo, load_sd, fill_replay, close
+from gpu_helpers import (COMP, DEV, CustomEnv, ProgramQuadrotor, _drifting_quadrotor_alg, _no_host_env,  # noqa: F401
+                         close, custom_oracle_env, fill_replay, load_sd, original_row_tape, small_smbpo)
 from oracle import drpo_oracle as O
-from test_gpu_rollout import original_row_tape
 
 pytestmark = pytest.mark.gpu
 
@@ -79,12 +77,6 @@ def _load_rollout_fixture(alg, d):
     m._elite_inds = list(d['model/elite_inds'])
 
 
-def _no_host_env(monkeypatch):
-    def refuse(*a, **k):
-        raise AssertionError('the host round trip ran for an env with a constraint program')
-    monkeypatch.setattr(ops, 'rollout_host_env', refuse)
-
-
 def test_step_engine_program_matches_reference_fixture(monkeypatch):
     """The set-up of test_rollout_host_env_fallback_matches_reference_fixture, but the
     unknown class carries the point-robot program: it stays on the device."""
@@ -133,36 +125,6 @@ def test_fused_engine_program_matches_reference_fixture_full_width(monkeypatch):
 
 
 # ------------------------------------------------------------------ 4. program against built-in
-class ProgramQuadrotor(envs.ShapeEnv):
-    """ShapeEnv('quadrotor') without the built-in id: dims plus the program."""
-    drpo_constraint_program = staticmethod(EP.quadrotor_program)
-
-    def __init__(self, name, id=None):
-        super().__init__(name)
-        assert name == 'quadrotor'
-        del self.drpo_env_id
-
-
-def _drifting_quadrotor_alg(rpt):
-    """bench.make_alg quadrotor, E 7, B 72, H 3. The model is put in bench's steady
-    mode (next state = state + tiny noise) with a +0.1 per-step drift on z, and the
-    replay's z is spread over [0.6, 1.6]: rows leave the z <= 1.5 constraint at step 0,
-    1 and 2 by their starting height, the lower ones survive the horizon."""
-    import bench
-    random.seed(11)
-    alg = bench.make_alg(DEV, 72, 3, 7, 0, bench.QUAD_JSON)
-    rep = bench.synth_replay('quadrotor', 400, np.random.RandomState(0))
-    rep['states'][:, 2] = np.linspace(0.6, 1.6, 400, dtype=np.float32)
-    rep['states'][:, [0, 4]] *= 0.1            # well inside the x and pitch bounds
-    alg.replay_buffer.extend(**{k: torch.from_numpy(v).to(DEV) for k, v in rep.items()})
-    alg.model_ensemble.state_normalizer.fit(alg.replay_buffer.get('states'))
-    bench.steady_mode(alg)
-    _, diff, _ = alg.model_ensemble.views()
-    diff[-1][1][..., 2] = 0.1
-    alg.rollout_engine, alg.rows_per_tile = 2, rpt
-    return alg
-
-
 @pytest.mark.parametrize('rpt', [16, 32])
 def test_fused_engine_program_equals_builtin_device_noise(monkeypatch, rpt):
     """Philox draws are keyed by row and step, so the program and the built-in id see
@@ -194,19 +156,6 @@ def test_fused_engine_program_equals_builtin_device_noise(monkeypatch, rpt):
         if x.dtype == torch.float32:
             x, y = x.view(torch.int32), y.view(torch.int32)
         assert torch.equal(x, y), k
-
-
-class CustomEnv(fake_envs._Env):
-    S, A, C, T = 9, 2, 3, 100
-    drpo_constraint_program = staticmethod(EP.custom_program)
-
-
-@pytest.fixture
-def custom_oracle_env():
-    prog = EP.custom_program()
-    O.ENV_CONSTRAINTS['_custom_program'] = prog.evaluate_numpy
-    yield '_custom_program'
-    del O.ENV_CONSTRAINTS['_custom_program']
 
 
 @pytest.mark.parametrize('engine', [1, 2])

@@ -2,7 +2,7 @@
 drpo_rollout_trajectories): the fused horizon kernel with the trajectory tail in place
 of the ordered emit.
 
-The scene of most tests is test_gpu_env_program._drifting_quadrotor_alg: B 72 (full
+The scene of most tests is gpu_helpers._drifting_quadrotor_alg: B 72 (full
 tiles plus one of 8 rows), H 3, rows leaving at steps 0, 1 and 2 while others survive.
 Tolerances: against the buffer path and between calls everything is compared bit for bit
 (float32 as int32); against the oracle the tolerance of the rollout test this mirrors
@@ -13,57 +13,18 @@ import torch
 
 import drpo_amd
 from drpo_amd import ops
-from gpu_helpers import DEV, COMP, close
+import env_programs as EP
+from gpu_helpers import (COMP, DEV, CustomEnv, _drifting_quadrotor_alg, _no_host_env, close,  # noqa: F401
+                         custom_oracle_env, original_row_tape)
+from imagine_helpers import B, H, TENSORS, _assert_every_length, assert_same, bits, flatten
 from oracle import drpo_oracle as O
-from test_gpu_env_program import (CustomEnv, EP, _drifting_quadrotor_alg, _no_host_env,  # noqa: F401
-                                  custom_oracle_env)
-from test_gpu_rollout import original_row_tape
 
 pytestmark = pytest.mark.gpu
-
-B, H = 72, 3
-TENSORS = ops.ImaginedRollout.TENSORS
-
-
-def flatten(im):
-    """The trajectories in the reference's order (src/smbpo.py:243-246): for t in 0..H-1,
-    the rows with length > t, in batch order. states[:, t] stands for the states and
-    states[:, t + 1] for the next states."""
-    length = im.lengths.cpu()
-    t_ = {k: getattr(im, k).cpu() for k in TENSORS}
-    rows = {k: [] for k in COMP}
-    for t in range(t_['rewards'].shape[1]):
-        keep = length > t
-        rows['states'].append(t_['states'][keep, t])
-        rows['next_states'].append(t_['states'][keep, t + 1])
-        for k in ('actions', 'rewards', 'constraint_values', 'dones', 'violations'):
-            rows[k].append(t_[k][keep, t])
-    return {k: torch.cat(v) for k, v in rows.items()}
-
-
-def bits(x):
-    x = x.detach().cpu()
-    return x.view(torch.int32) if x.dtype == torch.float32 else x
-
-
-def assert_same(a, b, names=TENSORS):
-    for k in names:
-        x, y = (getattr(a, k), getattr(b, k)) if not isinstance(a, dict) else (a[k], b[k])
-        assert x.dtype == y.dtype and x.shape == y.shape, k
-        assert torch.equal(bits(x), bits(y)), k
 
 
 @pytest.fixture(scope='module')
 def alg16():
     return _drifting_quadrotor_alg(16)
-
-
-def _assert_every_length(im):
-    """Otherwise the scene shows nothing: rows of every length, ended and cut ones."""
-    length, term = im.lengths.cpu().numpy(), im.terminated.cpu().numpy().astype(bool)
-    assert set(length.tolist()) == {1, 2, 3}
-    assert term.any() and (~term).any()
-    assert (length[~term] == H).all()
 
 
 # ------------------------------------------------------------------ 1. the buffer path, bit for bit

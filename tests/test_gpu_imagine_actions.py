@@ -8,39 +8,22 @@ of test_gpu_imagine.py; constraint values to 1e-6 as there. The one-step error a
 model_ensemble.means: the project's forward tolerance 1e-4 + 1e-4 |ref| on each predicted
 component, carried through the error norm by the triangle inequality.
 
-The action scene (_action_scene; tests 3 and 5). bench.make_alg quadrotor at the default
-widths, E 7, seed 0, with the raw initial weights. Those alone make a model that all but
-ignores its input (two action sets move its prediction by 4e-5 at most, below the
-tolerance), so the four weight matrices on the mean path (trunk.0, trunk.2, diff_head.0,
-diff_head.2) are scaled by 6: the same two action sets then move the prediction by 0.012
-on average and 0.064 at most, 30 and 160 times the tolerance. The diff head's z bias adds
-a drift of +0.05 per step and the replay's z is spread over [0.6, 1.6], so rows leave
-z <= 1.5 by their height (the scaled model adds to the drift where z is high). Counts of
-the CPU oracle alone (open loop from the start states, member 3, actions and draws as in
-the tests) are in the tests' docstrings."""
-import random
-
+Tests 3 and 5 run imagine_helpers._action_scene (its docstring says how the scene makes the
+actions matter). Counts of the CPU oracle alone (open loop from the start states, member 3,
+actions and draws as in the tests) are in the tests' docstrings."""
 import numpy as np
 import pytest
 import torch
 
-import bench
 import drpo_amd
 from drpo_amd import envs, ops
 from drpo_amd.sampling import episode_segments
-from gpu_helpers import DEV
+from gpu_helpers import DEV, ProgramQuadrotor, _drifting_quadrotor_alg, _fill, _no_host_env, _width_alg
+from imagine_helpers import (B, EP2_LEN, EP_LEN, H, MEMBER, PRE, TENSORS, _action_scene, _assert_every_length,
+                             _episode_inputs, assert_same, bits)
 from oracle import drpo_oracle as O
-from test_gpu_env_program import ProgramQuadrotor, _drifting_quadrotor_alg, _no_host_env  # noqa: F401
-from test_gpu_imagine import TENSORS, _assert_every_length, assert_same, bits
-from test_gpu_widths import _alg as _width_alg
-from test_gpu_configs import _fill
 
 pytestmark = pytest.mark.gpu
-
-B, H = 72, 3
-PRE = 'model_ensemble.'
-MEMBER = 3
-SCALE, DRIFT = 6.0, 0.05
 
 
 def _replay_equal(alg, ks, noise_seed=1234, **kw):
@@ -96,27 +79,6 @@ def test_replay_under_own_actions_generic_widths():
 
 
 # ------------------------------------------------------------------ 3. the actions drive the model
-def _action_scene(dev, scale=SCALE):
-    random.seed(11)
-    alg = bench.make_alg(dev, B, H, 7, 0, bench.QUAD_JSON)
-    rep = bench.synth_replay('quadrotor', 400, np.random.RandomState(0))
-    rep['states'][:, 2] = np.linspace(0.6, 1.6, 400, dtype=np.float32)
-    rep['states'][:, [0, 4]] *= 0.1            # well inside the x and pitch bounds
-    alg.replay_buffer.extend(**{k: torch.from_numpy(v).to(dev) for k, v in rep.items()})
-    m = alg.model_ensemble
-    mean, std = O.normalizer_fit(torch.from_numpy(rep['states']))
-    m.state_normalizer.mean.copy_(mean)
-    m.state_normalizer.std.copy_(std)
-    trunk, diff, _ = m.views()
-    for W in (trunk[0][0], trunk[1][0], diff[0][0], diff[1][0]):
-        W.mul_(scale)
-    diff[-1][1][..., 2] = DRIFT
-    m._elite_inds = [3, 0, 6, 2, 5]
-    alg.rollout_engine, alg.rows_per_tile = 2, 16
-    P = {k: v.detach().cpu().clone() for k, v in alg.state_dict().items() if k.startswith(PRE)}
-    return alg, rep, P
-
-
 def _teacher_inputs(rep):
     """72 start states over the whole z range, actions uniform in [-1, 1), model draws."""
     g = torch.Generator().manual_seed(7)
@@ -287,17 +249,6 @@ def test_small_and_odd_shapes_and_side_effects(monkeypatch):
 
 
 # ------------------------------------------------------------------ 5. model_rollout_error
-EP_LEN, EP2_LEN = 12, 6
-
-
-def _episode_inputs(rep):
-    """Start states and action sequences of the two model-made episodes."""
-    g = torch.Generator().manual_seed(19)
-    s0 = torch.from_numpy(rep['states'][[20, 60]].copy())        # z = 0.65 and 0.75
-    seq = 0.5 * (torch.rand(2, EP_LEN, 2, generator=g) * 2 - 1)
-    return s0, seq
-
-
 def test_model_rollout_error_on_episodes_the_model_made():
     """The replay is the model's own: an episode of 12 steps and one of 6 imagined under
     member 3 without model noise, appended to the 400 unlinked synthetic rows. Open loop

@@ -3,7 +3,7 @@
 drpo_rollout_trajectories_linear: the SH instantiations of rollout_persist_kernel with
 sh_lin_k candidates; the shield of src/sampling.py:430-437).
 
-The scene, the oracle helpers and the tolerances are test_gpu_imagine_shield.py's: B 72
+The scene, the oracle helpers and the tolerances are imagine_helpers.py's: B 72
 (16- and 32-row tiles and a partial one of 8), H 3, S 12, A 2, C 2, rows ending at steps 0,
 1 and 2. Between calls of the kernel everything is compared bit for bit; against the oracle
 and the stand-alone device path |d| <= 2e-4 + 2e-4 |ref|.
@@ -22,13 +22,11 @@ import torch
 
 import drpo_amd
 from drpo_amd import envs, ops, sampling
-from gpu_helpers import DEV
+from gpu_helpers import DEV, ProgramQuadrotor, _drifting_quadrotor_alg, _fill, _no_host_env, _width_alg
+from imagine_helpers import (B, H, INF, MEMBER, PRE, TENSORS, _assert_every_length, _imagine, _params, _scene,
+                             _teacher_inputs, _tol, assert_same, bits, check_certificate_at_step_0,
+                             check_replay_and_safe_action, oracle_qc)
 from oracle import drpo_oracle as O
-from test_gpu_env_program import ProgramQuadrotor, _drifting_quadrotor_alg, _no_host_env  # noqa: F401
-from test_gpu_imagine import TENSORS, _assert_every_length, assert_same, bits
-from test_gpu_imagine_shield import (B, H, INF, MEMBER, PRE, SEED, _params, _scene, _teacher_inputs, _tol)
-from test_gpu_widths import _alg as _width_alg
-from test_gpu_configs import _fill
 
 pytestmark = pytest.mark.gpu
 
@@ -47,12 +45,6 @@ def _linear_scene():
         alg.actor_safe.group.view('net.4.bias')[:alg.action_dim] += SAFE_SHIFT
         _LIN['alg'] = alg
     return _LIN['alg']
-
-
-def _imagine(alg, seed=SEED, **kw):
-    im = alg.imagine(noise=drpo_amd.DeviceNoise(seed), **kw)
-    torch.cuda.synchronize()
-    return im
 
 
 def assert_shield_same(a, b):
@@ -117,31 +109,8 @@ def check_linear_minus_inf(alg, unc=None, **kw):
     im = _imagine(alg, shield=('linear', -INF, K), shield_uncertainty=unc, **kw)
     assert torch.equal(im.blend, (K - 1) * im.mask.to(torch.uint8))
     assert_consistent(im, -INF)
-    re = _imagine(alg, actions=im.actions, **dict({'members': im.members}, **kw))
-    assert re.given_steps == im.rewards.shape[1] and re.blend is None
-    assert_same(im, re)
-    for t in range(im.rewards.shape[1]):
-        live = im.mask[:, t]
-        ref = alg.actor_safe.act(im.states[:, t], eval=True)
-        err = (im.actions[:, t] - ref).abs()[live]
-        assert bool((err <= 1e-4 + 1e-4 * ref.abs()[live]).all()), (t, float(err.max()))
+    check_replay_and_safe_action(alg, im, **kw)
     return im
-
-
-def oracle_qc(P, alg, s, a, unc=False):
-    cc = alg.constraint_critic
-    q = O.cons_critic(P, 'constraint_critic.', s, a, 'uncertainty' if unc else 'mean', std_ratio=cc.std_ratio,
-                      rng=O.LiveRNG(), lmin=cc.log_std_min, lmax=cc.log_std_max)
-    return O.get_qc(q, cc.output_dim)
-
-
-def check_certificate_at_step_0(alg, ln, unc=False):
-    """Of a run at +inf (its actions are the actor's): the oracle's certificate at the
-    kernel's own (states[:, 0], actions[:, 0])."""
-    q = oracle_qc(_params(alg), alg, ln.states[:, 0].cpu(), ln.actions[:, 0].cpu(), unc)
-    err = (ln.certificate[:, 0].cpu() - q).abs()
-    print(f'certificate at step 0: {float(q.min()):.4f} .. {float(q.max()):.4f}, max |d| {float(err.max()):.3g}')
-    assert bool((err <= _tol(q)).all()), float(err.max())
 
 
 @pytest.mark.parametrize('rpt', [16, 32])

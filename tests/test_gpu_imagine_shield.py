@@ -2,7 +2,7 @@
 ops.rollout_trajectories(shield=), drpo_rollout_trajectories_shielded: the SH
 instantiations of rollout_persist_kernel; the shield of src/smbpo.py:124-136).
 
-The scene is test_gpu_env_program._drifting_quadrotor_alg: B 72 (four full 16-row tiles
+The scene is gpu_helpers._drifting_quadrotor_alg: B 72 (four full 16-row tiles
 and one of 8, or two 32-row tiles and one of 8), H 3, S 12, A 2, C 2, rows leaving at
 steps 0, 1 and 2 while others survive. The safe actor starts as a copy of the actor, so
 its mean action tanh(mu) differs from the actor's sample tanh(mu + std * eps) by 0.28 on
@@ -19,57 +19,21 @@ import torch
 import drpo_amd
 from drpo_amd import envs, ops
 from drpo_amd.policy import SquashedGaussianPolicy
-from gpu_helpers import DEV
+from gpu_helpers import DEV, ProgramQuadrotor, _drifting_quadrotor_alg, _fill, _no_host_env, _width_alg
+from imagine_helpers import (B, H, INF, MEMBER, PRE, SEED, TENSORS, _assert_every_length, _params, _scene,
+                             _teacher_inputs, _tol, assert_same, bits, check_certificate_at_step_0,
+                             check_replay_and_safe_action, oracle_qc)
 from oracle import drpo_oracle as O
-from test_gpu_env_program import ProgramQuadrotor, _drifting_quadrotor_alg, _no_host_env  # noqa: F401
-from test_gpu_imagine import TENSORS, _assert_every_length, assert_same, bits
-from test_gpu_widths import _alg as _width_alg
-from test_gpu_configs import _fill
 
 pytestmark = pytest.mark.gpu
-
-B, H = 72, 3
-PRE = 'model_ensemble.'
-MEMBER = 3
-INF = float('inf')
-SEED = 1234
-
-
-def _params(alg):
-    """The oracle's flat parameter dict: solver.* without the prefix, model_ensemble.* with it."""
-    sd = {k: v.detach().cpu().clone() for k, v in alg.state_dict().items()}
-    P = {k[len('solver.'):]: v for k, v in sd.items() if k.startswith('solver.')}
-    P.update({k: v for k, v in sd.items() if k.startswith(PRE)})
-    return P
-
-
-def oracle_certificate(P, alg, s, a):
-    """get_qc of the constraint critic at (s, a), as _shielded_action asks for it."""
-    cc = alg.constraint_critic
-    mode = 'uncertainty' if alg.solver.distributional_qc else 'mean'
-    q = O.cons_critic(P, 'constraint_critic.', s, a, mode, std_ratio=cc.std_ratio, rng=O.LiveRNG(),
-                      lmin=cc.log_std_min, lmax=cc.log_std_max)
-    return O.get_qc(q, cc.output_dim)
 
 
 def oracle_shield_step(P, alg, s, eps_a_t):
     """(a_perf, q, a_safe) of one step from states s under the recorded action draws."""
     mu, std = O.policy_params(P, 'actor.net.', s)
     a_perf = torch.tanh(mu + std * eps_a_t)
-    return a_perf, oracle_certificate(P, alg, s, a_perf), O.policy_mean(P, 'actor_safe.net.', s)
-
-
-def _tol(ref):
-    return 2e-4 + 2e-4 * ref.abs()
-
-
-_ALG = {}
-
-
-def _scene(rpt):
-    if rpt not in _ALG:
-        _ALG[rpt] = _drifting_quadrotor_alg(rpt)
-    return _ALG[rpt]
+    return (a_perf, oracle_qc(P, alg, s, a_perf, alg.solver.distributional_qc),
+            O.policy_mean(P, 'actor_safe.net.', s))
 
 
 def _alg16():
@@ -100,26 +64,8 @@ def check_threshold_minus_inf(alg, **kw):
     torch.cuda.synchronize()
     assert torch.equal(im.interventions, im.mask)
     assert torch.equal(im.certificate != 0, im.mask)
-    re = alg.imagine(actions=im.actions, noise=drpo_amd.DeviceNoise(SEED), **dict({'members': im.members}, **kw))
-    torch.cuda.synchronize()
-    assert re.given_steps == im.rewards.shape[1] and re.interventions is None
-    assert_same(im, re)
-    for t in range(im.rewards.shape[1]):
-        live = im.mask[:, t]
-        ref = alg.actor_safe.act(im.states[:, t], eval=True)
-        err = (im.actions[:, t] - ref).abs()[live]
-        assert bool((err <= 1e-4 + 1e-4 * ref.abs()[live]).all()), (t, float(err.max()))
+    check_replay_and_safe_action(alg, im, **kw)
     return im
-
-
-def check_certificate_at_step_0(alg, sh):
-    """Of a run without interventions (its actions are the actor's): the oracle's
-    certificate at the kernel's own (states[:, 0], actions[:, 0])."""
-    P = _params(alg)
-    q = oracle_certificate(P, alg, sh.states[:, 0].cpu(), sh.actions[:, 0].cpu())
-    err = (sh.certificate[:, 0].cpu() - q).abs()
-    print(f'certificate at step 0: {float(q.min()):.4f} .. {float(q.max()):.4f}, max |d| {float(err.max()):.3g}')
-    assert bool((err <= _tol(q)).all()), float(err.max())
 
 
 @pytest.mark.parametrize('rpt', [16, 32])
@@ -135,15 +81,6 @@ def test_threshold_minus_inf_takes_the_safe_action_everywhere(rpt):
 
 
 # ------------------------------------------------------------------ 3. teacher-forced against the oracle
-def _teacher_inputs(alg):
-    """72 start states over the whole z range, recorded action and model draws."""
-    g = torch.Generator().manual_seed(7)
-    s = alg.replay_buffer.get('states')[2:400:5][:B].cpu().clone()
-    eps_a = torch.randn(H, B, alg.action_dim, generator=g)
-    eps_m = torch.randn(H, B, alg.state_dim + 1, generator=g)
-    return s, eps_a, eps_m
-
-
 def oracle_open_loop(P, alg, s, eps_a, eps_m, thr):
     """The oracle alone, open loop: policy -> certificate -> select -> ens_forward1 -> env
     functions. Per step (alive, intervening, not intervening, within the margin of thr)."""
@@ -221,7 +158,7 @@ def test_constraint_program_env(monkeypatch):
     assert alg.env_params['env_id'] == 4
     sh = check_threshold_plus_inf(alg)
     _assert_every_length(sh)
-    check_certificate_at_step_0(alg, sh)
+    check_certificate_at_step_0(alg, sh, alg.solver.distributional_qc)
     check_threshold_minus_inf(alg)
 
 
@@ -243,7 +180,7 @@ def test_generic_widths():
     assert len(s40) == 40
     sh = check_threshold_plus_inf(alg, states=s40)
     assert sh.certificate.shape == (40, alg.horizon)
-    check_certificate_at_step_0(alg, sh)
+    check_certificate_at_step_0(alg, sh, alg.solver.distributional_qc)
     check_threshold_minus_inf(alg, states=s40)
 
 
@@ -252,7 +189,7 @@ def test_mean_only_certificate(monkeypatch):
     alg = _alg16()
     monkeypatch.setattr(alg.solver, 'distributional_qc', False)
     sh = check_threshold_plus_inf(alg)
-    check_certificate_at_step_0(alg, sh)
+    check_certificate_at_step_0(alg, sh, alg.solver.distributional_qc)
     check_threshold_minus_inf(alg)
     monkeypatch.undo()
     dist = alg.imagine(noise=drpo_amd.DeviceNoise(SEED), shield=INF, members=sh.members)

@@ -18,15 +18,13 @@ import pytest
 import torch
 
 import drpo_amd
-from gpu_helpers import C_LIBM, DEV, f64, within
-from test_gpu_env_program import _drifting_quadrotor_alg
-from test_gpu_ens_spread import OUTPUTS, statistics
-from test_gpu_imagine import TENSORS, _assert_every_length, assert_same, bits
-from test_gpu_imagine_actions import EP_LEN, _action_scene, _episode_inputs
+from gpu_helpers import (C_LIBM, DEV, SPREAD_OUTPUTS as OUTPUTS, _drifting_quadrotor_alg, f64,
+                         spread_statistics as statistics, within)
+from imagine_helpers import (B, EP_LEN, H, TENSORS, _action_scene, _assert_every_length, _episode_inputs, assert_same,
+                             bits)
 
 pytestmark = pytest.mark.gpu
 
-B, H = 72, 3
 ELITES = [3, 0, 6, 2, 5]
 UNC = ('disagreement', 'epistemic', 'aleatoric')
 

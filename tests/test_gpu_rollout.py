@@ -8,7 +8,7 @@ import torch
 import drpo_amd
 from conftest import load_golden
 from fake_envs import ENVS
-from gpu_helpers import DEV, COMP, small_smbpo, load_sd, fill_replay, close
+from gpu_helpers import DEV, COMP, small_smbpo, load_sd, fill_replay, close, original_row_tape
 from oracle import drpo_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -93,34 +93,6 @@ def test_rollout_matches_oracle_full_width(env, B, H):
     got = out.get(as_dict=True)
     for k in COMP:
         close(got[k], ref[k], tol=2e-4, msg=k)
-
-
-def original_row_tape(entries, ref, B):
-    """Re-index the reference's per-step draws (row k of step t = k-th surviving row)
-    by original batch row: step t's arrays become [B, dim], row i = trajectory i
-    (zeros for rows already done). Survivors follow from the oracle's dones:
-    step t+1 keeps step t's rows with done == 0, in order (src/smbpo.py:243-246)."""
-    ids = np.arange(B)
-    out, off, t_rows = [], 0, None
-    dones = np.asarray(ref['dones']).astype(bool)
-    for kind, v in entries:
-        if kind == 'normal':               # eps_a of a step: [n_t, A]
-            n = v.shape[0]
-            assert n == len(ids)
-            full = np.zeros((B, v.shape[1]), np.float32)
-            full[ids] = v
-            out.append((kind, full))
-            t_rows = n
-        elif kind == 'randn_like':         # eps_m of the same step: [n_t, S+1]
-            full = np.zeros((B, v.shape[1]), np.float32)
-            full[ids] = v
-            out.append((kind, full))
-            ids = ids[~dones[off:off + t_rows]]
-            off += t_rows
-        else:
-            out.append((kind, v))
-    assert off == len(dones)
-    return out
 
 
 def test_fused_engine_matches_reference_fixture_full_width():

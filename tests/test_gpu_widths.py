@@ -26,29 +26,15 @@ import torch
 import bench
 import drpo_amd
 from drpo_amd import _abi
-from gpu_helpers import DEV, COMP, close
+from gpu_helpers import (DEV, COMP, WIDTH_B as B, WIDTH_E as E, WIDTH_H as H, _width_alg as _alg, close,
+                         original_row_tape)
 from oracle import drpo_oracle as O
 from test_gpu_configs import _check_params, _eff_grads, _fill, _sac_batch
-from test_gpu_rollout import original_row_tape
 
 pytestmark = pytest.mark.gpu
 
 WIDTHS = [(64, 64), (128, 128), (144, 96)]    # (actor / critic / multiplier hidden, model hidden)
-E, B, H = 3, 256, 4
-
-
-def _alg(env, hid, mh, seed=5):
-    torch.manual_seed(seed)
-    extra = {'model_cfg': {'ensemble_size': E, 'num_elites': E, 'hidden_dim': mh},
-             'sac_cfg': {'hidden_dim': hid, 'critic_cfg': {'hidden_dim': hid},
-                         'constraint_critic_cfg': {'hidden_dim': hid}, 'mlp_multiplier_cfg': {'hidden_dim': hid}}}
-    alg = bench.make_alg(DEV, B, H, E, seed, bench.ENV_JSON[env], extra=extra, env=env)
-    sd = alg.state_dict()
-    assert alg.model_ensemble.hidden_dim == mh and alg.model_ensemble.ensemble_size == E
-    for k in ('solver.actor.net.0.weight', 'solver.critic.qs.0.0.weight', 'solver.constraint_critic.trunk.0.weight',
-              'solver.constraint_critic.mean_head.0.weight', 'solver.multiplier.lam.0.weight'):
-        assert sd[k].shape[0] == hid, (k, tuple(sd[k].shape))
-    return alg
+assert (E, B, H) == (3, 256, 4)
 
 
 _ROLLOUT = {}
