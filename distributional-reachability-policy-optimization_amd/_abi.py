@@ -290,4 +290,12 @@ PROTOTYPES.update({
     'drpo_cc_head': (c_int, [P, P, c_int64, c_int, c_int, c_float, c_float, c_float, P, P, P]),
     'drpo_multiplier_head': (c_int, [c_int64, P, P, P, c_float, c_float, c_float, c_float, c_float, P, P, P]),
     'drpo_multiplier_out': (c_int, [c_int64, P, c_float, P, P]),
+    # path queries (host only): the shape conditions the entry points themselves check
+    'drpo_abi_const': (c_int64, [c_char_p]),
+    'drpo_mlp_pair_ok': (c_int, [POINTER(MlpNet), POINTER(MlpNet)]),
+    'drpo_mlp_heads_paired': (c_int, [POINTER(MlpNet), POINTER(MlpNet), POINTER(MlpNet)]),
+    'drpo_mlp_post_ok': (c_int, [c_int, POINTER(MlpNet)]),
+    'drpo_mlp_fb_ok': (c_int, [c_int] + [POINTER(MlpNet)] * 6 + [c_int]),
+    'drpo_ens_fit_paths': (c_int, [POINTER(MlpFwd), POINTER(MlpBwd), POINTER(EnsUpstream)]),
+    'drpo_rollout_engine': (c_int, [POINTER(RolloutDesc)]),
 })

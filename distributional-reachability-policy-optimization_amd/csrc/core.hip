@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "path_shapes.hpp"
 
 static thread_local char g_err[1024] = "";
 
@@ -86,3 +87,92 @@ DRPO_API int64_t drpo_abi_sizeof(const char* name) {
     if (strcmp(e.n, name) == 0) return (int64_t)e.s;
   return -1;
 }
+
+// every constant of the header a binding mirrors, by name; -1 for an unknown name
+DRPO_API int64_t drpo_abi_const(const char* name) {
+  struct E { const char* n; int64_t v; };
+#define K(x) {#x, x}
+  static const E table[] = {
+      K(DRPO_ACT_NONE), K(DRPO_ACT_RELU), K(DRPO_ACT_SILU), K(DRPO_ACT_TANH),
+      K(DRPO_ENV_POINT_ROBOT), K(DRPO_ENV_QUADROTOR), K(DRPO_ENV_CARTPOLE), K(DRPO_ENV_TRACKING), K(DRPO_ENV_PROGRAM),
+      K(DRPO_PROG_AFFINE), K(DRPO_PROG_BALLS),
+      K(DRPO_PROG_MAX_ROWS), K(DRPO_PROG_MAX_TERMS), K(DRPO_PROG_MAX_CENTRES), K(DRPO_PROG_MAX_BOX),
+      K(DRPO_HEAD_NONE), K(DRPO_HEAD_SAMPLE), K(DRPO_HEAD_RSAMPLE), K(DRPO_HEAD_MEAN),
+      K(DRPO_UPSTREAM_GOUT), K(DRPO_UPSTREAM_CRITIC), K(DRPO_UPSTREAM_CERT), K(DRPO_UPSTREAM_ENS),
+      K(DRPO_UPSTREAM_ACTOR_CC), K(DRPO_UPSTREAM_SAFE_CC), K(DRPO_UPSTREAM_NEG_MEAN), K(DRPO_UPSTREAM_SQUASH),
+      K(DRPO_UPSTREAM_SQUASH_SAFE),
+      K(DRPO_ROLLOUT_FUSED_MAX_H), K(DRPO_OPTIM_MAX_SEGS), K(DRPO_MLP_MULTI_MAX_JOBS), K(DRPO_MLP_MULTI_MAX_SLOTS),
+      K(DRPO_MLP_FB_MAX_JOBS),
+  };
+#undef K
+  for (const E& e : table)
+    if (strcmp(e.n, name) == 0) return e.v;
+  return -1;
+}
+
+// ---------------------------------------------------------------------------
+// path queries: the shape conditions of csrc/path_shapes.hpp, as the entry points call them
+// ---------------------------------------------------------------------------
+using namespace drpo;
+
+// the trunk job of three nets, and the backward that describes a forward's layers
+static drpo_mlp_fwd_t trunk_job(const drpo_mlp_net_t* t, const drpo_mlp_net_t* h1, const drpo_mlp_net_t* h2) {
+  drpo_mlp_fwd_t f{};
+  f.trunk = 1;
+  f.nnets = 3;
+  f.net[0] = *t, f.net[1] = *h1, f.net[2] = *h2;
+  return f;
+}
+
+static drpo_mlp_bwd_t bwd_of(const drpo_mlp_fwd_t& f) {
+  drpo_mlp_bwd_t b{};
+  b.trunk = f.trunk;
+  b.nnets = f.nnets;
+  for (int j = 0; j < f.nnets; ++j) {
+    b.net[j].nl = f.net[j].nl;
+    for (int l = 0; l < MLP_MAXL; ++l) {
+      b.net[j].L[l].din = f.net[j].L[l].din;
+      b.net[j].L[l].dout = f.net[j].L[l].dout;
+      b.net[j].L[l].act = f.net[j].L[l].act;
+    }
+  }
+  return b;
+}
+
+DRPO_API int drpo_mlp_pair_ok(const drpo_mlp_net_t* a, const drpo_mlp_net_t* b) { return a && b && pair_shapes(*a, *b); }
+
+DRPO_API int drpo_mlp_heads_paired(const drpo_mlp_net_t* trunk, const drpo_mlp_net_t* h1, const drpo_mlp_net_t* h2) {
+  if (!trunk || !h1 || !h2) return 0;
+  const drpo_mlp_fwd_t f = trunk_job(trunk, h1, h2);
+  return heads_pairable(&f);
+}
+
+DRPO_API int drpo_mlp_post_ok(int cols0, const drpo_mlp_net_t* post) { return post && post_shapes(cols0, *post); }
+
+DRPO_API int drpo_mlp_fb_ok(int cols0, const drpo_mlp_net_t* trunk, const drpo_mlp_net_t* h1, const drpo_mlp_net_t* h2,
+                            const drpo_mlp_net_t* post, const drpo_mlp_net_t* q0, const drpo_mlp_net_t* q1, int C) {
+  if (!trunk || !h1 || !h2 || !post || !q0 || !q1 || C < 1 || C > 16) return 0;
+  for (const drpo_mlp_net_t* n : {trunk, h1, h2, q0, q1})
+    if (!net_shape_ok(*n, n->L[0].din)) return 0;
+  const drpo_mlp_fwd_t f = trunk_job(trunk, h1, h2);
+  // the chained first forward (bound + multiplier), then each job's nets and upstream
+  if (!heads_pairable(&f) || !post_shapes(cols0, *post) || !fb_post_shapes(*post)) return 0;
+  if (!fb_trunk_shapes(&f, bwd_of(f), C) || !fb_net_shapes(*trunk, true)) return 0;
+  for (const drpo_mlp_net_t* n : {h1, h2, q0, q1})
+    if (!fb_net_shapes(*n, false)) return 0;
+  return fb_single_shapes(*q0) && fb_single_shapes(*q1);
+}
+
+DRPO_API int drpo_ens_fit_paths(const drpo_mlp_fwd_t* fwd, const drpo_mlp_bwd_t* bwd, const drpo_ens_upstream_t* up) {
+  if (!fwd || !bwd || !up) return 0;
+  bool ens = bwd->nnets >= 1 && bwd->nnets <= MLP_MAXN;
+  for (int h = 0; ens && h < bwd->nnets; ++h) {
+    const drpo_mlp_bwd_net_t& n = bwd->net[h];
+    ens = n.nl >= 1 && n.nl <= MLP_MAXL;
+    for (int l = 0; ens && l < n.nl; ++l) ens = bwd_layer_dims(n.L[l]);
+  }
+  ens = ens && ens_bwd_shapes(*bwd, up->S + 1);
+  return (ens ? 1 : 0) | (ens_fit_fb_shapes(*fwd, *bwd, up->S) ? 2 : 0);
+}
+
+DRPO_API int drpo_rollout_engine(const drpo_rollout_desc_t* d) { return d ? rollout_engine(d) : 0; }

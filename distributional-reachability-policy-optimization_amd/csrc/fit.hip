@@ -21,6 +21,7 @@
 // in one phase with the output layers (SIMD-balanced 7/6/6/7 blocks).
 #include "common.hpp"
 #include "ens_nll.hpp"
+#include "path_shapes.hpp"
 
 using namespace drpo;
 
@@ -464,22 +465,10 @@ DRPO_API int drpo_ens_fit_fb(const drpo_mlp_fwd_t* f, const drpo_mlp_bwd_t* bd, 
                              const drpo_ens_reduce_t* red_in, drpo_ens_reduce_t* reduce_out, drpo_stream_t stream) {
   DRPO_REQUIRE(f && bd && up && red_in && reduce_out, "drpo_ens_fit_fb: null argument");
   if (const int e = ens_upstream_check("drpo_ens_fit_fb", up, /*heads=*/false)) return e;
-  const drpo_mlp_net_t &tr = f->net[0], &h1 = f->net[1], &h2 = f->net[2];
-  const int S1 = up->S + 1;
-  const int din0 = f->cols[0] + f->cols[1];
-  const int H = tr.nl == 2 ? tr.L[1].dout : -1;
-  bool ok = f->trunk && f->nnets == 3 && tr.nl == 2 && h1.nl == 2 && h2.nl == 2 && f->cols[2] == 0 &&
-            f->cols[0] == up->S && din0 >= 1 && din0 <= 64 && (H == 200 || H == 256) && tr.L[0].dout == H &&
-            tr.L[0].din == din0 && tr.L[1].din == H && S1 <= 16 && f->nbatch == up->Z && f->rows == up->b &&
-            bd->nbatch == up->Z && bd->rows == up->b && bd->trunk && bd->nnets == 3;
-  for (const drpo_mlp_net_t* n : {&h1, &h2})
-    ok = ok && n->L[0].din == H && n->L[0].dout == H && n->L[1].din == H && n->L[1].dout == S1 &&
-         n->L[0].act == ACT_SILU && n->L[1].act == ACT_NONE;
-  ok = ok && tr.L[0].act == ACT_SILU && tr.L[1].act == ACT_SILU;
+  bool ok = ens_fit_fb_shapes(*f, *bd, up->S) && f->nbatch == up->Z && f->rows == up->b && bd->nbatch == up->Z &&
+            bd->rows == up->b;
   for (int j = 0; j < 3; ++j)
-    for (int l = 0; l < 2; ++l)
-      ok = ok && f->net[j].L[l].W && bd->net[j].L[l].W && bd->net[j].L[l].din == f->net[j].L[l].din &&
-           bd->net[j].L[l].dout == f->net[j].L[l].dout;
+    for (int l = 0; l < 2; ++l) ok = ok && f->net[j].L[l].W && bd->net[j].L[l].W;
   ok = ok && bd->net[0].L[0].dz && bd->net[0].L[0].dz2 && bd->net[0].L[1].dz && bd->net[0].L[1].dz2;
   DRPO_REQUIRE(ok, "drpo_ens_fit_fb: needs the ensemble trunk [S+A <= 64 -> H -> H] and two heads [H -> H -> S+1 <= 16] "
                    "(swish, H = 200 | 256) with the split-heads trunk dZ (dz | dz2)");

@@ -15,6 +15,7 @@
 #include "common.hpp"
 #include "sac_rows.hpp"
 #include "ens_nll.hpp"
+#include "path_shapes.hpp"
 
 using namespace drpo;
 
@@ -25,10 +26,10 @@ constexpr int FW_NT = FW_NW * 64;
 constexpr int FW_ROWS = 16;
 constexpr int FW_MAXC = 2;            // 16 column blocks / 8 waves
 constexpr int LDH = 264;              // LDS stride for widths <= 256 (== 8 mod 64)
-constexpr int MAXL = 3;
-constexpr int MAXN = 3;
-constexpr int MJ_MAXSLOT = 16;        // (job, net) slots of a multi-job launch (grid.y)
-constexpr int FB_MAXJOB = 4;          // jobs of a fused forward + backward launch (grid.y)
+constexpr int MAXL = MLP_MAXL;
+constexpr int MAXN = MLP_MAXN;
+constexpr int MJ_MAXSLOT = DRPO_MLP_MULTI_MAX_SLOTS;   // (job, net) slots of a multi-job launch (grid.y)
+constexpr int FB_MAXJOB = DRPO_MLP_FB_MAX_JOBS;        // jobs of a fused forward + backward launch (grid.y)
 constexpr int FB_MKW = 64;            // words of one layer's ReLU mask (GSave.mk): 16 blocks x 4 registers
 constexpr int FB_MKSLOTS = 5;         // masks a job keeps: trunk layers 0..2, heads 3 / 4 (or a net's layers)
 
@@ -178,11 +179,9 @@ __global__ __launch_bounds__(FW_NT) void mlp_fwd_kernel(drpo_mlp_fwd_t a) {
 static size_t fwd_lds() { return sizeof(float) * ((size_t)4 * FW_ROWS * LDH + FW_NW * 256); }
 
 static int check_net(const drpo_mlp_net_t& n, int din) {
-  if (n.nl < 1 || n.nl > MAXL) return 0;
-  for (int l = 0; l < n.nl; ++l) {
-    if (n.L[l].din != din || n.L[l].dout < 1 || n.L[l].dout > 256 || !n.L[l].W) return 0;
-    din = n.L[l].dout;
-  }
+  if (!net_shape_ok(n, din)) return 0;
+  for (int l = 0; l < n.nl; ++l)
+    if (!n.L[l].W) return 0;
   return 1;
 }
 
@@ -262,21 +261,7 @@ __device__ __forceinline__ float* run_net_g(const drpo_mlp_net_t& __restrict__ n
   return cur;
 }
 
-// Trunk-mode job whose two heads are [256 -> N, act0] -> [N -> n<=16, act1] each (the
-// constraint critic's mean and log-std heads, src/ssac.py:46-92): both heads' hidden
-// layers run as ONE paired layer over the trunk output (2N output columns, one
-// k-loop) and both output layers as one split-K narrow pair, so the job's serial
-// chain is 4 layers instead of 6.
-// (host: the ccb_out check of drpo_mlp_forward_multi)
-__host__ __device__ __forceinline__ bool heads_pairable(const drpo_mlp_fwd_t* __restrict__ a) {
-  if (a->nnets != 3) return false;
-  const drpo_mlp_net_t& n1 = a->net[1];
-  const drpo_mlp_net_t& n2 = a->net[2];
-  return n1.nl == 2 && n2.nl == 2 && n1.L[0].din == 256 && n2.L[0].din == 256 && n1.L[0].dout == n2.L[0].dout &&
-         n1.L[0].act == n2.L[0].act && n1.L[1].act == n2.L[1].act && n1.L[1].dout <= 16 && n2.L[1].dout <= 16;
-}
-
-
+// (heads_pairable, the trunk job whose two heads run as paired layers: csrc/path_shapes.hpp)
 template <int RB, int ACT0, int ACT1>
 __device__ __forceinline__ void heads_pair_act(const drpo_mlp_fwd_t* __restrict__ a, const float* T, float* hA,
                                                float* hB, float* o, int z, int row0, int nrows, float* red,
@@ -415,18 +400,9 @@ __device__ __forceinline__ void pair_nets(const drpo_mlp_net_t& A, const drpo_ml
   else pair_nets_nk<RB, 4>(A, B, rows, in, bA, bB, T, z, row0, nrows, red);
 }
 
-// host-side shape check of a pair job (the kernel's pair_nets assumptions; the kernel
-// trusts the checked `pair` flag). mlp_desc.pairable is its Python twin
-// (tests/test_mlp_desc_checks.py holds the two together).
+// host-side check of a pair job (the kernel trusts the checked `pair` flag)
 static int pair_ok(const drpo_mlp_fwd_t* a) {
-  if (a->trunk || a->nnets != 2) return 0;
-  const drpo_mlp_net_t &A = a->net[0], &B = a->net[1];
-  if (A.nl != 3 || B.nl != 3) return 0;
-  for (int l = 0; l < 3; ++l)
-    if (A.L[l].din != B.L[l].din || A.L[l].dout != B.L[l].dout || A.L[l].act != B.L[l].act) return 0;
-  const int k0 = (A.L[0].din + 15) >> 4;
-  return (k0 == 1 || k0 == 4) && A.L[0].dout == 256 && A.L[1].din == 256 && A.L[1].dout == 256 &&
-         A.L[2].dout <= 16 && A.L[0].act == ACT_RELU && A.L[1].act == ACT_RELU && A.L[2].act == ACT_NONE;
+  return !a->trunk && a->nnets == 2 && pair_shapes(a->net[0], a->net[1]);
 }
 
 // where one forward job of a multi-job launch left its results in LDS
@@ -599,7 +575,7 @@ static int check_fwd_multi_job(const char* who, int j, const drpo_mlp_fwd_t* a) 
                  who, j);
   if (a->post.nl > 0) {
     const drpo_mlp_net_t& pn = a->post;
-    DRPO_REQUIRE(a->ccb_out && a->cols[0] + 1 <= 64 && check_net(pn, a->cols[0] + 1) && !a->nmean,
+    DRPO_REQUIRE(a->ccb_out && post_shapes(a->cols[0], pn) && check_net(pn, a->cols[0] + 1) && !a->nmean,
                  "%s: job %d: a post chain needs the job's constraint bound (ccb_out) and a "
                  "net on [src[0] (<= 63 columns), bound]", who, j);
   } else {
@@ -611,7 +587,8 @@ static int check_fwd_multi_job(const char* who, int j, const drpo_mlp_fwd_t* a) 
 DRPO_API int drpo_mlp_forward_multi(const drpo_mlp_fwd_t* jobs_host, const drpo_mlp_fwd_t* jobs_dev, int njobs,
                                     uint64_t seed, uint64_t ctr, drpo_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  DRPO_REQUIRE(jobs_host && jobs_dev && njobs >= 1 && njobs <= 8, "drpo_mlp_forward_multi: 1..8 jobs");
+  DRPO_REQUIRE(jobs_host && jobs_dev && njobs >= 1 && njobs <= DRPO_MLP_MULTI_MAX_JOBS,
+               "drpo_mlp_forward_multi: 1..8 jobs");
   MultiArgs m{};
   m.jobs = jobs_dev;
   m.seed = seed;
@@ -737,24 +714,7 @@ __device__ __forceinline__ float* bwd_net(const drpo_mlp_bwd_net_t& __restrict__
   return cur;
 }
 
-// Two heads of the same shape on a shared trunk (the dynamics model's diff / log-var
-// heads, src/dynamics.py:84-91; the constraint critic's mean / log-std heads,
-// src/ssac.py:46-92), each [trunk width -> H -> out] with an identity output layer:
-// backed through TOGETHER. Their output layers' products run side by side (one
-// two-input pair layer), and the trunk-output gradient -- the sum of the two heads'
-// hidden-layer products -- is ONE product with the concatenated K (dZ_1 | dZ_2) x
-// [W_1; W_2]: three dependent GEMM phases instead of five, and no LDS accumulation.
-// (host: drpo_mlp_backward_ens checks its heads with it)
-__host__ __device__ __forceinline__ bool bwd_paired_heads(const drpo_mlp_bwd_t& a) {
-  if (!a.trunk || a.split_heads || a.nnets != 3) return false;
-  const drpo_mlp_bwd_net_t &h1 = a.net[1], &h2 = a.net[2];
-  if (h1.nl != 2 || h2.nl != 2 || h1.dx || h2.dx) return false;
-  for (int l = 0; l < 2; ++l)
-    if (h1.L[l].din != h2.L[l].din || h1.L[l].dout != h2.L[l].dout || h1.L[l].act != h2.L[l].act) return false;
-  const int hid = h1.L[0].dout, out = h1.L[1].dout;
-  return h1.L[1].act == ACT_NONE && (hid == 200 || hid == 256) && out <= 64 && h1.L[0].din <= 256;
-}
-
+// (bwd_paired_heads, two heads of one shape backed through together: csrc/path_shapes.hpp)
 template <int NK>
 __device__ __forceinline__ void bwd_heads_catk(const drpo_mlp_bwd_net_t& h1, const drpo_mlp_bwd_net_t& h2, const float* D1,
                                                const float* D2, float* out, int z,
@@ -1281,7 +1241,7 @@ static int check_bwd(const char* who, int j, const drpo_mlp_bwd_t* a) {
     const bool reads_gout = a->upstream == DRPO_UPSTREAM_GOUT && !(a->trunk && h == 0);
     DRPO_REQUIRE(n.gout || !reads_gout, "%s: job %d: net %d needs gout (upstream DRPO_UPSTREAM_GOUT)", who, j, h);
     for (int l = 0; l < n.nl; ++l)
-      DRPO_REQUIRE(n.L[l].din >= 1 && n.L[l].din <= 256 && n.L[l].dout >= 1 && n.L[l].dout <= 256 && n.L[l].W,
+      DRPO_REQUIRE(bwd_layer_dims(n.L[l]) && n.L[l].W,
                    "%s: job %d: bad layer %d of net %d", who, j, l, h);
     if (n.dx)
       DRPO_REQUIRE(n.dx_col0 >= 0 && n.dx_col0 + n.dx_cols <= n.L[0].din, "%s: job %d: dx columns of net %d", who, j, h);
@@ -1316,11 +1276,7 @@ DRPO_API int drpo_mlp_backward_ens(const drpo_mlp_bwd_t* a, const drpo_ens_upstr
   DRPO_REQUIRE(a->upstream == DRPO_UPSTREAM_ENS && a->trunk && a->nnets == 3 && a->nbatch == up->Z &&
                    a->rows == up->b,
                "drpo_mlp_backward_ens: the descriptor must be the ensemble trunk + two heads with upstream ENS");
-  // the NLL upstream assumes the paired head shape, also when each head then runs in a
-  // workgroup of its own (split_heads)
-  drpo_mlp_bwd_t shape = *a;
-  shape.split_heads = 0;
-  DRPO_REQUIRE(bwd_paired_heads(shape) && a->net[1].L[1].dout == up->S + 1,
+  DRPO_REQUIRE(ens_bwd_shapes(*a, up->S + 1),
                "drpo_mlp_backward_ens: heads must be paired [H -> 200|256 -> S+1] (S+1 <= 64)");
   const int nbx = ens_tile_nbx(up->b);
   const drpo_ens_reduce_t r = ens_reduce_from(*up, *red_in, nbx);
@@ -1355,7 +1311,8 @@ DRPO_API int drpo_mlp_backward_multi_actor(const drpo_mlp_bwd_t* jobs_host, cons
 
 static int bwd_multi_launch(const drpo_mlp_bwd_t* jobs_host, const drpo_mlp_bwd_t* jobs_dev, int njobs,
                             const drpo_critic_head_t* head, const drpo_actor_head_t* actor, hipStream_t stream) {
-  DRPO_REQUIRE(jobs_host && jobs_dev && njobs >= 1 && njobs <= 8, "drpo_mlp_backward_multi: 1..8 jobs");
+  DRPO_REQUIRE(jobs_host && jobs_dev && njobs >= 1 && njobs <= DRPO_MLP_MULTI_MAX_JOBS,
+               "drpo_mlp_backward_multi: 1..8 jobs");
   BwdMultiArgs m{};
   m.jobs = jobs_dev;
   if (actor) {
@@ -1522,12 +1479,7 @@ static size_t fb_lds() {
 }
 
 // the last forward of a fused job and its backward must describe the same layers
-static int fb_same_net(const drpo_mlp_net_t& f, const drpo_mlp_bwd_net_t& b) {
-  if (f.nl != b.nl) return 0;
-  for (int l = 0; l < f.nl; ++l)
-    if (f.L[l].din != b.L[l].din || f.L[l].dout != b.L[l].dout || f.L[l].act != b.L[l].act) return 0;
-  return 1;
-}
+static int fb_same_net(const drpo_mlp_net_t& f, const drpo_mlp_bwd_net_t& b) { return same_layers(f, b); }
 
 DRPO_API int drpo_mlp_fb_multi(const drpo_mlp_fwd_t* fwd_host, const drpo_mlp_fwd_t* fwd_dev, int nfwd,
                                const drpo_mlp_bwd_t* bwd_host, const drpo_mlp_bwd_t* bwd_dev, int nbwd,
@@ -1561,7 +1513,7 @@ DRPO_API int drpo_mlp_fb_multi(const drpo_mlp_fwd_t* fwd_host, const drpo_mlp_fw
       DRPO_REQUIRE(f->rows == actor->B, "%s: job %d: forward %d has %lld rows, the actor head %lld", who, j, i,
                    (long long)f->rows, (long long)actor->B);
       if (i < J.nfwd - 1)
-        DRPO_REQUIRE(f->post.nl > 0 && f->post.L[f->post.nl - 1].dout == 1 && actor->lams,
+        DRPO_REQUIRE(fb_post_shapes(f->post) && actor->lams,
                      "%s: job %d: a first forward must end in a post chain with one output (the multiplier)", who, j);
     }
     const drpo_mlp_fwd_t* f = fwd_host + J.fwd[J.nfwd - 1];
@@ -1577,19 +1529,18 @@ DRPO_API int drpo_mlp_fb_multi(const drpo_mlp_fwd_t* fwd_host, const drpo_mlp_fw
       for (int l = 0; l < n.nl; ++l) {
         DRPO_REQUIRE(!n.L[l].dz && !n.L[l].dz2, "%s: job %d: net %d layer %d: dz saves are not written here", who, j, h, l);
         const bool hidden = l < n.nl - 1 || (b->trunk && h == 0);
-        DRPO_REQUIRE(n.L[l].act == (hidden ? ACT_RELU : ACT_NONE) && (!hidden || n.L[l].dout > 16),
+        DRPO_REQUIRE(fb_layer_shape(n.L[l], hidden),
                      "%s: job %d: net %d layer %d: hidden layers are ReLU and wider than 16, outputs identity", who, j, h,
                      l);
       }
     }
     if (!b->trunk) {
       const drpo_mlp_bwd_net_t& n0 = b->net[0];
-      DRPO_REQUIRE(b->upstream == DRPO_UPSTREAM_NEG_MEAN && n0.L[n0.nl - 1].dout == 1 && J.nfwd == 1,
+      DRPO_REQUIRE(b->upstream == DRPO_UPSTREAM_NEG_MEAN && fb_single_shapes(n0) && J.nfwd == 1,
                    "%s: job %d: a single net takes the -1/B upstream on one output, after one forward", who, j);
     } else {
       DRPO_REQUIRE((b->upstream == DRPO_UPSTREAM_ACTOR_CC || b->upstream == DRPO_UPSTREAM_SAFE_CC) &&
-                       heads_pairable(f) && bwd_paired_heads(*b) && b->net[1].L[0].dout == 256 &&
-                       b->net[0].L[b->net[0].nl - 1].dout == 256 && b->net[1].L[1].dout == actor->C,
+                       fb_trunk_shapes(f, *b, actor->C),
                    "%s: job %d: a trunk job takes the constraint-critic upstream on paired 256-wide heads "
                    "[256 -> 256 -> C]", who, j);
       DRPO_REQUIRE(J.nfwd == 1 || b->upstream == DRPO_UPSTREAM_ACTOR_CC,

@@ -124,7 +124,7 @@ DRPO_API int drpo_normalize(const float* x, const float* mean, const float* std,
 // launches). Elements are processed independently; segments never overlap.
 // ---------------------------------------------------------------------------
 namespace {
-constexpr int OPT_MAXSEG = 8;
+constexpr int OPT_MAXSEG = DRPO_OPTIM_MAX_SEGS;
 constexpr int OPT_MAXTASK = 32;
 constexpr int OPT_BLOCK_ELEMS = 1024;   // flat task: elements per workgroup (256 threads x 4)
 constexpr int OPT_BLOCKS4 = 64;         // matrix task: 4x4 blocks per workgroup (one per lane quad)

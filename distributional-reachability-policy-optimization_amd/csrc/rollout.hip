@@ -64,6 +64,7 @@ extern "C" __attribute__((visibility("default"))) int drpo_debug_stamps_rollout(
 #endif
 
 #include "common.hpp"
+#include "path_shapes.hpp"
 #include "env_constraints.hpp"
 #include "prp.hpp"
 #include "sac_rows.hpp"
@@ -436,7 +437,7 @@ __global__ void rollout_finalize_kernel(int64_t* vptr, const int* n, int64_t* of
 // step time did not change, and the held fragments pushed the kernel to 256 VGPRs
 // with scratch reloads in front of the MFMA loops.
 // ---------------------------------------------------------------------------
-constexpr int PERSIST_MAX_H = 128;
+constexpr int PERSIST_MAX_H = DRPO_ROLLOUT_FUSED_MAX_H;
 
 // The actor's weights are the same every step: without this the compiler hoists
 // all of a layer's (restrict, loop-invariant) fragment loads out of the horizon
@@ -1828,8 +1829,7 @@ DRPO_API int drpo_rollout(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
   int rpt;
   int64_t rlen;
   if (const int rc = rollout_checks(d, "drpo_rollout", true, rpt, rlen)) return rc;
-  int engine = d->engine;
-  if (engine == 0) engine = (d->eps_a && d->eps_layout == 0) || d->H > PERSIST_MAX_H ? 1 : 2;
+  const int engine = rollout_engine(d);
   if (d->eps_a)
     DRPO_REQUIRE(d->eps_layout == engine - 1, "drpo_rollout: eps_layout %d cannot drive engine %d (compacted draws "
                  "need engine 1, original-row draws engine 2)", d->eps_layout, engine);

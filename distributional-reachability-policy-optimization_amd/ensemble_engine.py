@@ -16,11 +16,13 @@ small row-wise kernels (csrc/ensemble.hip):
 
 FitPlan.compute -- forward, NLL and backward-data, leaving the NLL's block partials and
 their reduction as data (drpo_ens_reduce_t). The first variant whose condition holds:
-  1. drpo_ens_fit_fb, all three in one launch: the shapes of ens_fb_shapes (the reference
-     default: two trunk layers, one hidden layer per head, width 200 | 256, S+A <= 64,
-     S+1 <= 16), a split-heads grid, and the switches fit_fb_enabled and split_bwd on.
+  1. drpo_ens_fit_fb, all three in one launch: the shapes that entry point admits (the
+     reference default: two trunk layers, one hidden layer per head, width 200 | 256,
+     S+A <= 64, S+1 <= 16), a split-heads grid, and the switches fit_fb_enabled and
+     split_bwd on.
   2. drpo_mlp_forward + drpo_mlp_backward_ens, the NLL gradients formed inside the
-     backward launch: the shapes of ens_fused_shapes (heads [H -> 200|256 -> S+1 <= 64]).
+     backward launch: the shapes that entry point admits (heads [H -> 200|256 -> S+1 <= 64]).
+  (Which shapes: drpo_ens_fit_paths, the library's own conditions.)
      One workgroup per (row tile, head) at split-heads grids with split_bwd on, else
      one per row tile with the heads paired.
   3. drpo_mlp_forward + drpo_ens_loss (deferred reduction) + drpo_mlp_backward: any other
@@ -48,7 +50,7 @@ import torch
 from . import _lib
 from .optim import OPT_MAXSEG, fused_step
 from .rng import DeviceNoise
-from .mlp_desc import ACT_ID, Net, fill_bwd, fill_fwd, wgrad_workspace
+from .mlp_desc import ACT_ID, UPSTREAM_ENS, UPSTREAM_GOUT, Layer, Net, fill_bwd, fill_fwd, wgrad_workspace
 from ._abi import EnsReduce, EnsSpread, EnsUpstream, WgradItem
 
 
@@ -66,43 +68,6 @@ SPLIT_HEADS_MAX_TILES = 256
 
 def split_heads(n, Z):
     return (n + 15) // 16 * Z <= SPLIT_HEADS_MAX_TILES
-
-
-def ens_fused_shapes(nets, S1):
-    """Path selector: the shapes drpo_mlp_backward_ens accepts (it mirrors that entry point's
-    check in csrc/mlp.hip: bwd_paired_heads on the descriptor plus dout == S+1): both heads
-    [H -> 200|256 -> S+1] with the same hidden width and activation and an identity
-    output layer, S+1 <= 64, and every trunk layer at most 256 wide."""
-    h1, h2 = nets[1].layers, nets[2].layers
-    if len(h1) != 2 or len(h2) != 2 or S1 > 64:
-        return False
-    (_, _, _, hid1, act1, _), (_, _, _, hid2, act2, _) = h1[0], h2[0]
-    if hid1 not in (200, 256) or hid1 != hid2 or act1 != act2:
-        return False
-    if h1[1][3] != S1 or h2[1][3] != S1 or h1[1][4] != 0 or h2[1][4] != 0:
-        return False
-    return all(din <= 256 and dout <= 256 for (_, _, din, dout, _, _) in nets[0].layers)
-
-
-def ens_fb_shapes(nets, S, A):
-    """Path selector: the shapes drpo_ens_fit_fb takes (it mirrors the `ok` condition of that
-    entry point in csrc/fit.hip; the fit step's forward, NLL and backward-data in one launch):
-    trunk [S+A <= 64 -> H -> H], heads [H -> H -> S+1 <= 16], swish hidden layers, identity
-    outputs, H = 200 | 256 (the reference default:
-    src/dynamics.py:59-61,85-86, hidden_dim=200, trunk_layers=2, head_hidden_layers=1)."""
-    if len(nets) != 3 or S + A > 64 or S + 1 > 16:
-        return False
-    sw = ACT_ID['swish']
-    t = nets[0].layers
-    if len(t) != 2:
-        return False
-    H = t[1][3]
-    if H not in (200, 256) or t[0][3] != H or t[0][4] != sw or t[1][4] != sw:
-        return False
-    for h in (nets[1].layers, nets[2].layers):
-        if len(h) != 2 or h[0][2] != H or h[0][3] != H or h[0][4] != sw or h[1][3] != S + 1 or h[1][4] != 0:
-            return False
-    return True
 
 
 def _addr(t):
@@ -166,7 +131,7 @@ class EnsembleEngine:
                 else:          # packed-mirror stride per member, bias stride
                     st.append((W.shape[1], dout))
                     W, WT, b = W[z0], WT[z0], b[z0]
-                lay.append((W, b, din, dout, ACT_ID[act], WT))
+                lay.append(Layer(W, b, din, dout, ACT_ID[act], WT))
                 if grads:
                     gl.append((g.view(f'{prefix}{2 * i}.weight', g.grad)[z0],
                                g.view(f'{prefix}{2 * i}.bias', g.grad)[z0]))
@@ -458,6 +423,20 @@ class EnsembleEngine:
             self._side = (torch.cuda.Stream(device=self.dev), evs[0], evs[1])
         return self._side
 
+    def fit_plan(self, steps=1, sh=None):
+        """The FitPlan of a fit(steps=) call over the members of shard ``sh`` (None: all), with
+        its gathered-minibatch workspace: .fused / .fb / .path say which launches it runs."""
+        m = self.m
+        S, A = m.state_dim, m.action_dim
+        rows = (sh.count if sh is not None else m.ensemble_size) * m.batch_size
+        # The minibatches of a chunk of steps are gathered in ONE launch (the replay is
+        # not written during the fit); the step's descriptors are pointed at its slice.
+        # Chunks of <= 64 MB of gathered rows.
+        chunk = max(1, min(steps, (64 << 20) // (4 * (2 * S + A + 1) * max(rows, 1))))
+        mb = (self.buf('fit.s_all', chunk * rows, S), self.buf('fit.a_all', chunk * rows, A),
+              self.buf('fit.t_all', chunk * rows, S + 1))
+        return FitPlan(self, sh, mb, torch.empty(max(steps, 1), device=self.dev), chunk)
+
     def fit(self, buffer, steps, noise=None):
         """fit(steps=) (src/dynamics.py:155-183). Under data parallelism the members are
         sharded over the ranks (distributed.MemberShard) unless dp_mode='batch', in which
@@ -480,15 +459,9 @@ class EnsembleEngine:
         E, b = m.ensemble_size, m.batch_size
         z0, Z = (sh.z0, sh.count) if sh is not None else (0, E)
         rows = Z * b
-        losses = torch.empty(max(steps, 1), device=self.dev)
         m.group.grad.zero_()
-        # The minibatches of a chunk of steps are gathered in ONE launch (the replay is
-        # not written during the fit); the step's descriptors are pointed at its slice.
-        # Chunks of <= 64 MB of gathered rows.
-        chunk = max(1, min(steps, (64 << 20) // (4 * (2 * S + A + 1) * max(rows, 1))))
-        mb = (self.buf('fit.s_all', chunk * rows, S), self.buf('fit.a_all', chunk * rows, A),
-              self.buf('fit.t_all', chunk * rows, S1))
-        plan = FitPlan(self, sh, mb, losses)
+        plan = self.fit_plan(steps, sh)
+        mb, losses, chunk = plan.mb, plan.losses, plan.chunk
         self.fit_fb, self.fit_path = plan.fb, plan.path    # (tests, probes)
         # parity mode: the reference's randint over all E*b rows, this shard's slice
         idx_all = None
@@ -607,12 +580,13 @@ class FitPlan:
     launches in order; which of their three variants run is decided here (the header of
     this file says when)."""
 
-    def __init__(self, eng, sh, mb, losses):
+    def __init__(self, eng, sh, mb, losses, chunk):
         from ._abi import OptimSeg, WgradAdam
         m, g = eng.m, eng.m.group
         S, A, b = m.state_dim, m.action_dim, m.batch_size
         z0, Z = (sh.z0, sh.count) if sh is not None else (0, m.ensemble_size)
         self.eng, self.sh, self.mb, self.rows = eng, sh, mb, Z * b
+        self.losses, self.chunk = losses, chunk
         self.loss_base = losses.data_ptr()
         self.fd, nets, strides, save_x = eng._forward_desc(mb[0], mb[1], b, Z, b * S, b * A, tag='fit', save=True,
                                                            z0=z0)
@@ -623,11 +597,13 @@ class FitPlan:
         self.bd, wl = eng._backward_descs(nets, strides, save_x, gD, gL, b, Z)
         self.refs = [ctypes.byref(x) for x in (self.fd, self.bd, self.up, self.red_in, self.red)]
         self.L, self.stream = _lib.lib(), _lib.stream()
-        # compute: the NLL in the backward launch needs the shapes drpo_mlp_backward_ens takes,
-        # the one-launch step also a split-heads grid and the shapes of drpo_ens_fit_fb
-        self.fused = ens_fused_shapes(nets, S + 1)
-        self.bd.upstream = 3 if self.fused else 0   # DRPO_UPSTREAM_ENS : DRPO_UPSTREAM_GOUT
-        self.fb = eng.fit_fb_enabled and self.fused and bool(self.bd.split_heads) and ens_fb_shapes(nets, S, A)
+        # compute: the NLL in the backward launch needs the shapes drpo_mlp_backward_ens takes
+        # (bit 0), the one-launch step also a split-heads grid and the shapes of drpo_ens_fit_fb
+        # (bit 1)
+        paths = self.L.drpo_ens_fit_paths(*self.refs[:3])
+        self.fused = bool(paths & 1)
+        self.bd.upstream = UPSTREAM_ENS if self.fused else UPSTREAM_GOUT
+        self.fb = eng.fit_fb_enabled and self.fused and bool(self.bd.split_heads) and bool(paths & 2)
         # apply: Adam in the weight-gradient launch needs the fused NLL, no clip and no exchange
         # of the member gradients (a member shard and batch DP exclude each other:
         # member_sharding() is None under dp_mode='batch')

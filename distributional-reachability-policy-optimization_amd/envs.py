@@ -8,6 +8,9 @@ reference's classes need gym / mujoco / safe_control_gym, which the build does n
 import) or by an explicit ``drpo_env_id`` attribute."""
 import numpy as np
 
+from . import _abi
+
+# the device environment ids (DRPO_ENV_*; tests/test_path_queries.py pins them to drpo_abi_const)
 ENV_IDS = {'PointRobot': 0, 'QuadrotorWrapperEnv': 1, 'SafeInvertedPendulumEnv': 2,
            'SimuVeh3dofcontiSurrCstr': 3}
 ENV_NAMES = {'point-robot': 0, 'quadrotor': 1, 'cartpole': 2, 'cartpole-move': 2, 'cartpole-upright': 2,
@@ -17,7 +20,7 @@ QUAD_X_THRESHOLD, QUAD_Z_THRESHOLD = 2.0, 3.0   # safe_control_gym defaults (unp
 CART_X_THRESHOLD, CART_TH_THRESHOLD = 0.9, 0.2   # SafeInvertedPendulumEnv defaults (inverted_pendulum.py:11-16)
 
 
-ENV_PROGRAM = 4   # DRPO_ENV_PROGRAM: constraint functions described by a ConstraintProgram
+ENV_PROGRAM = _abi.ENV_PROGRAM   # DRPO_ENV_PROGRAM: constraint functions described by a ConstraintProgram
 PROGRAM_ATTR = 'drpo_constraint_program'
 
 
@@ -73,7 +76,8 @@ class ConstraintProgram:
                 .done_box((0, 1), -3.0, 3.0).done_ball((0, 1), (2.2, 2.2), 0.3))
     """
 
-    MAX_ROWS, MAX_TERMS, MAX_CENTRES, MAX_BOX = 8, 8, 8, 8
+    MAX_ROWS, MAX_TERMS, MAX_CENTRES, MAX_BOX = (_abi.PROG_MAX_ROWS, _abi.PROG_MAX_TERMS, _abi.PROG_MAX_CENTRES,
+                                                 _abi.PROG_MAX_BOX)
 
     def __init__(self):
         self.rows = []             # ('affine', dims, coefs, bias) | ('balls', dims, centres [n][nd], radius)
@@ -258,7 +262,6 @@ class ConstraintProgram:
 
     # ------------------------------------------------------------------ packing / upload
     def _struct(self):
-        from . import _abi
         self._require_complete()
         p = _abi.EnvProgram()
         p.C = self.C

@@ -6,17 +6,25 @@ drpo_wgrad_item_t, the with_* helpers attach the multi-job launch's fused pieces
 by the SAC engine (sac_step.py), the ensemble engine (ensemble_engine.py) and the
 stand-alone forwards of ops.py."""
 import ctypes
+from collections import namedtuple
 
 import torch
 
 from . import _lib
-from ._abi import MlpBwd, MlpFwd, WgradItem
+from ._abi import MlpBwd, MlpFwd, MlpNet, WgradItem
 
+# the ids below mirror include/drpo_hip.h (DRPO_ACT_*, DRPO_UPSTREAM_*, DRPO_HEAD_*): they are
+# read at import, before the library loads, and tests/test_path_queries.py pins each to
+# drpo_abi_const
 ACT_ID = {None: 0, 'identity': 0, 'relu': 1, 'swish': 2, 'tanh': 3}
+
+# one layer as the kernels see it: packed forward mirror, bias, widths, activation id,
+# packed transposed mirror (None for a group that is never trained)
+Layer = namedtuple('Layer', 'P b din dout act PT')
 
 
 def spec_layers(group, prefix, spec, buf=None):
-    """[(P, b, din, dout, act, PT)] for an MLPSpec stored under prefix in a flat group:
+    """[Layer] for an MLPSpec stored under prefix in a flat group:
     P / PT are the layer's packed forward / transposed weight mirrors (group.pview),
     b the bias view (of ``buf`` if given, else the group data)."""
     out = []
@@ -26,16 +34,16 @@ def spec_layers(group, prefix, spec, buf=None):
         key = f'{prefix}{2 * i}.weight'
         b = group.view(f'{prefix}{2 * i}.bias', buf)
         PT = group.pview(key, True)
-        out.append((group.pview(key)[0], b, spec.dims[i], spec.dims[i + 1], ACT_ID[act],
-                    None if PT is None else PT[0]))
+        out.append(Layer(group.pview(key)[0], b, spec.dims[i], spec.dims[i + 1], ACT_ID[act],
+                         None if PT is None else PT[0]))
     return out
 
 
 class Net:
-    """One MLP as seen by the kernels: layer tuples + (optional) per-layer save buffers."""
+    """One MLP as seen by the kernels: layers + (optional) per-layer save buffers."""
 
     def __init__(self, layers, grad_layers=None):
-        self.layers = layers              # [(P, b, din, dout, act, PT)]
+        self.layers = [Layer(*x) for x in layers]
         self.grad_layers = grad_layers    # [(gW, gb)] or None
         self.sy = [None] * len(layers)
         self.sz = [None] * len(layers)
@@ -44,11 +52,17 @@ class Net:
 
     @property
     def dout(self):
-        return self.layers[-1][3]
+        return self.layers[-1].dout
 
     @property
     def din(self):
-        return self.layers[0][2]
+        return self.layers[0].din
+
+    def desc(self):
+        """This net as a drpo_mlp_net_t: what the path queries of include/drpo_hip.h take."""
+        d = MlpNet()
+        fill_net(d, self)
+        return d
 
 
 def _p(t):
@@ -58,9 +72,8 @@ def _p(t):
 def fill_net(dst, net, wstride=None):
     """drpo_mlp_net_t of a Net (layers, save buffers, per-member strides)."""
     dst.nl = len(net.layers)
-    for l, (W, b, din, dout, act, WT) in enumerate(net.layers):
-        L = dst.L[l]
-        L.W, L.b, L.din, L.dout, L.act = W.data_ptr(), b.data_ptr(), din, dout, act
+    for l, (L, lay) in enumerate(zip(dst.L, net.layers)):   # (a net of more than 3 layers: the library refuses nl)
+        L.W, L.b, L.din, L.dout, L.act = lay.P.data_ptr(), lay.b.data_ptr(), lay.din, lay.dout, lay.act
         L.sy, L.sz = _p(net.sy[l]), _p(net.sz[l])
         L.wstride, L.bstride = (0, 0) if wstride is None else wstride[l]
 
@@ -85,16 +98,8 @@ def fill_fwd(nets, srcs, rows, trunk=False, save_x=None, norm=None, nbatch=1, ws
 
 
 def pairable(a, b):
-    """Two nets one pair job can run (csrc/mlp.hip pair_ok): 3-layer ReLU nets of one shape
-    [K <= 16 or 49..64 -> 256 -> 256 -> <= 16] (the reference's default widths)."""
-    la, lb = a.layers, b.layers
-    if len(la) != 3 or len(lb) != 3:
-        return False
-    if any(x[2:5] != y[2:5] for x, y in zip(la, lb)):
-        return False
-    (_, _, k0, n0, a0, _), (_, _, k1, n1, a1, _), (_, _, _, n2, a2, _) = la
-    return ((k0 + 15) // 16 in (1, 4) and n0 == 256 and k1 == 256 and n1 == 256 and n2 <= 16 and
-            a0 == ACT_ID['relu'] and a1 == ACT_ID['relu'] and a2 == 0)
+    """Two nets one pair job can run: what drpo_mlp_forward_multi admits with pair = 1."""
+    return bool(_lib.lib().drpo_mlp_pair_ok(ctypes.byref(a.desc()), ctypes.byref(b.desc())))
 
 
 def with_pre(d, policy, mode, A, eps, site, logp=None):

@@ -225,16 +225,16 @@ def _fill_call(d, marr, alg, noise, start, members, eps_a, eps_m, ctr, engine, e
     d.rows_per_tile = getattr(alg, 'rows_per_tile', 0)
     d.engine, d.eps_layout = engine, (eps_layout if eps_a is not None else 0)
     d.step_events = timer.events if timer is not None else None
-    if timer is not None:
-        timer.pairs = 1 if engine == 2 else len(marr)
+    if timer is not None:   # (the engine the library runs for this descriptor)
+        timer.pairs = 1 if _lib.lib().drpo_rollout_engine(ctypes.byref(d)) == 2 else len(marr)
 
 
 def rollout(alg, policy, initial_states, noise, timer=None, eps_layout=0):
     """One imagined rollout (src/smbpo.py:229-249) into alg.virt_buffer.
 
-    Engine (``alg.rollout_engine``, 0 = auto): 2 = fused horizon kernel (default for
-    device noise), 1 = one launch per horizon step (used for recorded reference
-    draws, which are indexed by the compacted row of each step). ``eps_layout=1``
+    Engine (``alg.rollout_engine``, 0 = auto, the library's choice: drpo_rollout_engine):
+    2 = fused horizon kernel (default for device noise), 1 = one launch per horizon step
+    (used for recorded reference draws, which are indexed by the compacted row of each step). ``eps_layout=1``
     marks a tape whose per-step draws are indexed by the original batch row
     ([B] rows every step), which drives engine 2 with recorded draws."""
     H, model, vb = alg.horizon, alg.model_ensemble, alg.virt_buffer._module
@@ -248,16 +248,16 @@ def rollout(alg, policy, initial_states, noise, timer=None, eps_layout=0):
     policy.group.ensure_packed()
     model.group.ensure_packed()
     d, marr, count, _ = _rollout_static(alg, policy, B, H, buffer=True)
-    engine = getattr(alg, 'rollout_engine', 0)
-    if engine == 0:
-        engine = 1 if (noise.parity and eps_layout == 0) or H > 128 else 2
-    _fill_call(d, marr, alg, noise, start, members, eps_a, eps_m, ctr, engine, eps_layout, timer)
+    _fill_call(d, marr, alg, noise, start, members, eps_a, eps_m, ctr, getattr(alg, 'rollout_engine', 0), eps_layout,
+               timer)
     _lib.check(_lib.lib().drpo_rollout(ctypes.byref(d), _lib.stream()), 'rollout')
     vb._device_advanced()
     return _RolloutResult(vb, start_ptr, count, ns)
 
 
-TRAJ_MAX_H = 128    # the fused engine's horizon limit (PERSIST_MAX_H)
+# the fused engine's horizon limit (DRPO_ROLLOUT_FUSED_MAX_H; read at import, before the
+# library loads: tests/test_path_queries.py pins it to drpo_abi_const)
+TRAJ_MAX_H = 128
 
 
 def _traj_spec(B, H, S, A, C):

@@ -154,7 +154,9 @@ def ema_segment(p, start, end, target, rate, pack_map=None):
     return sg
 
 
-OPT_MAXSEG = 8   # segments per drpo_optim_step launch (csrc/optim.hip)
+# segments per drpo_optim_step launch (DRPO_OPTIM_MAX_SEGS; read at import, before the library
+# loads: tests/test_path_queries.py pins it to drpo_abi_const)
+OPT_MAXSEG = 8
 
 
 def fused_step(segs):

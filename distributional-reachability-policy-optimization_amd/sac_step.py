@@ -30,9 +30,9 @@ import torch
 
 from . import _lib, ops
 from ._abi import ActorHead, BufferView, CriticHead, MlpFbJob, SumDesc
-from .mlp_desc import (ACT_ID, HEAD_MEAN, HEAD_RSAMPLE, HEAD_SAMPLE, UPSTREAM_ACTOR_CC, UPSTREAM_CERT, UPSTREAM_CRITIC,
+from .mlp_desc import (HEAD_MEAN, HEAD_RSAMPLE, HEAD_SAMPLE, UPSTREAM_ACTOR_CC, UPSTREAM_CERT, UPSTREAM_CRITIC,
                        UPSTREAM_NEG_MEAN, UPSTREAM_SAFE_CC, UPSTREAM_SQUASH, UPSTREAM_SQUASH_SAFE, Net, _p,
-                       bwd_flops, fill_bwd, fill_fwd, fwd_flops, pairable, spec_layers, wgrad_flops, wgrad_items,
+                       bwd_flops, fill_bwd, fill_fwd, fwd_flops, spec_layers, wgrad_flops, wgrad_items,
                        wgrad_workspace, with_head, with_post, with_pre)
 from .mlp_desc import LaunchProfiler  # noqa: F401  (bench.py --full takes the engine's profiler class from here)
 from .optim import ema_segment, fused_step, grad_sumsq_multi
@@ -158,6 +158,18 @@ class SACEngine:
             n['cc_ls' + tag] = mk(grp, 'constraint_critic.log_std_head.', ccs.logstd_spec, gr)
         if sol.mlp_multiplier:
             n['mult'] = mk(mg, 'lam.', sol.multiplier.spec)
+        # Which fused launches these nets' shapes admit: asked of the library (the path
+        # queries of include/drpo_hip.h, the conditions its entry points check) once per net
+        # set. A step reads these ANDed with the switches above (_post_mult, _fb_actor).
+        L, ref = _lib.lib(), lambda key: ctypes.byref(n[key].desc())
+        cc = [ref(k) for k in ('cc_trunk', 'cc_mean', 'cc_ls')]
+        self.pair_q = bool(L.drpo_mlp_pair_ok(ref('q0'), ref('q1')))
+        self.pair_pi = bool(L.drpo_mlp_pair_ok(ref('actor'), ref('safe')))
+        self.ccb_shapes = bool(L.drpo_mlp_heads_paired(*cc))
+        self.post_shapes = self.fb_shapes = False
+        if sol.mlp_multiplier:
+            self.post_shapes = self.ccb_shapes and bool(L.drpo_mlp_post_ok(S, ref('mult')))
+            self.fb_shapes = bool(L.drpo_mlp_fb_ok(S, *cc, ref('mult'), ref('q0'), ref('q1'), C))
         self.nets_view = {}
         # forward saves (post-activations) and dz for every trained net
         for key, net in n.items():
@@ -298,12 +310,9 @@ class SACEngine:
         return {sg: self.buf(f'sq.{key}.{sg}', 4096) for sg in segs}
 
     def _ccb_fused(self):
-        """The multi-job forward can form the bound when the constraint critic's heads are
-        pairable (256-wide trunk, two [256 -> H -> C <= 16] heads: the reference widths)."""
-        t, h1, h2 = self._cc_nets()
-        (_, _, _, tw, _, _), l1, l2 = t.layers[-1], h1.layers, h2.layers
-        return (tw == 256 and len(l1) == 2 and len(l2) == 2 and l1[0][3] == l2[0][3] and l1[1][3] <= 16
-                and l2[1][3] <= 16 and l1[0][4] == l2[0][4] and l1[1][4] == l2[1][4])
+        """The multi-job forward can form the bound: the constraint critic's heads run paired
+        (drpo_mlp_heads_paired; the reference widths do)."""
+        return self.ccb_shapes
 
     def _ccb(self, d, out, dist):
         """The constraint critic's max-C upper bound (the one drpo_cc_head computes) formed
@@ -319,25 +328,14 @@ class SACEngine:
     def _post_mult(self):
         """The multiplier forward as a post chain of the bound's job (csrc/mlp.hip,
         drpo_mlp_fwd_t.post) when the shapes allow it (self.post_mult)."""
-        return (self.post_mult and self._ccb_fused() and self.S + 1 <= 64 and
-                self.nets['mult'].layers[0][2] == self.S + 1)
+        return self.post_mult and self.post_shapes
 
     def _fb_actor(self, dist):
-        """The actor update runs 'a.fb' (drpo_mlp_fb_multi's conditions, csrc/mlp.hip): the
-        MLP multiplier as a post chain, the distributional certificate with paired
-        256-wide heads, not the cost certificate, ReLU hidden layers wider than 16 and
-        identity outputs everywhere."""
-        sol, n = self.sol, self.nets
-        if not (self.fb_actor and sol.mlp_multiplier and dist and not self.cost and self._post_mult()):
-            return False
-        relu = ACT_ID['relu']
-        t, h1, h2 = self._cc_nets()
-
-        def hidden(layers):
-            return all(l[4] == relu and l[3] > 16 for l in layers)
-        return (n['mult'].dout == 1 and hidden(t.layers) and
-                all(hidden(h.layers[:1]) and h.layers[0][3] == 256 and h.layers[1][4] == 0 for h in (h1, h2)) and
-                all(hidden(q.layers[:-1]) and tuple(q.layers[-1][3:5]) == (1, 0) for q in (n['q0'], n['q1'])))
+        """The actor update runs 'a.fb' (drpo_mlp_fb_multi): the MLP multiplier as a post
+        chain, the distributional certificate, not the cost certificate, and the shapes that
+        launch admits (drpo_mlp_fb_ok)."""
+        return bool(self.fb_actor and self.sol.mlp_multiplier and dist and not self.cost and self._post_mult() and
+                    self.fb_shapes)
 
     def _cc_bound_after(self, name, out, dist):
         """drpo_cc_head over the saved head outputs of job `name` when _ccb could not fuse it."""
@@ -422,7 +420,7 @@ class SACEngine:
         # (robust: the model's s') -> target certificate at (s', a'_safe); a' ~ pi(s') with
         # log pi -> target twins at (s', a') (src/ssac.py:284-294,304-400). The cost certificate
         # draws its next action from the actor instead (src/ssac.py:306-310).
-        pq = pairable(n['q0'], n['q1'])
+        pq = self.pair_q
         tpol = n['actor' if self.cost else 'safe']
         # early_actor: the following actor update's first forward (actor / safe-actor
         # rsample, independent of the critic update) rides in this launch as its shortest
@@ -708,7 +706,7 @@ class SACEngine:
         if not mlp_mult:
             return self._policy_jobs(n['actor'], pi, save_x=xa)
         # (its own job runs a no-save view; the pair job keeps the net's save buffers)
-        safe = n['safe'] if pairable(n['actor'], n['safe']) else Net(n['safe'].layers)
+        safe = n['safe'] if self.pair_pi else Net(n['safe'].layers)
         return self._policy_jobs(n['actor'], pi, safe, dict(mode=HEAD_MEAN, eps=None, site=0, amean=am), save_x=xa)
 
     def _policy_jobs(self, actor, head, safe=None, head2=None, save_x=None):
@@ -719,7 +717,7 @@ class SACEngine:
         src, B, A = [(self.bs, self.S), (None, 0), (None, 0)], self.B, self.A
         if safe is None:
             return [with_head(fill_fwd([actor], src, B, save_x=save_x), A=A, **head)]
-        if pairable(actor, safe):
+        if self.pair_pi:
             d = fill_fwd([actor, safe], src, B, save_x=save_x, pair=True)
             return [with_head(with_head(d, A=A, **head), A=A, second=True, **head2)]
         return [with_head(fill_fwd([actor], src, B, save_x=save_x), A=A, **head),
@@ -742,7 +740,7 @@ class SACEngine:
         if v is None:
             v = Net(net.layers, net.grad_layers)
             last = len(net.layers) - 1
-            if net.layers[last][3] <= 16:
+            if net.layers[last].dout <= 16:
                 v.sy[last] = self.buf(f'{name}.sy{last}', self.B, net.dout)
             self.nets_view['fb.' + name] = v
         return v

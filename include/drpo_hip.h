@@ -84,9 +84,21 @@ typedef struct {
  * out-of-bounds read in the kernel. DRPO_EINVAL with a message otherwise. */
 int drpo_env_program_check(const drpo_env_program_t* host_prog, int S);
 
+/* limits of the launches; a binding that mirrors one checks it against drpo_abi_const */
+enum {
+  DRPO_ROLLOUT_FUSED_MAX_H = 128, /* horizon of the fused rollout engine (engine 2, drpo_rollout_trajectories*) */
+  DRPO_OPTIM_MAX_SEGS = 8,        /* segments of one drpo_optim_step */
+  DRPO_MLP_MULTI_MAX_JOBS = 8,    /* jobs of one drpo_mlp_forward_multi / drpo_mlp_backward_multi* */
+  DRPO_MLP_MULTI_MAX_SLOTS = 16,  /* (job, net) workgroup slots of such a launch */
+  DRPO_MLP_FB_MAX_JOBS = 4        /* jobs of one drpo_mlp_fb_multi */
+};
+
 /* ---------------------------------------------------------------- library */
 int drpo_version(void);
 int64_t drpo_abi_sizeof(const char* struct_name);   /* binding self-check */
+/* the value of an enum constant or DRPO_UPSTREAM_* macro of this header by its name
+ * ("DRPO_ACT_RELU"), -1 for an unknown name: a binding's mirrors are checked against it */
+int64_t drpo_abi_const(const char* name);
 const char* drpo_last_error(void);
 /* SHA-256 (hex) of the csrc/include sources this binary was built from; the Python
  * binding refuses a library whose digest differs from the sources beside it */
@@ -312,8 +324,9 @@ typedef struct {
 
 /* squashed-Gaussian policy head fused into a forward pass: applied to net[0]'s
  * final output (2A columns = [mu | log-std pre-activation]), src/policy.py:88-97 */
+enum { DRPO_HEAD_NONE = 0, DRPO_HEAD_SAMPLE = 1, DRPO_HEAD_RSAMPLE = 2, DRPO_HEAD_MEAN = 3 };
 typedef struct {
-  int mode;            /* 0 none, 1 sample (Normal.sample), 2 rsample, 3 mean only (tanh(mu)) */
+  int mode;            /* DRPO_HEAD_*: 0 none, 1 sample (Normal.sample), 2 rsample, 3 mean only (tanh(mu)) */
   int A;
   const float* eps;    /* [rows][A] recorded draws, or NULL: Philox (launch seed/ctr, this site) */
   uint32_t site;
@@ -813,6 +826,31 @@ int drpo_normalizer_fit(const float* X, int64_t N, int S, float* mean, float* st
                         drpo_stream_t stream);
 int drpo_normalize(const float* x, const float* mean, const float* std, float eps, float* y, int64_t n, int S,
                    drpo_stream_t stream);
+
+/* ---------------------------------------------------------------- path queries
+ * Every fused launch has a general launch behind it, and an entry point refuses the
+ * shapes its kernel cannot run. These host-only queries are those shape conditions
+ * (csrc/path_shapes.hpp: the functions the entry points themselves call), for a caller
+ * that picks the path before it builds the launch. They need no device, read nothing
+ * but the descriptors they are given (never a weight or save pointer; a NULL descriptor
+ * is a no), and return 1 (yes) or 0.                                             */
+/* drpo_mlp_forward_multi admits a `pair` job over these two nets */
+int drpo_mlp_pair_ok(const drpo_mlp_net_t* a, const drpo_mlp_net_t* b);
+/* a trunk job over these nets runs its heads paired and may carry ccb_out */
+int drpo_mlp_heads_paired(const drpo_mlp_net_t* trunk, const drpo_mlp_net_t* h1, const drpo_mlp_net_t* h2);
+/* a job with ccb_out and cols[0] == cols0 may carry this post chain */
+int drpo_mlp_post_ok(int cols0, const drpo_mlp_net_t* post);
+/* drpo_mlp_fb_multi admits the actor update's three jobs over these nets: the certificate
+ * (trunk, h1, h2; C outputs) with `post` chained behind its bound on cols0 columns, the
+ * certificate again, and each of q0 / q1 */
+int drpo_mlp_fb_ok(int cols0, const drpo_mlp_net_t* trunk, const drpo_mlp_net_t* h1, const drpo_mlp_net_t* h2,
+                   const drpo_mlp_net_t* post, const drpo_mlp_net_t* q0, const drpo_mlp_net_t* q1, int C);
+/* the model fit step's launches for these descriptors: bit 0 drpo_mlp_backward_ens admits
+ * bwd's shapes (its upstream taken as DRPO_UPSTREAM_ENS), bit 1 drpo_ens_fit_fb admits
+ * fwd's and bwd's */
+int drpo_ens_fit_paths(const drpo_mlp_fwd_t* fwd, const drpo_mlp_bwd_t* bwd, const drpo_ens_upstream_t* up);
+/* the engine (1 or 2) drpo_rollout runs for this descriptor (d->engine when it is not 0) */
+int drpo_rollout_engine(const drpo_rollout_desc_t* d);
 
 #ifdef __cplusplus
 }

@@ -298,16 +298,14 @@ def test_config_full_width_fit_vs_oracle(c):
 def test_fit_head_hidden_layers_2_vs_oracle():
     """A model with head_hidden_layers=2 (a config option; the reference default is 1)
     is outside drpo_mlp_backward_ens's shapes: the fit must take the separate NLL launch
-    + generic backward (ensemble_engine.ens_fused_shapes), not raise from the fused one."""
-    from drpo_amd.ensemble_engine import ens_fused_shapes
+    + generic backward (FitPlan.fused, from drpo_ens_fit_paths), not raise from the fused one."""
     cd = bench.CONFIGS[2]
     torch.manual_seed(11)
     alg = bench.make_alg(DEV, 256, cd['H'], cd['E'], 11, bench.ENV_JSON[cd['env']], env=cd['env'],
                          extra={'model_cfg': {'head_hidden_layers': 2}})
     m = alg.model_ensemble
     assert m.head_hidden_layers == 2
-    nets, _ = m.engine._nets(grads=False)
-    assert not ens_fused_shapes(nets, m.state_dim + 1)
+    assert not m.engine.fit_plan().fused
     _fill(alg, cd['env'], 30000, 8)
     buf = {k: v.cpu() for k, v in alg.replay_buffer.get(as_dict=True).items()}
     P = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}

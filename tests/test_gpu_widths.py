@@ -160,12 +160,10 @@ def test_width_sac_update_vs_oracle(hid, mh):
 
 @pytest.mark.parametrize('hid,mh', WIDTHS)
 def test_width_fit_vs_oracle(hid, mh):
-    from drpo_amd.ensemble_engine import ens_fused_shapes
     env = 'point-robot'
     alg = _alg(env, hid, mh)
     m = alg.model_ensemble
-    nets, _ = m.engine._nets(grads=False)
-    assert not ens_fused_shapes(nets, m.state_dim + 1)
+    assert not m.engine.fit_plan().fused
     _fill(alg, env, 30000, 6)
     buf = {k: v.cpu() for k, v in alg.replay_buffer.get(as_dict=True).items()}
     P = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}

@@ -163,8 +163,9 @@ PAIR_SHAPES = [([K, 256, 256, 6], R3) for K in (16, 17, 48, 49, 64, 65)] + [
 
 
 def test_pairable_agrees_with_the_c_pair_check():
-    """mlp_desc.pairable (which picks pair jobs) against csrc/mlp.hip pair_ok (which admits
-    them), through a rows = 0 drpo_mlp_forward_multi call with pair = 1."""
+    """mlp_desc.pairable (which picks pair jobs: drpo_mlp_pair_ok over the nets' shapes) against
+    csrc/mlp.hip pair_ok (which admits them), through a rows = 0 drpo_mlp_forward_multi call with
+    pair = 1."""
     L = _lib.lib()
     verdicts = []
     cases = [(s, s) for s in PAIR_SHAPES] + [(PAIR_SHAPES[0], ([16, 256, 256, 4], R3)),    # two shapes
