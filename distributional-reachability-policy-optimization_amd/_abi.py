@@ -57,6 +57,12 @@ class RolloutLinear(ctypes.Structure):
     _fields_ = [('candidates', c_int), ('blend', P)]
 
 
+class RolloutCut(ctypes.Structure):
+    """drpo_rollout_cut_t"""
+    _fields_ = [('scores', P), ('row_stride', c_int64), ('step_stride', c_int64), ('threshold', c_float),
+                ('halted_at', P)]
+
+
 ENV_PROGRAM = 4          # DRPO_ENV_PROGRAM
 PROG_AFFINE, PROG_BALLS = 0, 1
 PROG_MAX_ROWS = PROG_MAX_TERMS = PROG_MAX_CENTRES = PROG_MAX_BOX = 8
@@ -133,6 +139,10 @@ PROTOTYPES = {
                                                    P]),
     'drpo_rollout_trajectories_linear': (c_int, [POINTER(RolloutDesc), POINTER(RolloutShield), POINTER(RolloutLinear),
                                                  POINTER(RolloutTraj), P]),
+    'drpo_rollout_stage': (c_int, [POINTER(RolloutDesc), P]),
+    'drpo_rollout_emit_cut': (c_int, [POINTER(RolloutDesc), POINTER(RolloutCut), P]),
+    'drpo_rollout_trajectories_cut': (c_int, [POINTER(RolloutDesc), POINTER(RolloutCut), POINTER(RolloutTraj), P]),
+    'drpo_rollout_staging_offsets': (c_int, [c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     'drpo_env_constraints': (c_int, [c_int, c_int, c_int, c_double, c_double, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_constraints_program': (c_int, [P, c_int, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_program_check': (c_int, [POINTER(EnvProgram), c_int]),

@@ -1377,6 +1377,7 @@ struct TrajArgs {
   const float *st_s, *st_s2, *st_a, *st_r, *st_h;   // staging [t][original row], real widths A and C
   const uint8_t* st_dv;
   drpo_rollout_traj_t out;
+  const int* newlen;   // [B] or nullptr: row i keeps its first newlen[i] <= its natural length steps (rollout_cut_kernel)
 };
 
 // the weights are wave-uniform data no kernel writes: read like the constraint programs
@@ -1426,7 +1427,9 @@ __global__ __launch_bounds__(TRAJ_NT) void rollout_traj_kernel(TrajArgs p) {
       int fv = -1;
       unsigned last = 0;
       double acc = 0.0;
-      for (int t = 0; t < H; ++t) {
+      // a cut row (newlen < its natural length) ends alive: last keeps a clear done bit
+      const int lim = p.newlen ? min(max(p.newlen[i], 0), H) : H;
+      for (int t = 0; t < lim; ++t) {
         const size_t src = (size_t)t * B + i;
         const unsigned dv = p.st_dv[src];
         const float r = p.st_r[src];
@@ -1463,7 +1466,8 @@ __global__ __launch_bounds__(TRAJ_NT) void rollout_traj_kernel(TrajArgs p) {
       const size_t i = (size_t)row0 + r;
       float* dst = o.states + i * (H + 1) * S + k;
       traj_steps<false>(p.st_s + i * S + k, B * S, dst, S, len);
-      dst[(size_t)len * S] = p.st_s2[((size_t)(len - 1) * B + i) * S + k];
+      // length 0 (a row cut at its first step): the start state, which step 0 staged
+      dst[(size_t)len * S] = len > 0 ? p.st_s2[((size_t)(len - 1) * B + i) * S + k] : p.st_s[i * S + k];
       for (int t = len + 1; t <= H; ++t) dst[(size_t)t * S] = 0.f;
     } else if (e < nS + nA) {
       const int q = e - nS, r = q / A, d = q - r * A, len = s_len[r];
@@ -1475,12 +1479,84 @@ __global__ __launch_bounds__(TRAJ_NT) void rollout_traj_kernel(TrajArgs p) {
       const int q = e - nS - nA, r = q / C, c = q - r * C, len = s_len[r];
       const size_t i = (size_t)row0 + r;
       float* dst = o.constraint_values ? o.constraint_values + i * H * C + c : nullptr;
-      const float m = traj_steps<true>(p.st_h + i * C + c, B * C, dst, C, len);
+      const float m = len > 0 ? traj_steps<true>(p.st_h + i * C + c, B * C, dst, C, len) : -INFINITY;   // max's identity
       if (dst)
         for (int t = len; t < H; ++t) dst[(size_t)t * C] = 0.f;
       if (o.hmax) o.hmax[i * C + c] = m;
     }
   }
+}
+
+// ---------------------------------------------------------------------------
+// Halting (drpo_rollout_emit_cut, drpo_rollout_trajectories_cut): a post-pass on the
+// staged horizon. Row i is cut at the first step t of its life whose score is not
+// <= thr (a NaN cuts, a score equal to thr does not); steps t >= the cut do not exist.
+// Neither kernel makes a draw or touches the staged rows themselves.
+// ---------------------------------------------------------------------------
+
+// One lane per original row: walks the row's done bits as phase A of rollout_traj_kernel
+// does (a row was staged at t exactly when it was alive at t) and its scores, which the
+// caller lays out by a row and a step stride in elements. Scores at or beyond the row's
+// length are never read. newlen[i]: the cut if there is one, else the natural length.
+// Both walks load four steps at a time: the loads of a group do not wait for one another
+// (one load per step in a chain measured 10.5 us for cut + recount at B 4096, H 10).
+__global__ __launch_bounds__(256) void rollout_cut_kernel(const uint8_t* __restrict__ st_dv,
+                                                          const float* __restrict__ scores, int64_t row_stride,
+                                                          int64_t step_stride, float thr, int B, int H,
+                                                          int* __restrict__ newlen, int* __restrict__ halted_at) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= B) return;
+  // the natural length: the first done bit. Every [t][i] slot with t < H lies inside the
+  // staging; those behind the first done bit were never staged and are not looked at.
+  int len = -1;
+  for (int t0 = 0; t0 < H && len < 0; t0 += 4) {
+    unsigned dv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) dv[u] = t0 + u < H ? st_dv[(int64_t)(t0 + u) * B + i] : 0u;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (len < 0 && (dv[u] & 1)) len = t0 + u + 1;
+  }
+  if (len < 0) len = H;   // cut by the horizon
+  // the first score of the row's life that is not <= thr (thr itself stands in beyond it)
+  int cut = -1;
+  for (int t0 = 0; t0 < len && cut < 0; t0 += 4) {
+    float sc[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) sc[u] = t0 + u < len ? scores[i * row_stride + (int64_t)(t0 + u) * step_stride] : thr;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (cut < 0 && !(sc[u] <= thr)) cut = t0 + u;
+  }
+  newlen[i] = cut >= 0 ? cut : len;
+  if (halted_at) halted_at[i] = cut;
+}
+
+// One wave per (step, tile): the tile's list of rows alive at the step, filtered by
+// t < newlen[row], order kept (ballot + prefix popcount), in place; the new count. A tile
+// that had emptied keeps count 0. Counts and in-tile indices come back from memory and are
+// clamped to the tile, so that a workspace that is not the staging of this shape gives
+// wrong rows and never an access outside the tile's rows.
+template <int ROWS>
+__global__ __launch_bounds__(256) void rollout_recount_kernel(int* __restrict__ cnt, int* __restrict__ inv,
+                                                              const int* __restrict__ newlen, int B, int H,
+                                                              int ntiles) {
+  const int lane = threadIdx.x & 63;
+  const int64_t ti = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);   // t * ntiles + tile
+  if (ti >= (int64_t)H * ntiles) return;                             // wave-uniform
+  const int t = (int)(ti / ntiles), tile = (int)(ti - (int64_t)t * ntiles);
+  const int c = min(max(cnt[ti], 0), ROWS);
+  int r = 0;
+  bool keep = false;
+  if (lane < c) {
+    r = min(max(inv[ti * ROWS + lane], 0), ROWS - 1);
+    const int64_t row = (int64_t)tile * ROWS + r;
+    keep = row < B && t < newlen[row];
+  }
+  const uint64_t mk = __ballot(keep);
+  // every lane has read its entry before any lane writes: one wave, in lockstep
+  if (keep) inv[ti * ROWS + __popcll(mk & ((1ull << lane) - 1ull))] = r;
+  if (lane == 0) cnt[ti] = __popcll(mk);
 }
 
 // ---------------------------------------------------------------------------
@@ -1504,6 +1580,8 @@ struct RolloutWs {
   float *st_s, *st_s2, *st_a, *st_r, *st_h;
   uint8_t* st_dv;
   int *st_cnt, *st_inv, *pos;
+  // halting: the rows' lengths after the cut (rollout_cut_kernel); last, so no other piece moves
+  int* newlen;
 };
 
 // Carves the workspace at `base` (0: the pieces' byte offsets); returns its size in bytes.
@@ -1531,6 +1609,7 @@ static size_t rollout_ws(int B, int S, int H, uintptr_t base, RolloutWs& w) {
   take(w.st_cnt, sizeof(int) * (size_t)H * T16);
   take(w.st_inv, sizeof(int) * (size_t)H * (B + 32));
   take(w.pos, sizeof(int) * (size_t)H * T16);
+  take(w.newlen, sizeof(int) * (size_t)B);
   return o;
 }
 
@@ -1545,6 +1624,18 @@ DRPO_API size_t drpo_rollout_count_offset(int B, int S, int H) {
   RolloutWs w;
   rollout_ws(B, S, H, 0, w);
   return (size_t)reinterpret_cast<uintptr_t>(w.off + H);
+}
+
+// Byte offsets (inside the workspace) of the fused engine's staged states [H][B][S] and
+// actions [H][B][A] (step-major, original row; a row's step is staged iff the row was alive).
+DRPO_API int drpo_rollout_staging_offsets(int B, int S, int H, size_t* st_s, size_t* st_a) {
+  DRPO_REQUIRE(B >= 1 && S >= 1 && H >= 1 && st_s && st_a, "drpo_rollout_staging_offsets: B=%d S=%d H=%d or a null output",
+               B, S, H);
+  RolloutWs w;
+  rollout_ws(B, S, H, 0, w);
+  *st_s = (size_t)reinterpret_cast<uintptr_t>(w.st_s);
+  *st_a = (size_t)reinterpret_cast<uintptr_t>(w.st_a);
+  return DRPO_OK;
 }
 
 // The fields RolloutStepArgs and PersistArgs share, from the descriptor.
@@ -1701,12 +1792,14 @@ static int persist_run(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt
   return DRPO_OK;
 }
 
-// engine 2: fused-horizon kernel + one of the two emit tails
-static int rollout_fused(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt, int64_t rlen, hipStream_t stream) {
+// which of the two emit tails a (horizon, tile count) takes
+static bool emit_is_self(int H, int B, int rpt) { return (int64_t)H * ((B + rpt - 1) / rpt) <= EMIT_SELF_MAX; }
+
+// The emit tail over the staging and counts `a` names: one launch for small rollouts (the
+// horizon kernel has copied the buffer pointer into off[H + 1]), else scan + emit + finalize.
+static int emit_tail(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt, const PersistArgs& a, bool self_emit,
+                     hipStream_t stream) {
   const int H = d->H;
-  const bool self_emit = (int64_t)H * ((d->B + rpt - 1) / rpt) <= EMIT_SELF_MAX;
-  PersistArgs a{};
-  if (const int rc = persist_run(d, w, rpt, rlen, self_emit, "drpo_rollout", stream, a)) return rc;
   const dim3 eg((unsigned)((a.ntiles * rpt + 255) / 256), (unsigned)H);
   const EmitDst dst{d->vs, d->va, d->vs2, d->vr, d->vh, d->vd, d->vv, d->vcap};
   if (self_emit) {
@@ -1723,6 +1816,14 @@ static int rollout_fused(const drpo_rollout_desc_t* d, const RolloutWs& w, int r
   rollout_persist_finalize_kernel<<<1, 1, 0, stream>>>(d->vptr, w.n, w.off, H);
   DRPO_LAUNCH_CHECK("rollout_finalize");
   return DRPO_OK;
+}
+
+// engine 2: fused-horizon kernel + one of the two emit tails
+static int rollout_fused(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt, int64_t rlen, hipStream_t stream) {
+  const bool self_emit = emit_is_self(d->H, d->B, rpt);
+  PersistArgs a{};
+  if (const int rc = persist_run(d, w, rpt, rlen, self_emit, "drpo_rollout", stream, a)) return rc;
+  return emit_tail(d, w, rpt, a, self_emit, stream);
 }
 
 // engine 1: one launch per horizon step + pointer advance
@@ -1914,6 +2015,94 @@ DRPO_API int drpo_rollout_trajectories_linear(const drpo_rollout_desc_t* d, cons
                                               const drpo_rollout_linear_t* linear, const drpo_rollout_traj_t* out,
                                               drpo_stream_t stream) {
   return rollout_trajectories(d, nullptr, shield, linear, out, "drpo_rollout_trajectories_linear", (hipStream_t)stream);
+}
+
+// ---- halting: stage, then cut + emit; or cut + the trajectory tail ------------------
+
+// What the three halting entry points check alike after rollout_checks: the fused engine.
+static int halt_engine_checks(const drpo_rollout_desc_t* d, const char* who) {
+  DRPO_REQUIRE(d->engine != 1, "%s: runs the fused engine only (engine 0 or 2, not 1)", who);
+  DRPO_REQUIRE(d->H <= PERSIST_MAX_H, "%s: engine 2 supports horizon <= %d", who, PERSIST_MAX_H);
+  DRPO_REQUIRE(!(d->eps_a && d->eps_layout == 0),
+               "%s: recorded draws must be indexed by original row (eps_layout 1), not compacted per step", who);
+  return DRPO_OK;
+}
+
+static int cut_checks(const drpo_rollout_cut_t* cut, const char* who) {
+  DRPO_REQUIRE(cut && cut->scores, "%s: null cut descriptor or scores", who);
+  DRPO_REQUIRE(cut->row_stride != 0 && cut->step_stride != 0, "%s: score strides %lld / %lld must not be zero", who,
+               (long long)cut->row_stride, (long long)cut->step_stride);
+  DRPO_REQUIRE(cut->threshold == cut->threshold, "%s: the threshold is NaN", who);
+  return DRPO_OK;
+}
+
+static void launch_cut(const drpo_rollout_desc_t* d, const RolloutWs& w, const drpo_rollout_cut_t* cut,
+                       hipStream_t stream) {
+  rollout_cut_kernel<<<(d->B + 255) / 256, 256, 0, stream>>>(w.st_dv, cut->scores, cut->row_stride, cut->step_stride,
+                                                             cut->threshold, d->B, d->H, w.newlen, cut->halted_at);
+}
+
+// The horizon kernel alone: the staging, counts and the buffer pointer's copy stay in the
+// workspace for drpo_rollout_emit_cut. Neither the buffer nor its pointer is written.
+DRPO_API int drpo_rollout_stage(const drpo_rollout_desc_t* d, drpo_stream_t stream_) {
+  const char* who = "drpo_rollout_stage";
+  int rpt;
+  int64_t rlen;
+  if (const int rc = rollout_checks(d, who, true, rpt, rlen)) return rc;
+  if (const int rc = halt_engine_checks(d, who)) return rc;
+  RolloutWs w;
+  rollout_ws(d->B, d->S, d->H, reinterpret_cast<uintptr_t>(d->workspace), w);
+  PersistArgs a{};
+  return persist_run(d, w, rpt, rlen, true, who, (hipStream_t)stream_, a);
+}
+
+// Cut + recount over the staging drpo_rollout_stage left, then drpo_rollout's emit tail on
+// the new counts.
+DRPO_API int drpo_rollout_emit_cut(const drpo_rollout_desc_t* d, const drpo_rollout_cut_t* cut, drpo_stream_t stream_) {
+  const char* who = "drpo_rollout_emit_cut";
+  hipStream_t stream = (hipStream_t)stream_;
+  int rpt;
+  int64_t rlen;
+  if (const int rc = rollout_checks(d, who, true, rpt, rlen)) return rc;
+  if (const int rc = halt_engine_checks(d, who)) return rc;
+  if (const int rc = cut_checks(cut, who)) return rc;
+  RolloutWs w;
+  rollout_ws(d->B, d->S, d->H, reinterpret_cast<uintptr_t>(d->workspace), w);
+  // what the emit kernels read of the horizon kernel's arguments
+  PersistArgs a{};
+  a.S = d->S; a.A = d->A; a.C = d->C; a.B = d->B; a.H = d->H;
+  a.ntiles = (d->B + rpt - 1) / rpt;
+  a.st_s = w.st_s; a.st_s2 = w.st_s2; a.st_a = w.st_a; a.st_r = w.st_r; a.st_h = w.st_h; a.st_dv = w.st_dv;
+  a.cnt = w.st_cnt; a.inv = w.st_inv;
+  launch_cut(d, w, cut, stream);
+  DRPO_LAUNCH_CHECK("rollout_cut");
+  const unsigned rg = (unsigned)(((int64_t)d->H * a.ntiles + 3) / 4);
+  auto k = rpt == 32 ? rollout_recount_kernel<32> : rollout_recount_kernel<16>;
+  k<<<rg, 256, 0, stream>>>(a.cnt, a.inv, w.newlen, d->B, d->H, a.ntiles);
+  DRPO_LAUNCH_CHECK("rollout_recount");
+  return emit_tail(d, w, rpt, a, emit_is_self(d->H, d->B, rpt), stream);
+}
+
+// Cut + the trajectory tail over the staging the last drpo_rollout_trajectories* call left.
+DRPO_API int drpo_rollout_trajectories_cut(const drpo_rollout_desc_t* d, const drpo_rollout_cut_t* cut,
+                                           const drpo_rollout_traj_t* out, drpo_stream_t stream_) {
+  const char* who = "drpo_rollout_trajectories_cut";
+  hipStream_t stream = (hipStream_t)stream_;
+  int rpt;
+  int64_t rlen;
+  if (const int rc = rollout_checks(d, who, false, rpt, rlen)) return rc;
+  if (const int rc = halt_engine_checks(d, who)) return rc;
+  if (const int rc = cut_checks(cut, who)) return rc;
+  DRPO_REQUIRE(out && out->len, "%s: null len (the one required output)", who);
+  DRPO_REQUIRE(!out->ret || out->weights, "%s: ret needs weights", who);
+  RolloutWs w;
+  rollout_ws(d->B, d->S, d->H, reinterpret_cast<uintptr_t>(d->workspace), w);
+  launch_cut(d, w, cut, stream);
+  DRPO_LAUNCH_CHECK("rollout_cut");
+  const TrajArgs ta{d->S, d->A, d->C, d->B, d->H, w.st_s, w.st_s2, w.st_a, w.st_r, w.st_h, w.st_dv, *out, w.newlen};
+  rollout_traj_kernel<<<(d->B + TRAJ_ROWS - 1) / TRAJ_ROWS, TRAJ_NT, 0, stream>>>(ta);
+  DRPO_LAUNCH_CHECK("rollout_traj");
+  return DRPO_OK;
 }
 
 __global__ void prp_kernel(int64_t* out, int64_t B, int64_t N, int hb, uint32_t k0, uint32_t k1, uint32_t k2,

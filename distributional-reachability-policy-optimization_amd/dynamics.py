@@ -148,7 +148,7 @@ class BatchedGaussianEnsemble(Configurable, Module):
     def elite_samples(self, states, actions, noise=None):
         return self.engine.elite_samples(states, actions, list(self._elite_inds), noise)
 
-    def disagreement(self, states, actions, members=None, scale=None):
+    def disagreement(self, states, actions, members=None, scale=None, outputs=None):
         """Where the model does not know: how far the members' predictions for each row
         (s, a) are apart (ops.EnsembleSpread), from one all-member forward and one reduction
         launch (drpo_ens_spread); no per-member output is made.
@@ -158,7 +158,9 @@ class BatchedGaussianEnsemble(Configurable, Module):
         scale     column weights of the per-row numbers. None: the model's own normalised
                   state units, 1 / (state_normalizer.std + epsilon) on the state columns and
                   0 on the reward, so they read "in standard deviations of the state". A
-                  tensor [S] (reward weight 0) or [S+1]."""
+                  tensor [S] (reward weight 0) or [S+1].
+        outputs   None: every tensor of EnsembleSpread; else the names to compute (the
+                  others are None), e.g. ('disagreement',)."""
         E, S = self.ensemble_size, self.state_dim
         if members is None:
             members = self.__dict__.get('_elite_inds')
@@ -179,7 +181,7 @@ class BatchedGaussianEnsemble(Configurable, Module):
                 scale = torch.cat([scale, scale.new_zeros(1)])
             if scale.numel() != S + 1:
                 raise ValueError(f'disagreement: scale has {scale.numel()} entries, not {S} or {S + 1}')
-        return self.engine.spread(states, actions, members, scale)
+        return self.engine.spread(states, actions, members, scale, outputs)
 
     def compute_loss(self, states, actions, targets):
         from .ensemble_engine import EnsembleLoss

@@ -248,20 +248,25 @@ class EnsembleEngine:
     # rows per forward + reduction of spread(): bounds the [E, rows, S+1] head-output workspace
     spread_chunk_rows = 65536
 
-    def spread(self, s, a, members, scale):
+    def spread(self, s, a, members, scale, outputs=None):
         """BatchedGaussianEnsemble.disagreement: per chunk of rows one all-member forward on
         shared rows (as elite_samples) and drpo_ens_spread over its raw head outputs. Rows are
         independent, so the chunk size does not change a bit of the result. scale None: the
         model's normalised state units. What the reduction alone needs (outputs, member list,
-        weights) is made after the first forward is under way, not in front of it."""
+        weights) is made after the first forward is under way, not in front of it.
+        outputs: the names of EnsembleSpread.TENSORS to compute (None: all); the others stay None."""
         from .ops import EnsembleSpread
+        outputs = EnsembleSpread.TENSORS if outputs is None else tuple(outputs)
+        if not outputs or set(outputs) - set(EnsembleSpread.TENSORS):
+            raise ValueError(f'spread: outputs {outputs!r} (one or more of {EnsembleSpread.TENSORS})')
         m = self.m
         S, A, E = m.state_dim, m.action_dim, m.ensemble_size
         s, a = self._prep(s.reshape(-1, S), a.reshape(-1, A))
         n, S1 = len(s), S + 1
         if n == 0:
-            return EnsembleSpread(list(members), *(s.new_empty(0, S1) for _ in range(3)),
-                                  *(s.new_empty(0) for _ in range(3)))
+            empty = {k: s.new_empty(*((0, S1) if i < 3 else (0,))) if k in outputs else None
+                     for i, k in enumerate(EnsembleSpread.TENSORS)}
+            return EnsembleSpread(list(members), **empty)
         out = EnsembleSpread(list(members), *[None] * 6)
         d = EnsSpread()
         d.S, d.Z, d.M = S, E, len(out.members)
@@ -271,10 +276,9 @@ class EnsembleEngine:
             c = min(chunk, n - r0)
             nets, _, _ = self._forward(s[r0:r0 + c], a[r0:r0 + c], c, E, 0, 0)
             if r0 == 0:
-                for k in EnsembleSpread.TENSORS[:3]:
-                    setattr(out, k, torch.empty(n, S1, device=self.dev))
-                for k in EnsembleSpread.TENSORS[3:]:
-                    setattr(out, k, torch.empty(n, device=self.dev))
+                for i, k in enumerate(EnsembleSpread.TENSORS):
+                    if k in outputs:
+                        setattr(out, k, torch.empty(*((n, S1) if i < 3 else (n,)), device=self.dev))
                 zsel = self._zsel.get(tuple(out.members))       # device copies of the member lists seen
                 if zsel is None:
                     zsel = self._zsel[tuple(out.members)] = torch.tensor(out.members, dtype=torch.int32,
@@ -285,7 +289,7 @@ class EnsembleEngine:
                 scale = scale.to(self.dev).contiguous().float()
                 d.zsel, d.scale = zsel.data_ptr(), scale.data_ptr()
             d.D, d.LVR, d.s, d.n = nets[1].sy[-1].data_ptr(), nets[2].sy[-1].data_ptr(), s[r0:].data_ptr(), c
-            for k in EnsembleSpread.TENSORS:
+            for k in outputs:
                 setattr(d, k, getattr(out, k)[r0:].data_ptr())
             _lib.check(_lib.lib().drpo_ens_spread(ctypes.byref(d), _lib.stream()), 'ens_spread')
         return out

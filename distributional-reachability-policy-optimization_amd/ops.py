@@ -229,15 +229,70 @@ def _fill_call(d, marr, alg, noise, start, members, eps_a, eps_m, ctr, engine, e
         timer.pairs = 1 if _lib.lib().drpo_rollout_engine(ctypes.byref(d)) == 2 else len(marr)
 
 
-def rollout(alg, policy, initial_states, noise, timer=None, eps_layout=0):
+def _halt_request(alg, noise, halt, buffer, eps_layout=1):
+    """Every refusal of a halt threshold (rollout(halt=), imagine(halt=)), before anything
+    touches a device. buffer: the virtual-buffer path, which halts on the fused engine only.
+    Returns None (off) or the threshold as the kernel compares it, rounded to float32."""
+    if halt is None:
+        return None
+    if isinstance(halt, bool) or not isinstance(halt, (int, float, np.integer, np.floating)):
+        raise ValueError(f'halt: {halt!r} (None or a float threshold on the ensemble\'s disagreement)')
+    thr = float(np.float32(halt))
+    if thr != thr:
+        raise ValueError('halt: the threshold is NaN')
+    if alg.env_params is None:
+        raise ValueError('halt needs the constraint functions on the device: the host round trip of an env without '
+                         'them stages nothing to cut')
+    if not alg.model_ensemble.__dict__.get('_elite_inds'):
+        raise ValueError('halt: the model has no elites before its first fit, so no disagreement to halt on')
+    if buffer and (getattr(alg, 'rollout_engine', 0) == 1 or (noise.parity and eps_layout == 0)):
+        raise ValueError('halt runs the fused engine only: not rollout_engine 1, and not a recorded tape whose draws '
+                         'are indexed by the compacted row of each step (eps_layout 0), which needs it')
+    return thr
+
+
+def _staged_rows(alg, ws_name, B, H):
+    """The fused engine's staged (states [H * B, S], actions [H * B, A]) as views of the
+    workspace ``ws_name`` (step-major, original row; slots of steps a row did not live hold
+    stale floats)."""
+    S, A = alg.state_dim, alg.action_dim
+    L = _lib.lib()
+    ws = alg._workspace(ws_name, L.drpo_rollout_workspace_size(B, S, H))
+    o_s, o_a = ctypes.c_size_t(), ctypes.c_size_t()
+    _lib.check(L.drpo_rollout_staging_offsets(B, S, H, ctypes.byref(o_s), ctypes.byref(o_a)), 'rollout_staging_offsets')
+    n = H * B
+    return (ws[o_s.value:o_s.value + 4 * n * S].view(torch.float32).view(n, S),
+            ws[o_a.value:o_a.value + 4 * n * A].view(torch.float32).view(n, A))
+
+
+def _cut_desc(scores, row_stride, step_stride, thr, B, dev):
+    """drpo_rollout_cut_t over ``scores`` with a fresh halted_at [B]. Returns (descriptor, halted_at)."""
+    from ._abi import RolloutCut
+    cut = RolloutCut()
+    halted_at = torch.empty(B, dtype=torch.int32, device=dev)
+    cut.scores, cut.row_stride, cut.step_stride = scores.data_ptr(), row_stride, step_stride
+    cut.threshold, cut.halted_at = thr, halted_at.data_ptr()
+    return cut, halted_at
+
+
+def rollout(alg, policy, initial_states, noise, timer=None, eps_layout=0, halt=None):
     """One imagined rollout (src/smbpo.py:229-249) into alg.virt_buffer.
 
     Engine (``alg.rollout_engine``, 0 = auto, the library's choice: drpo_rollout_engine):
     2 = fused horizon kernel (default for device noise), 1 = one launch per horizon step
     (used for recorded reference draws, which are indexed by the compacted row of each step). ``eps_layout=1``
     marks a tape whose per-step draws are indexed by the original batch row
-    ([B] rows every step), which drives engine 2 with recorded draws."""
+    ([B] rows every step), which drives engine 2 with recorded draws.
+
+    halt: None, or a float threshold on the elites' disagreement (model.disagreement, the
+    model's normalised state units): a row stops at the first step of its life whose
+    disagreement at (state, action) is not <= halt, and that step and every later one of the
+    row are not written into the buffer (drpo_rollout_stage, one disagreement pass over the
+    H * B staged rows, drpo_rollout_emit_cut). The steps kept are bit-identical to the
+    unhalted call's, no draw is made or moved, nothing syncs; the result carries
+    ``halted_at`` ([B] int32 on the device, -1: not halted). Fused engine only."""
     H, model, vb = alg.horizon, alg.model_ensemble, alg.virt_buffer._module
+    thr = _halt_request(alg, noise, halt, True, eps_layout)
     _lib.require_device(policy.group.data, model.group.data, vb._states, initial_states)
     start = _start_states(alg, initial_states, noise, alg.device)
     B = start[-1]
@@ -248,11 +303,21 @@ def rollout(alg, policy, initial_states, noise, timer=None, eps_layout=0):
     policy.group.ensure_packed()
     model.group.ensure_packed()
     d, marr, count, _ = _rollout_static(alg, policy, B, H, buffer=True)
-    _fill_call(d, marr, alg, noise, start, members, eps_a, eps_m, ctr, getattr(alg, 'rollout_engine', 0), eps_layout,
-               timer)
-    _lib.check(_lib.lib().drpo_rollout(ctypes.byref(d), _lib.stream()), 'rollout')
+    _fill_call(d, marr, alg, noise, start, members, eps_a, eps_m, ctr,
+               getattr(alg, 'rollout_engine', 0) if thr is None else 2, eps_layout, timer)
+    L = _lib.lib()
+    if thr is None:
+        _lib.check(L.drpo_rollout(ctypes.byref(d), _lib.stream()), 'rollout')
+        vb._device_advanced()
+        return _RolloutResult(vb, start_ptr, count, ns)
+    _lib.check(L.drpo_rollout_stage(ctypes.byref(d), _lib.stream()), 'rollout_stage')
+    # never-staged slots hold stale floats: their scores are computed and never read
+    s, a = _staged_rows(alg, f'rollout.{B}.{H}', B, H)
+    scores = model.disagreement(s, a, outputs=('disagreement',)).disagreement
+    cut, halted_at = _cut_desc(scores, 1, B, thr, B, alg.device)
+    _lib.check(L.drpo_rollout_emit_cut(ctypes.byref(d), ctypes.byref(cut), _lib.stream()), 'rollout_emit_cut')
     vb._device_advanced()
-    return _RolloutResult(vb, start_ptr, count, ns)
+    return _RolloutResult(vb, start_ptr, count, ns, halted_at)
 
 
 # the fused engine's horizon limit (DRPO_ROLLOUT_FUSED_MAX_H; read at import, before the
@@ -277,7 +342,7 @@ class ImaginedRollout:
       states [B, H+1, S]         states[i, t] at the start of step t, states[i, lengths[i]] the last next state
       actions [B, H, A], rewards [B, H], constraint_values [B, H, C]
       dones, violations [B, H]   bool
-      lengths [B] int32          steps the row lived, 1..H
+      lengths [B] int32          steps the row lived, 1..H (0..H under imagine(halt=))
       returns [B]                sum_t weights[t] * rewards[i, t] (weights: discount ** t)
       max_constraint [B, C]      max over the row's steps of constraint_values
       first_violation [B] int32  first step with a violation, -1 if none
@@ -300,13 +365,22 @@ class ImaginedRollout:
     With imagine(uncertainty=) four more, None otherwise (EnsembleSpread's per-row numbers
     at (states[i, t], actions[i, t]), in the model's normalised state units):
       disagreement, epistemic, aleatoric [B, H]   zero at and beyond a row's length
-      max_disagreement [B]       the largest disagreement over the row's steps"""
+      max_disagreement [B]       the largest disagreement over the row's steps
+    With imagine(halt=) two more, None otherwise; every tensor above then describes the
+    trajectories as cut (a row halted at step 0 has length 0: states[i, 0] its start state,
+    returns 0, max_constraint -inf, terminated False):
+      halted_at [B] int32        the step whose disagreement was not <= the threshold, where
+                                 the row stops (its new length), -1 if it was not halted
+      halt_threshold             the threshold, as compared (float32)"""
     TENSORS = tuple(s[0] for s in _traj_spec(0, 0, 0, 0, 0))
     # the optional groups: name -> (per-run tensors, which stack stacks; scalars, which it copies)
     GROUPS = {'shield': (('interventions', 'certificate'), ('shield_threshold',)),
               'linear': (('blend',), ('shield_candidates',)),
               'uncertainty': (('disagreement', 'epistemic', 'aleatoric', 'max_disagreement'), ())}
-    _UNSET = dict.fromkeys(k for per_run, scalars in GROUPS.values() for k in per_run + scalars)
+    # the group of the post-pass that rewrites the core tensors (imagine(halt=)); set and stacked like GROUPS
+    HALT_GROUP = {'halt': (('halted_at',), ('halt_threshold',))}
+    _ALL_GROUPS = dict(GROUPS, **HALT_GROUP)
+    _UNSET = dict.fromkeys(k for per_run, scalars in _ALL_GROUPS.values() for k in per_run + scalars)
 
     def __init__(self, members, given_steps=0, **tensors):
         assert set(tensors) == set(self.TENSORS)
@@ -316,7 +390,7 @@ class ImaginedRollout:
 
     def set_group(self, group, **values):
         """Set every attribute of one optional group."""
-        per_run, scalars = self.GROUPS[group]
+        per_run, scalars = self._ALL_GROUPS[group]
         assert set(values) == set(per_run + scalars), (group, sorted(values))
         self.__dict__.update(values)
 
@@ -338,7 +412,7 @@ class ImaginedRollout:
     def stack(cls, runs):
         out = cls([r.members for r in runs], runs[0].given_steps,
                   **{k: torch.stack([getattr(r, k) for r in runs]) for k in cls.TENSORS})
-        for group, (per_run, scalars) in cls.GROUPS.items():
+        for group, (per_run, scalars) in cls._ALL_GROUPS.items():
             if getattr(runs[0], per_run[0]) is not None:
                 out.set_group(group, **{k: torch.stack([getattr(r, k) for r in runs]) for k in per_run},
                               **{k: getattr(runs[0], k) for k in scalars})
@@ -555,6 +629,7 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
     spec = _traj_spec(B, H, S, A, C)
     res = _traj_outputs(out, spec, dev)
     im = ImaginedRollout(mem, K, **res)
+    im._weights = w     # (kept for _cut_trajectories, which sums the returns again)
 
     # descriptors
     policy.group.ensure_packed()
@@ -586,6 +661,43 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
     # launch
     launch = getattr(_lib.lib(), 'drpo_' + entry)
     _lib.check(launch(ctypes.byref(d), *map(ctypes.byref, extra), ctypes.byref(t), _lib.stream()), entry)
+    return im
+
+
+def _cut_trajectories(alg, policy, im, scores, thr):
+    """Cuts the trajectories of ``im`` in place where ``scores`` [B, H] (float32, on the device,
+    any non-zero strides) is not <= ``thr`` within a row's life (drpo_rollout_trajectories_cut;
+    imagine(halt=) passes im.disagreement): rewrites the core tensors from the staging, masks
+    the optional groups with the new lengths and sets the group 'halt'. Valid only directly
+    after the rollout_trajectories call that made ``im`` (a single run: under members='each'
+    each run before the next), whose staging it reads."""
+    from ._abi import RolloutTraj
+    B, H = im.rewards.shape
+    S, A, C = alg.state_dim, alg.action_dim, alg.con_dim
+    _lib.require_device(scores)
+    if scores.dtype != torch.float32 or tuple(scores.shape) != (B, H):
+        raise ValueError(f'scores: float32 [{B}, {H}], not {scores.dtype} {tuple(scores.shape)}')
+    if 0 in scores.stride():
+        scores = scores.contiguous()
+    thr = float(np.float32(thr))
+    d, _, _, _ = _rollout_static(alg, policy, B, H, buffer=False)
+    t = RolloutTraj()
+    for name, _, _, field in _traj_spec(B, H, S, A, C):
+        setattr(t, field, getattr(im, name).data_ptr())
+    t.weights = im._weights.data_ptr()
+    cut, halted_at = _cut_desc(scores, scores.stride(0), scores.stride(1), thr, B, alg.device)
+    _lib.check(_lib.lib().drpo_rollout_trajectories_cut(ctypes.byref(d), ctypes.byref(cut), ctypes.byref(t),
+                                                        _lib.stream()), 'rollout_trajectories_cut')
+    # the optional groups' [B, H] tensors: zero at and beyond the new lengths
+    mask = im.mask
+    for group in ('shield', 'linear', 'uncertainty'):
+        for k in ImaginedRollout.GROUPS[group][0]:
+            v = getattr(im, k)
+            if v is not None and v.shape == mask.shape:
+                setattr(im, k, torch.where(mask, v, torch.zeros_like(v)))
+    if im.disagreement is not None:
+        im.max_disagreement = im.disagreement.max(dim=-1).values
+    im.set_group('halt', halted_at=halted_at, halt_threshold=thr)
     return im
 
 
@@ -635,8 +747,9 @@ def rollout_host_env(alg, policy, initial_states, noise):
 
 
 class _RolloutResult:
-    def __init__(self, vb, start_ptr, count, tape_counts=None):
+    def __init__(self, vb, start_ptr, count, tape_counts=None, halted_at=None):
         self.vb, self._start, self._count, self.tape_counts = vb, start_ptr, count, tape_counts
+        self.halted_at = halted_at     # rollout(halt=): device int32 [B], the step each row halted at, -1 if none
 
     def __len__(self):
         return int(self._count.item())

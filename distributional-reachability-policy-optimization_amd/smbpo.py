@@ -25,7 +25,7 @@ import torch
 
 from .buffers import ConstraintSafetySampleBuffer, DummyModuleWrapper
 from .checkpoint import CheckpointableData
-from .config import BaseConfig, Configurable
+from .config import BaseConfig, Configurable, Optional
 from .distributed import GradReducer
 from .dynamics import BatchedGaussianEnsemble
 from .envs import ProductEnv, device_env_params, env_dims, get_max_episode_steps  # noqa: F401
@@ -72,6 +72,8 @@ class SMBPO(Configurable, Module):
         safe_shield_threshold = -0.1
         eval_shield_threshold = -0.05
         eval_shield_type = "linear"
+        # rollout(halt=)'s default: rows stop where the elites' disagreement exceeds it; unset: off
+        rollout_halt_threshold = Optional(float)
 
     def __init__(self, config, env_factory, data=None, epochs=1, device=default_device, noise_seed=None):
         Configurable.__init__(self, config)
@@ -242,20 +244,28 @@ class SMBPO(Configurable, Module):
             yield t
 
     # ------------------------------------------------------------------ hot path
-    def rollout(self, policy, initial_states=None, noise=None, timer=None):
+    _CONFIG = object()    # rollout(halt=)'s default: the config's rollout_halt_threshold
+
+    def rollout(self, policy, initial_states=None, noise=None, timer=None, halt=_CONFIG):
         """src/smbpo.py:229-249 as one fused kernel for the whole horizon (device
-        constraint fns), or per-step launches around the env's host fns otherwise."""
+        constraint fns), or per-step launches around the env's host fns otherwise.
+        halt: None: off; a float: rows stop where the elites' disagreement is not <= it
+        (ops.rollout); default: the config's rollout_halt_threshold (unset: off)."""
         from . import ops
         noise = self.noise if noise is None else noise
+        if halt is self._CONFIG:
+            halt = self.rollout_halt_threshold
+            halt = None if isinstance(halt, Optional) else halt
         if self.env_params is None:
+            ops._halt_request(self, noise, halt, True)    # (refuses any threshold: nothing is staged)
             return ops.rollout_host_env(self, policy, initial_states, noise)
-        return ops.rollout(self, policy, initial_states, noise, timer)
+        return ops.rollout(self, policy, initial_states, noise, timer, halt=halt)
 
     IMAGINE_SALT = 0x1A6E
 
     def imagine(self, states=None, policy=None, horizon=None, *, members=None, deterministic=False,
                 model_noise=True, discount=None, noise=None, actions=None, shield=None,
-                shield_uncertainty=None, uncertainty=None):
+                shield_uncertainty=None, uncertainty=None, halt=None):
         """What the model predicts happens from ``states`` under ``policy``: the rollout of
         src/smbpo.py:229-249 kept per trajectory (ops.ImaginedRollout: row i of every tensor
         is the trajectory from start state i), on the fused horizon kernel. Nothing of the
@@ -316,7 +326,17 @@ class SMBPO(Configurable, Module):
                    ``epistemic``, ``aleatoric`` and ``max_disagreement``, and
                    first_uncertain(threshold) reads them. 'all': over every member. A
                    post-pass: it works with every other argument, makes no draw, moves no
-                   counter and changes no other tensor of the result."""
+                   counter and changes no other tensor of the result.
+        halt       None: nothing more. A float: the trajectories as rollout(halt=) keeps them.
+                   A row stops at the first step of its life whose disagreement (over the
+                   elites; over every member with uncertainty='all') is not <= halt: that
+                   step and the later ones do not exist, ``lengths`` is 0..H, and every
+                   tensor is rewritten for the new lengths (drpo_rollout_trajectories_cut on
+                   the staged horizon; the optional groups are masked). Implies
+                   uncertainty=True. The result carries ``halted_at`` and
+                   ``halt_threshold``. A post-pass like uncertainty=: every step kept is
+                   bit-identical to the unhalted call's, and no draw or counter moves. Under
+                   members='each' each run is cut on its own."""
         from . import ops
         from .rng import _mix64
         if self.env_params is None:
@@ -326,6 +346,9 @@ class SMBPO(Configurable, Module):
         H = self.horizon if horizon is None else int(horizon)   # (its range: checked by ops)
         if not (uncertainty is None or isinstance(uncertainty, bool) or uncertainty == 'all'):
             raise ValueError(f"uncertainty: {uncertainty!r} (None, True or 'all')")
+        halt_thr = ops._halt_request(self, noise, halt, False)
+        if halt_thr is not None and not uncertainty:
+            uncertainty = True
         policy = self.actor if policy is None else policy
         if noise is None:
             if self.__dict__.get('_imagine_noise') is None:
@@ -372,12 +395,16 @@ class SMBPO(Configurable, Module):
             kw.update(eps_a=draws(not deterministic, A), eps_m=draws(model_noise, S1), eps_layout=1)
 
         def run(m):
-            return ops.rollout_trajectories(self, policy, states, noise, members=m, weights=weights, horizon=H, **kw)
+            im = ops.rollout_trajectories(self, policy, states, noise, members=m, weights=weights, horizon=H, **kw)
+            if halt_thr is not None:     # while the run's staging is still in the workspace
+                self._imagined_uncertainty(im, None if uncertainty is True else 'all')
+                ops._cut_trajectories(self, policy, im, im.disagreement, halt_thr)
+            return im
         if each:
             im = ops.ImaginedRollout.stack([run(int(m)) for m in self.model_ensemble._elite_inds])
         else:
             im = run(members)
-        if uncertainty:
+        if uncertainty and halt_thr is None:
             self._imagined_uncertainty(im, None if uncertainty is True else 'all')
         return im
 

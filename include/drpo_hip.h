@@ -275,6 +275,63 @@ int drpo_rollout_trajectories_linear(const drpo_rollout_desc_t* d /* host */,
                                      const drpo_rollout_linear_t* linear /* host; NULL: the threshold shield */,
                                      const drpo_rollout_traj_t* out /* host */, drpo_stream_t stream);
 
+/* Halting the imagined rollout (src/smbpo.py:229-249) where a per-step score says the
+ * model should not be trusted. The reference has a fixed horizon and no counterpart. With
+ * score[i][t] = scores[i * row_stride + t * step_stride] and len_i the row's natural length:
+ * c_i is the first t < len_i with !(score[i][t] <= threshold), so a NaN score halts and a
+ * score equal to the threshold does not; halted_at[i] = c_i, or -1 if there is none; a
+ * halted row's length becomes c_i (0 is allowed: the row contributes nothing). Steps
+ * t >= c_i do not exist; step c_i - 1 stays as staged: its done bit is 0 and its next
+ * state is the state the row halted at. Scores at or beyond len_i are never read.
+ * A post-pass on the staged horizon: no draw is made, no counter moves, and every step a
+ * halted and an unhalted run share is bit-identical.
+ * Contract: the two _cut entry points read the staging that the last drpo_rollout_stage /
+ * drpo_rollout_trajectories* call left in d->workspace; `d` must have that call's shapes
+ * (B, S, A, C, H) and rows_per_tile. Tile counts and in-tile indices read back from the
+ * workspace are clamped to the tile, so a caller that breaks this gets wrong rows, never
+ * an access outside the workspace or the buffer.
+ * DRPO_EINVAL before any launch: a null cut or scores, a zero stride, a NaN threshold,
+ * engine 1, H above DRPO_ROLLOUT_FUSED_MAX_H, and whatever drpo_rollout refuses. */
+typedef struct {
+  const float* scores;   /* device; [H][B] staging order (row_stride 1, step_stride B), [B][H] trajectory order
+                            (row_stride H, step_stride 1) or any other strided layout; not written while a call runs */
+  int64_t row_stride;    /* in elements, != 0 */
+  int64_t step_stride;   /* in elements, != 0 */
+  float threshold;       /* not NaN; +inf halts NaN scores only, -inf every row at step 0 */
+  int32_t* halted_at;    /* device [B] or NULL */
+} drpo_rollout_cut_t;
+
+/* The first half of drpo_rollout (src/smbpo.py:229-249): its checks and the fused
+ * engine's horizon kernel (engine 1 is refused), which stages every row's steps in the
+ * workspace and copies the buffer pointer there. Nothing is emitted: neither the virtual
+ * buffer nor *vptr is written. Records the event pair of drpo_rollout's engine 2. */
+int drpo_rollout_stage(const drpo_rollout_desc_t* d /* host */, drpo_stream_t stream);
+
+/* The second half of drpo_rollout (src/smbpo.py:229-249) under a cut: shortens the staged
+ * rows (one launch for the cut, one that filters each (step, tile) list of alive rows,
+ * order kept) and runs the emit tail drpo_rollout would have run, chosen by the same
+ * rule. off[H] (drpo_rollout_count_offset) and *vptr advance by the rows actually
+ * emitted, which keep the reference's order. */
+int drpo_rollout_emit_cut(const drpo_rollout_desc_t* d /* host */, const drpo_rollout_cut_t* cut /* host */,
+                          drpo_stream_t stream);
+
+/* The trajectory tail (src/smbpo.py:229-249 per trajectory) again under a cut, on the
+ * staging of the preceding drpo_rollout_trajectories* call in any of its four forms:
+ * rewrites every output given as drpo_rollout_trajectories defines it with len[i] the new
+ * length, 0..H. A halted row's terminated is 0 and its first_violation -1 unless it lies
+ * before the cut; ret sums the kept steps in the same double order. A row of length 0:
+ * states[i][0] the start state, every other element zero, ret 0, hmax -inf (the
+ * identity of max). The shield's outputs are not this call's: the caller masks them. */
+int drpo_rollout_trajectories_cut(const drpo_rollout_desc_t* d /* host */, const drpo_rollout_cut_t* cut /* host */,
+                                  const drpo_rollout_traj_t* out /* host */, drpo_stream_t stream);
+
+/* Host only: the byte offsets in the workspace of the fused engine's staged states
+ * ([H][B][S] float32) and actions ([H][B][A] float32) of the rollout (src/smbpo.py:229-249),
+ * step-major and indexed by original row; the step of a row is staged iff the row was
+ * alive at it, every other slot holds whatever was there. For viewing the staged
+ * (state, action) rows without a copy. DRPO_EINVAL for a non-positive shape or a null output. */
+int drpo_rollout_staging_offsets(int B, int S, int H, size_t* st_s /* host */, size_t* st_a /* host */);
+
 /* batched env constraint functions, e.g. PointRobot.get_constraint_values /
  * check_violation / check_done (src/env/point_robot.py:96-131); h is [n][C] */
 int drpo_env_constraints(int env_id, int tracking_surr_start, int tracking_n_surr, double env_thr0,
