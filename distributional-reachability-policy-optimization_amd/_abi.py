@@ -63,6 +63,16 @@ class RolloutCut(ctypes.Structure):
                 ('halted_at', P)]
 
 
+class RolloutLookahead(ctypes.Structure):
+    """drpo_rollout_lookahead_t"""
+    _fields_ = [('B', c_int), ('H', c_int), ('C', c_int), ('mode', c_int), ('gamma', c_double),
+                ('reward_scale', c_double), ('alive_bonus', c_double), ('constraint_scale', c_double),
+                ('constraint_offset', c_double),
+                ('rewards', P), ('constraint_values', P), ('dones', P), ('violations', P), ('lengths', P),
+                ('terminated', P), ('weights', P), ('step_q', P), ('step_qc', P), ('terminal_q', P),
+                ('terminal_qc', P), ('value', P), ('certificate', P)]
+
+
 ENV_PROGRAM = 4          # DRPO_ENV_PROGRAM
 PROG_AFFINE, PROG_BALLS = 0, 1
 PROG_MAX_ROWS = PROG_MAX_TERMS = PROG_MAX_CENTRES = PROG_MAX_BOX = 8
@@ -143,6 +153,7 @@ PROTOTYPES = {
     'drpo_rollout_emit_cut': (c_int, [POINTER(RolloutDesc), POINTER(RolloutCut), P]),
     'drpo_rollout_trajectories_cut': (c_int, [POINTER(RolloutDesc), POINTER(RolloutCut), POINTER(RolloutTraj), P]),
     'drpo_rollout_staging_offsets': (c_int, [c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
+    'drpo_rollout_lookahead': (c_int, [POINTER(RolloutLookahead), P]),
     'drpo_env_constraints': (c_int, [c_int, c_int, c_int, c_double, c_double, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_constraints_program': (c_int, [P, c_int, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_program_check': (c_int, [POINTER(EnvProgram), c_int]),

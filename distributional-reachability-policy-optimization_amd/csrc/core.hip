@@ -19,7 +19,7 @@ void drpo_set_error(const char* fmt, ...) {
 
 DRPO_API const char* drpo_last_error(void) { return g_err; }
 
-DRPO_API int drpo_version(void) { return 11; }
+DRPO_API int drpo_version(void) { return 12; }
 
 // HIP event helpers so hosts without a HIP binding (ctypes/cgo/JNI) can time
 // individual kernels on the stream they run on. The events are timing-only: created
@@ -82,7 +82,7 @@ DRPO_API int64_t drpo_abi_sizeof(const char* name) {
       {"drpo_env_program_row_t", sizeof(drpo_env_program_row_t)}, {"drpo_rollout_traj_t", sizeof(drpo_rollout_traj_t)},
       {"drpo_rollout_given_t", sizeof(drpo_rollout_given_t)}, {"drpo_rollout_shield_t", sizeof(drpo_rollout_shield_t)},
       {"drpo_rollout_linear_t", sizeof(drpo_rollout_linear_t)}, {"drpo_ens_spread_t", sizeof(drpo_ens_spread_t)},
-      {"drpo_rollout_cut_t", sizeof(drpo_rollout_cut_t)},
+      {"drpo_rollout_cut_t", sizeof(drpo_rollout_cut_t)},     {"drpo_rollout_lookahead_t", sizeof(drpo_rollout_lookahead_t)},
   };
   for (const E& e : table)
     if (strcmp(e.n, name) == 0) return (int64_t)e.s;

@@ -371,7 +371,22 @@ class ImaginedRollout:
     returns 0, max_constraint -inf, terminated False):
       halted_at [B] int32        the step whose disagreement was not <= the threshold, where
                                  the row stops (its new length), -1 if it was not halted
-      halt_threshold             the threshold, as compared (float32)"""
+      halt_threshold             the threshold, as compared (float32)
+    With imagine(lookahead=) seven more, None otherwise (C: the constraint critic's outputs,
+    con_dim, or 1 for a 'cost' solver; drpo_rollout_lookahead has the definition):
+      step_q [B, H]              min over solver.critic's nets at (states[i, t], actions[i, t]); 0 at
+                                 and beyond the length
+      step_qc [B, H, C]          solver.constraint_critic (its mean or its bound) at the same rows,
+                                 always with the C axis; 0 at and beyond the length
+      terminal_q [B]             min Q at (states[i, lengths[i]], the policy's mean action there); 0
+                                 for terminated rows
+      terminal_qc [B, C]         Qc at (states[i, lengths[i]], actor_safe's mean action there); 0 for
+                                 terminated rows
+      value_lookahead [B, H+1]   entry k: sum_{t<k} discount^t r'_t + discount^k min Q after k steps,
+                                 in the critics' reward units; entries beyond the length repeat
+      certificate_lookahead [B, H+1, C]   entry k: the constraint critic's backup unrolled k steps
+                                 along the trajectory, closed with Qc
+      lookahead_kind             'mean' or 'bound'"""
     TENSORS = tuple(s[0] for s in _traj_spec(0, 0, 0, 0, 0))
     # the optional groups: name -> (per-run tensors, which stack stacks; scalars, which it copies)
     GROUPS = {'shield': (('interventions', 'certificate'), ('shield_threshold',)),
@@ -379,7 +394,10 @@ class ImaginedRollout:
               'uncertainty': (('disagreement', 'epistemic', 'aleatoric', 'max_disagreement'), ())}
     # the group of the post-pass that rewrites the core tensors (imagine(halt=)); set and stacked like GROUPS
     HALT_GROUP = {'halt': (('halted_at',), ('halt_threshold',))}
-    _ALL_GROUPS = dict(GROUPS, **HALT_GROUP)
+    # the group of the critics' post-pass (imagine(lookahead=)), which runs after the cut; set and stacked alike
+    LOOKAHEAD_GROUP = {'lookahead': (('step_q', 'step_qc', 'terminal_q', 'terminal_qc', 'value_lookahead',
+                                      'certificate_lookahead'), ('lookahead_kind',))}
+    _ALL_GROUPS = dict(GROUPS, **HALT_GROUP, **LOOKAHEAD_GROUP)
     _UNSET = dict.fromkeys(k for per_run, scalars in _ALL_GROUPS.values() for k in per_run + scalars)
 
     def __init__(self, members, given_steps=0, **tensors):
@@ -698,6 +716,91 @@ def _cut_trajectories(alg, policy, im, scores, thr):
     if im.disagreement is not None:
         im.max_disagreement = im.disagreement.max(dim=-1).values
     im.set_group('halt', halted_at=halted_at, halt_threshold=thr)
+    return im
+
+
+_NO_DRAW = None     # the noise object of lookahead's drpo_cc_dist call, which draws nothing
+
+
+def _lookahead_request(alg, lookahead):
+    """imagine(lookahead=) checked: None (off), 'mean' or 'bound'."""
+    if lookahead is None or lookahead is False:
+        return None
+    if lookahead is True:
+        return 'mean'
+    if isinstance(lookahead, str) and lookahead == 'bound':
+        if not alg.solver.distributional_qc:
+            raise ValueError("lookahead='bound' needs a distributional constraint critic (solver.distributional_qc)")
+        return 'bound'
+    raise ValueError(f"lookahead: {lookahead!r} (None, True or 'bound')")
+
+
+def lookahead(alg, policy, im, kind, gamma, *, reward_scale=None, alive_bonus=None, constraint_scale=None,
+              constraint_offset=None):
+    """What the two critics say along and at the end of the imagined trajectories ``im`` (one
+    run, cut or not): fills the group 'lookahead' (imagine(lookahead=)). The stand-alone
+    forwards of solver.critic (min over its nets) and solver.constraint_critic (kind 'mean': its
+    mean, 'bound': mean + std_ratio * std) at every (states[i, t], actions[i, t]) and at the
+    state a row ends in (under ``policy``'s and actor_safe's mean action), masked to zero
+    beyond the lengths and for terminated rows; then one drpo_rollout_lookahead launch for the
+    k-step expansions, k = 0..H. Dead rows are evaluated and masked, not compacted. Makes no
+    draw and moves no counter. gamma: the discount; the four scales (src/smbpo.py:260-270)
+    default to the trainer's config."""
+    from ._abi import RolloutLookahead
+    global _NO_DRAW
+    assert kind in ('mean', 'bound'), kind
+    sol, cc = alg.solver, alg.solver.constraint_critic
+    B, H = im.rewards.shape
+    S, A, C = alg.state_dim, alg.action_dim, cc.output_dim
+    dev = im.rewards.device
+    _lib.require_device(im.rewards, im.states, im.actions)
+    cfg = {'reward_scale': reward_scale, 'alive_bonus': alive_bonus, 'constraint_scale': constraint_scale,
+           'constraint_offset': constraint_offset}
+    cfg = {k: float(getattr(alg, k) if v is None else v) for k, v in cfg.items()}
+    if kind == 'bound' and _NO_DRAW is None:
+        from .rng import DeviceNoise
+        _NO_DRAW = DeviceNoise(0, rank=0, world=1)
+
+    def qc(s, a):
+        q = constraint_critic_forward(cc, s, a, uncertainty=kind == 'bound', noise=_NO_DRAW)
+        return q.reshape(-1, C)
+
+    def qmin(s, a):
+        qs = critic_all(sol.critic, s, a)
+        q = qs[0]
+        for other in qs[1:]:
+            q = torch.min(q, other)
+        return q
+
+    mask = im.mask
+    s, a = im.states[:, :-1].reshape(B * H, S), im.actions.reshape(B * H, A)
+    zero = torch.zeros((), device=dev)
+    step_q = torch.where(mask, qmin(s, a).reshape(B, H), zero)
+    step_qc = torch.where(mask.unsqueeze(-1), qc(s, a).reshape(B, H, C), zero)
+    # the state a row ends in: states[i, lengths[i]]
+    at = im.lengths.clamp(0, H).to(torch.int64).reshape(B, 1, 1).expand(B, 1, S)
+    last = torch.gather(im.states, 1, at).reshape(B, S)
+    alive = ~im.terminated.view(torch.bool)
+    terminal_q = torch.where(alive, qmin(last, policy.act(last, eval=True)).reshape(B), zero)
+    terminal_qc = torch.where(alive.unsqueeze(-1), qc(last, alg.actor_safe.act(last, eval=True)), zero)
+
+    w = torch.as_tensor(np.power(np.float64(gamma), np.arange(H + 1, dtype=np.float64))).to(dev)
+    value = torch.empty(B, H + 1, device=dev)
+    cert = torch.empty(B, H + 1, C, device=dev)
+    keep = [t.contiguous() for t in (im.rewards, im.constraint_values, im.dones, im.violations, im.lengths,
+                                     im.terminated, step_q, step_qc, terminal_q, terminal_qc)]
+    d = RolloutLookahead()
+    d.B, d.H, d.C, d.mode, d.gamma = B, H, C, 0 if sol.constrained_fcn == 'reachability' else 1, float(gamma)
+    for k, v in cfg.items():
+        setattr(d, k, v)
+    if d.mode == 0:
+        assert tuple(im.constraint_values.shape) == (B, H, C), 'constraint_values: one column per critic output'
+    (d.rewards, d.constraint_values, d.dones, d.violations, d.lengths, d.terminated, d.step_q, d.step_qc,
+     d.terminal_q, d.terminal_qc) = (t.data_ptr() for t in keep)
+    d.weights, d.value, d.certificate = w.data_ptr(), value.data_ptr(), cert.data_ptr()
+    _lib.check(_lib.lib().drpo_rollout_lookahead(ctypes.byref(d), _lib.stream()), 'rollout_lookahead')
+    im.set_group('lookahead', step_q=step_q, step_qc=step_qc, terminal_q=terminal_q, terminal_qc=terminal_qc,
+                 value_lookahead=value, certificate_lookahead=cert, lookahead_kind=kind)
     return im
 
 

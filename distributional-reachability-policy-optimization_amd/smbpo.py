@@ -265,7 +265,7 @@ class SMBPO(Configurable, Module):
 
     def imagine(self, states=None, policy=None, horizon=None, *, members=None, deterministic=False,
                 model_noise=True, discount=None, noise=None, actions=None, shield=None,
-                shield_uncertainty=None, uncertainty=None, halt=None):
+                shield_uncertainty=None, uncertainty=None, halt=None, lookahead=None):
         """What the model predicts happens from ``states`` under ``policy``: the rollout of
         src/smbpo.py:229-249 kept per trajectory (ops.ImaginedRollout: row i of every tensor
         is the trajectory from start state i), on the fused horizon kernel. Nothing of the
@@ -336,7 +336,28 @@ class SMBPO(Configurable, Module):
                    uncertainty=True. The result carries ``halted_at`` and
                    ``halt_threshold``. A post-pass like uncertainty=: every step kept is
                    bit-identical to the unhalted call's, and no draw or counter moves. Under
-                   members='each' each run is cut on its own."""
+                   members='each' each run is cut on its own.
+        lookahead  None / False: nothing more. True: what the two critics say about the
+                   trajectories, which otherwise end at the horizon: ``step_q`` / ``step_qc``
+                   (min over solver.critic's nets and solver.constraint_critic's mean at every
+                   (states[i, t], actions[i, t])), ``terminal_q`` / ``terminal_qc`` (at the state a
+                   row ends in, under the policy's and under actor_safe's mean action), and for
+                   every k = 0..H ``value_lookahead[:, k]``, the k-step value expansion
+                   sum_{t<k} discount^t r_t + discount^k min Q(s_k, a_k), and
+                   ``certificate_lookahead[:, k]``, the constraint critic's own backup
+                   (src/ssac.py:284-294) unrolled k steps and closed with Qc: "k steps of this
+                   controller, then the safe actor: still certified?". Both in the critics'
+                   training units (reward_scale, alive_bonus, constraint_scale and
+                   constraint_offset applied, src/smbpo.py:260-270), with ``discount``.
+                   [:, k] - [:, 0] is the k-step TD residual of the critic against the model;
+                   value_lookahead[:, H] under actions= is the planning score with a terminal
+                   value. 'bound': with the constraint critic's distributional bound mean +
+                   std_ratio * std, what the shield compares (needs a distributional critic).
+                   The result carries ``lookahead_kind`` ('mean' or 'bound'). A post-pass like
+                   uncertainty= (ops.lookahead, drpo_rollout_lookahead): it works with every
+                   other argument, runs after the cut of halt= on the cut trajectories, makes no
+                   draw, moves no counter and changes no other tensor of the result. Anything
+                   else is a ValueError."""
         from . import ops
         from .rng import _mix64
         if self.env_params is None:
@@ -347,6 +368,7 @@ class SMBPO(Configurable, Module):
         if not (uncertainty is None or isinstance(uncertainty, bool) or uncertainty == 'all'):
             raise ValueError(f"uncertainty: {uncertainty!r} (None, True or 'all')")
         halt_thr = ops._halt_request(self, noise, halt, False)
+        look = ops._lookahead_request(self, lookahead)
         if halt_thr is not None and not uncertainty:
             uncertainty = True
         policy = self.actor if policy is None else policy
@@ -399,6 +421,8 @@ class SMBPO(Configurable, Module):
             if halt_thr is not None:     # while the run's staging is still in the workspace
                 self._imagined_uncertainty(im, None if uncertainty is True else 'all')
                 ops._cut_trajectories(self, policy, im, im.disagreement, halt_thr)
+            if look is not None:
+                ops.lookahead(self, policy, im, look, gamma)
             return im
         if each:
             im = ops.ImaginedRollout.stack([run(int(m)) for m in self.model_ensemble._elite_inds])

@@ -332,6 +332,61 @@ int drpo_rollout_trajectories_cut(const drpo_rollout_desc_t* d /* host */, const
  * (state, action) rows without a copy. DRPO_EINVAL for a non-positive shape or a null output. */
 int drpo_rollout_staging_offsets(int B, int S, int H, size_t* st_s /* host */, size_t* st_a /* host */);
 
+/* Model-based lookahead of the two critics along imagined trajectories: for every row and
+ * every k = 0..H, the k-step value expansion sum_{t<k} gamma^t r_t + gamma^k min Q(s_k, a_k)
+ * and the constraint critic's own backup (compute_cons_target, src/ssac.py:284-294, inside
+ * the critic loss src/ssac.py:304-413) unrolled k steps along the trajectory and closed with
+ * Qc(s_k, a_k). The reference has one-step targets only and no counterpart. A post-pass on the
+ * trajectory-major tensors of drpo_rollout_trajectories* (after a cut as well): it needs no
+ * workspace and no staging, makes no draw and writes nothing but its two outputs. The critics'
+ * values are inputs: the caller evaluates them with the stand-alone forwards.
+ * With len_i = lengths[i] clamped to 0..H, term_i = terminated[i], w = weights, g = gamma, and
+ * the critics' training units (src/smbpo.py:260-270), formed in double from the float32 inputs:
+ *   r'_t = rewards[i][t] (* reward_scale if reward_scale != 0) (+ alive_bonus if alive_bonus != 0)
+ *   h'_t = constraint_values[i][t][c] * constraint_scale;  h'_t += (h'_t > 0 ? 1 : 0) * constraint_offset
+ * entry k of row i, with kk = min(k, len_i) (entries beyond a row's length repeat the one at it):
+ *   bootstrap  kk < len_i: q = step_q[i][kk], x = step_qc[i][kk][c];
+ *              kk == len_i and !term_i: q = terminal_q[i], x = terminal_qc[i][c];
+ *              kk == len_i and term_i: none (the scan below starts from x = 0.0, which the done
+ *              select of the row's last step replaces; terminal_q / terminal_qc are not used)
+ *   value[i][k]  acc = 0.0; acc += w[t] * r'_t for t = 0 .. kk-1 in that order; + w[kk] * q if
+ *              there is a bootstrap
+ *   certificate[i][k][c]  from x, for t = kk-1 down to 0:
+ *              mode 0 (reachability): x = dones[i][t] ? h'_t : (1 - g) * h'_t + g * max(h'_t, x),
+ *                a NaN in either operand of the max stays (torch.maximum);
+ *              mode 1 (cost): x = dones[i][t] ? v_t : v_t + g * x, v_t = violations[i][t] as 0 / 1
+ *              (the same for every c); the done branch is a select, never a product with zero
+ * Every operation is one double add or multiply, round to nearest, nothing contracted, in the
+ * order written; the result is rounded to float32 once and a NaN stored as 0x7FC00000. A row of
+ * length 0 has every entry equal to its bootstrap (w[0] * terminal_q; terminal_qc).
+ * Every element of every given output is written. DRPO_EINVAL before any launch: a null
+ * descriptor or input pointer (violations may be NULL in mode 0), H outside
+ * 1..DRPO_ROLLOUT_FUSED_MAX_H, C < 1, a mode other than 0 / 1, gamma not finite or outside
+ * [0, 1], B < 0, or a B beyond one grid (2^24 rows at the longest horizons, where a workgroup
+ * takes one row). B == 0: DRPO_OK without a launch. */
+typedef struct {
+  int B, H, C, mode;            /* rows, horizon, critic outputs; mode 0 reachability, 1 cost */
+  double gamma;
+  double reward_scale, alive_bonus, constraint_scale, constraint_offset;
+  /* inputs, device, not written while the call runs */
+  const float* rewards;            /* [B][H] */
+  const float* constraint_values;  /* [B][H][C]; required, though mode 1 does not read it */
+  const uint8_t* dones;            /* [B][H] */
+  const uint8_t* violations;       /* [B][H]; read in mode 1 only, may be NULL in mode 0 */
+  const int32_t* lengths;          /* [B]; clamped to 0..H as read */
+  const uint8_t* terminated;       /* [B] */
+  const double* weights;           /* [H + 1]: gamma^k */
+  const float* step_q;             /* [B][H]: min Q at (states[i][t], actions[i][t]) */
+  const float* step_qc;            /* [B][H][C]: Qc at the same rows */
+  const float* terminal_q;         /* [B]: min Q at (states[i][len_i], the policy's mean action there) */
+  const float* terminal_qc;        /* [B][C]: Qc at (states[i][len_i], the safe actor's mean action there) */
+  /* outputs, device; either may be NULL */
+  float* value;                    /* [B][H + 1] */
+  float* certificate;              /* [B][H + 1][C] */
+} drpo_rollout_lookahead_t;
+
+int drpo_rollout_lookahead(const drpo_rollout_lookahead_t* d /* host */, drpo_stream_t stream);
+
 /* batched env constraint functions, e.g. PointRobot.get_constraint_values /
  * check_violation / check_done (src/env/point_robot.py:96-131); h is [n][C] */
 int drpo_env_constraints(int env_id, int tracking_surr_start, int tracking_n_surr, double env_thr0,
