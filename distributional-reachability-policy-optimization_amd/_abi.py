@@ -73,6 +73,32 @@ class RolloutLookahead(ctypes.Structure):
                 ('terminal_qc', P), ('value', P), ('certificate', P)]
 
 
+PLAN_MAX_CANDIDATES = 1024     # DRPO_PLAN_MAX_CANDIDATES
+PLAN_SITE = 0x91a7             # DRPO_PLAN_SITE
+
+
+class PlanSample(ctypes.Structure):
+    """drpo_plan_sample_t"""
+    _fields_ = [('P', c_int), ('N', c_int), ('K', c_int), ('A', c_int), ('lo', c_float), ('hi', c_float),
+                ('seed', c_uint64), ('ctr', c_uint64), ('mean', P), ('std', P), ('incumbent', P), ('cand', P)]
+
+
+class PlanRefit(ctypes.Structure):
+    """drpo_plan_refit_t"""
+    _fields_ = [('P', c_int), ('N', c_int), ('H', c_int), ('K', c_int), ('A', c_int), ('C', c_int), ('mode', c_int),
+                ('elites', c_int), ('gamma', c_double),
+                ('reward_scale', c_double), ('alive_bonus', c_double), ('constraint_scale', c_double),
+                ('constraint_offset', c_double),
+                ('temperature', c_double), ('momentum', c_double), ('min_std', c_double),
+                ('threshold', c_float), ('pad_', c_int),
+                ('rewards', P), ('constraint_values', P), ('dones', P), ('violations', P), ('lengths', P),
+                ('terminated', P), ('weights', P), ('terminal_q', P), ('terminal_qc', P), ('cand', P),
+                ('mean_in', P), ('std_in', P),
+                ('mean_out', P), ('std_out', P), ('best_actions', P), ('best', P), ('n_feasible', P),
+                ('best_score', P), ('best_cert', P), ('best_feasible', P),
+                ('score', P), ('cert', P), ('rank', P), ('weight', P)]
+
+
 ENV_PROGRAM = 4          # DRPO_ENV_PROGRAM
 PROG_AFFINE, PROG_BALLS = 0, 1
 PROG_MAX_ROWS = PROG_MAX_TERMS = PROG_MAX_CENTRES = PROG_MAX_BOX = 8
@@ -154,6 +180,8 @@ PROTOTYPES = {
     'drpo_rollout_trajectories_cut': (c_int, [POINTER(RolloutDesc), POINTER(RolloutCut), POINTER(RolloutTraj), P]),
     'drpo_rollout_staging_offsets': (c_int, [c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     'drpo_rollout_lookahead': (c_int, [POINTER(RolloutLookahead), P]),
+    'drpo_plan_sample': (c_int, [POINTER(PlanSample), P]),
+    'drpo_plan_refit': (c_int, [POINTER(PlanRefit), P]),
     'drpo_env_constraints': (c_int, [c_int, c_int, c_int, c_double, c_double, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_constraints_program': (c_int, [P, c_int, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_program_check': (c_int, [POINTER(EnvProgram), c_int]),

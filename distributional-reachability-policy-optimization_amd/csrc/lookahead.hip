@@ -8,17 +8,13 @@
 
 #include "common.hpp"
 
-// The definition is ordered double arithmetic, one rounding per operation. The header's
-// __dadd_rn / __dmul_rn are a plain + and * compiled under the default contraction, which
-// stays with them when they are inlined: a multiply feeding an add became one v_fma_f64 (one
-// rounding for two operations; measured: one float32 of 9,546 off by an ulp at H 128). So the
-// two operations are written here, with contraction off for this file.
-#pragma clang fp contract(off)
+// The definition is ordered double arithmetic, one rounding per operation: the per-step pieces
+// (dadd / dmul, the preprocessing, the two backup steps, look_max, look_store) are in
+// lookahead_rows.hpp, shared with csrc/plan.hip; that header turns contraction off for the
+// rest of this file.
+#include "lookahead_rows.hpp"
 
 namespace drpo {
-
-__device__ __forceinline__ double dadd(double a, double b) { return a + b; }   // round to nearest, never fused
-__device__ __forceinline__ double dmul(double a, double b) { return a * b; }
 
 // ---------------------------------------------------------------------------
 // rollout_lookahead_kernel. One workgroup per LOOK_ROWS rows.
@@ -31,7 +27,7 @@ __device__ __forceinline__ double dmul(double a, double b) { return a * b; }
 //      load, issued before the chain; inside the chain a lane reads LDS only, so the longest
 //      dependent chain is k <= H steps of two double operations (value) or three and a
 //      select (certificate), not H^2 / 2 loads.
-// All arithmetic is double, dadd / dmul above (no contraction), rounded to float32 once
+// All arithmetic is double, dadd / dmul of lookahead_rows.hpp (no contraction), rounded to float32 once
 // at the store; a NaN is stored as the canonical quiet NaN, so that the result does not
 // depend on which NaN an operation produced. Every element of every given output is
 // written, by plain vector stores: lanes of a pass store consecutive addresses.
@@ -62,14 +58,6 @@ __host__ __device__ inline size_t look_lds_bytes(int H, int R) {
          (size_t)R * H;
 }
 
-__device__ __forceinline__ float look_store(double x) {
-  const float f = (float)x;
-  return f != f ? __int_as_float(0x7FC00000) : f;
-}
-
-// torch.maximum on doubles: a NaN in either operand stays
-__device__ __forceinline__ double look_max(double a, double b) { return a != a ? a : (b != b ? b : (a < b ? b : a)); }
-
 __global__ __launch_bounds__(LOOK_NT) void rollout_lookahead_kernel(LookArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char look_smem[];
   const drpo_rollout_lookahead_t& d = p.d;
@@ -98,10 +86,7 @@ __global__ __launch_bounds__(LOOK_NT) void rollout_lookahead_kernel(LookArgs p) 
   }
   for (int e = tid; e < nr * H; e += LOOK_NT) {
     const size_t src = (size_t)row0 * H + e;
-    double r = (double)d.rewards[src];
-    if (rs != 0.0) r = dmul(r, rs);
-    if (ab != 0.0) r = dadd(r, ab);
-    s_r[e] = r;
+    s_r[e] = look_reward(d.rewards[src], rs, ab);
     s_bits[e] = (d.dones[src] ? 1 : 0) | ((cost && d.violations[src]) ? 2 : 0);
   }
   __syncthreads();
@@ -138,9 +123,7 @@ __global__ __launch_bounds__(LOOK_NT) void rollout_lookahead_kernel(LookArgs p) 
       if (c0) __syncthreads();   // the pass before has read its h'
       for (int e = tid; e < nr * H * cw; e += LOOK_NT) {
         const int rt = e / cw, cc = e - rt * cw;   // rt = row * H + t
-        double h = dmul((double)d.constraint_values[((size_t)row0 * H + rt) * C + c0 + cc], cs);
-        h = dadd(h, dmul(h > 0.0 ? 1.0 : 0.0, co));
-        s_h[rt * LOOK_CC + cc] = h;
+        s_h[rt * LOOK_CC + cc] = look_hprime(d.constraint_values[((size_t)row0 * H + rt) * C + c0 + cc], cs, co);
       }
       __syncthreads();
     }
@@ -157,11 +140,7 @@ __global__ __launch_bounds__(LOOK_NT) void rollout_lookahead_kernel(LookArgs p) 
       double x = boot ? (double)xb : 0.0;
       const unsigned char* bp = s_bits + r * H;
       if (cost) {
-        for (int t = kk - 1; t >= 0; --t) {
-          const unsigned b = bp[t];
-          const double v = (b & 2) ? 1.0 : 0.0;
-          x = (b & 1) ? v : dadd(v, dmul(g, x));
-        }
+        for (int t = kk - 1; t >= 0; --t) x = look_cost_step(bp[t], g, x);
       } else {
         const double* hp = s_h + (size_t)r * H * LOOK_CC + cc;
         int t = kk - 1;
@@ -175,11 +154,11 @@ __global__ __launch_bounds__(LOOK_NT) void rollout_lookahead_kernel(LookArgs p) 
             a[u] = dmul(one_minus_g, h[u]);
           }
 #pragma unroll
-          for (int u = 0; u < 4; ++u) x = (b[u] & 1) ? h[u] : dadd(a[u], dmul(g, look_max(h[u], x)));
+          for (int u = 0; u < 4; ++u) x = look_reach_step(b[u] & 1, h[u], a[u], g, x);
         }
         for (; t >= 0; --t) {
           const double h = hp[t * LOOK_CC];
-          x = (bp[t] & 1) ? h : dadd(dmul(one_minus_g, h), dmul(g, look_max(h, x)));
+          x = look_reach_step(bp[t] & 1, h, dmul(one_minus_g, h), g, x);
         }
       }
       d.certificate[(i * H1 + k) * C + c] = look_store(x);

@@ -1,0 +1,271 @@
+// Sampling-based planning on the learned model (drpo_plan_sample, drpo_plan_refit;
+// include/drpo_hip.h has the definitions): the two launches of an MPPI / CEM iteration around
+// one given-actions rollout of P * N rows and the terminal critic forwards. The score of a
+// candidate is entry k = H of the model-based lookahead (src/ssac.py:284-294 unrolled along the
+// trajectory, in the units of src/smbpo.py:260-270), from the per-step pieces of
+// lookahead_rows.hpp that csrc/lookahead.hip runs for every k.
+#include <math.h>
+
+#include "common.hpp"
+
+// ordered double arithmetic, nothing contracted, from here to the end of the file
+#include "lookahead_rows.hpp"
+
+namespace drpo {
+
+constexpr int PLAN_NT = 256;
+
+// ---------------------------------------------------------------------------
+// plan_sample_kernel. One lane per element of cand[P * N][K][A]; a lane's element index is
+// its draw index, so consecutive lanes store consecutive addresses.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(PLAN_NT) void plan_sample_kernel(drpo_plan_sample_t d) {
+  const int64_t KA = (int64_t)d.K * d.A;
+  const int64_t total = (int64_t)d.P * d.N * KA;
+  const int64_t e = (int64_t)blockIdx.x * PLAN_NT + threadIdx.x;
+  if (e >= total) return;
+  const int64_t r = e / KA, j = e - r * KA;
+  const int64_t p = r / d.N;
+  const int n = (int)(r - p * d.N);
+  const int64_t src = p * KA + j;
+  if (n == 0) {
+    d.cand[e] = d.incumbent[src];
+    return;
+  }
+  const float z = normal_at(nullptr, e, d.seed, d.ctr, (uint32_t)DRPO_PLAN_SITE);
+  float x = fmaf(d.std[src], z, d.mean[src]);
+  x = x < d.lo ? d.lo : x;
+  x = x > d.hi ? d.hi : x;
+  d.cand[e] = x;
+}
+
+// ---------------------------------------------------------------------------
+// plan_refit_kernel. One workgroup of 256 lanes per start state.
+//   A. One lane per candidate (N <= 1024: at most four passes) runs the row's two chains at
+//      k = H: the value expansion forwards and, per critic output, the certificate's recursion
+//      backwards, reading its own row's steps directly. The float32 results go to LDS.
+//   B. Ranks by counting over the keys in LDS: lane n counts the rows that precede row n
+//      (N reads that every lane of a wave makes at the same address).
+//   C. The elites' weights, doubles in LDS.
+//   D. One lane per (t, a) of the given steps sums over the elites in candidate order; lanes
+//      read cand[n][t][a] at consecutive addresses. Rows of weight 0 are skipped (the branch
+//      is uniform), so only the elites' actions are fetched.
+// Plain stores, no atomics, no waits between workgroups.
+// ---------------------------------------------------------------------------
+__host__ __device__ inline size_t plan_lds_bytes(int N, int H) {
+  // w[H + 1], weight[N] doubles; score, cert, key [N] floats; class [N] bytes; 4 ints
+  return sizeof(double) * ((size_t)(H + 1) + N) + sizeof(float) * 3 * (size_t)N + sizeof(int) * 4 + (size_t)N;
+}
+
+// the position of row m before row n in a state's order: class (0 feasible, 1 valid and not
+// feasible, 2 invalid), then the key descending (score; -cert; 0), then the lower n
+__device__ __forceinline__ bool plan_precedes(int cm, float km, int m, int cn, float kn, int n) {
+  return cm < cn || (cm == cn && (km > kn || (km == kn && m < n)));
+}
+
+__global__ __launch_bounds__(PLAN_NT) void plan_refit_kernel(drpo_plan_refit_t d) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char plan_smem[];
+  const int N = d.N, H = d.H, C = d.C, tid = threadIdx.x;
+  const int KA = d.K * d.A;
+  double* s_w = reinterpret_cast<double*>(plan_smem);   // [H + 1]
+  double* s_wt = s_w + (H + 1);                         // [N]
+  float* s_score = reinterpret_cast<float*>(s_wt + N);  // [N]
+  float* s_cert = s_score + N;                          // [N]
+  float* s_key = s_cert + N;                            // [N]
+  int* s_int = reinterpret_cast<int*>(s_key + N);       // best, n_feasible, n_valid
+  unsigned char* s_cls = reinterpret_cast<unsigned char*>(s_int + 4);   // [N]
+
+  const size_t p = blockIdx.x;
+  const size_t row0 = p * (size_t)N;
+  const double g = d.gamma, one_minus_g = 1.0 - d.gamma;
+  const double rs = d.reward_scale, ab = d.alive_bonus, cs = d.constraint_scale, co = d.constraint_offset;
+  const bool cost = d.mode == 1;
+  const float thr = d.threshold;
+
+  for (int e = tid; e <= H; e += PLAN_NT) s_w[e] = d.weights[e];
+  __syncthreads();
+
+  // ---- A. score and cert of every candidate -------------------------------------
+  for (int n = tid; n < N; n += PLAN_NT) {
+    const size_t r = row0 + n;
+    const int len = min(max(d.lengths[r], 0), H);
+    const bool boot = d.terminated[r] == 0;
+    const float* rw = d.rewards + r * H;
+    const uint8_t* dn = d.dones + r * H;
+    double acc = 0.0;
+    for (int t = 0; t < len; ++t) acc = dadd(acc, dmul(s_w[t], look_reward(rw[t], rs, ab)));
+    if (boot) acc = dadd(acc, dmul(s_w[len], (double)d.terminal_q[r]));
+    double top = 0.0;
+    for (int c = 0; c < C; ++c) {
+      // a terminated row has no bootstrap: the scan starts from 0.0, which the done select of
+      // its last step replaces
+      double x = boot ? (double)d.terminal_qc[r * C + c] : 0.0;
+      if (cost) {
+        const uint8_t* vi = d.violations + r * H;
+        for (int t = len - 1; t >= 0; --t) x = look_cost_step((dn[t] ? 1u : 0u) | (vi[t] ? 2u : 0u), g, x);
+      } else {
+        const float* hv = d.constraint_values + r * H * C + c;
+        for (int t = len - 1; t >= 0; --t) {
+          const double h = look_hprime(hv[(size_t)t * C], cs, co);
+          x = look_reach_step(dn[t] != 0, h, dmul(one_minus_g, h), g, x);
+        }
+      }
+      top = c == 0 ? x : look_max(top, x);
+    }
+    const float sc = look_store(acc), ce = look_store(top);
+    const bool valid = sc == sc && ce == ce;
+    const int cls = valid ? (ce <= thr ? 0 : 1) : 2;
+    s_score[n] = sc;
+    s_cert[n] = ce;
+    s_cls[n] = (unsigned char)cls;
+    s_key[n] = cls == 0 ? sc : (cls == 1 ? -ce : 0.f);
+    if (d.score) d.score[r] = sc;
+    if (d.cert) d.cert[r] = ce;
+  }
+  __syncthreads();
+
+  // ---- B. the order ---------------------------------------------------------------
+  // every lane counts the classes itself (the same N reads as its ranks): no reduction
+  int nf = 0, nv = 0;
+  for (int m = 0; m < N; ++m) {
+    const int c = s_cls[m];
+    nf += c == 0;
+    nv += c <= 1;
+  }
+  const int Ke = min(d.elites, nf > 0 ? nf : nv);
+  int my_rank[DRPO_PLAN_MAX_CANDIDATES / PLAN_NT];
+#pragma unroll
+  for (int j = 0; j < DRPO_PLAN_MAX_CANDIDATES / PLAN_NT; ++j) {
+    const int n = tid + j * PLAN_NT;
+    int rank = 0;
+    if (n < N) {
+      const int cn = s_cls[n];
+      const float kn = s_key[n];
+      for (int m = 0; m < N; ++m) rank += plan_precedes(s_cls[m], s_key[m], m, cn, kn, n) ? 1 : 0;
+      if (rank == 0) s_int[0] = n;
+      if (d.rank) d.rank[row0 + n] = rank;
+    }
+    my_rank[j] = rank;
+  }
+  __syncthreads();
+  const int best = s_int[0];
+
+  // ---- C. the elites' weights -------------------------------------------------------
+  const double key_best = (double)s_key[best];
+  const bool flat = isinf(d.temperature);
+#pragma unroll
+  for (int j = 0; j < DRPO_PLAN_MAX_CANDIDATES / PLAN_NT; ++j) {
+    const int n = tid + j * PLAN_NT;
+    if (n < N) {
+      double w = 0.0;
+      if (my_rank[j] < Ke) {
+        const double key = (double)s_key[n];
+        const double diff = key == key_best ? 0.0 : key - key_best;
+        w = flat ? 1.0 : exp(diff / d.temperature);
+      }
+      s_wt[n] = w;
+      if (d.weight) d.weight[row0 + n] = (float)w;
+    }
+  }
+  __syncthreads();
+
+  // ---- D. the refit, E. the best candidate ------------------------------------------
+  const double mom = d.momentum, keep = 1.0 - d.momentum;
+  const float* cand0 = d.cand + row0 * KA;
+  for (int e = tid; e < KA; e += PLAN_NT) {
+    const size_t o = p * KA + e;
+    const float mean_in = d.mean_in[o], std_in = d.std_in[o];
+    float mean_out = mean_in, std_out = std_in;
+    double sw = 0.0, swx = 0.0;
+    for (int n = 0; n < N; ++n) {
+      const double w = s_wt[n];
+      if (w > 0.0) {
+        sw = dadd(sw, w);
+        swx = dadd(swx, dmul(w, (double)cand0[(size_t)n * KA + e]));
+      }
+    }
+    if (sw > 0.0) {
+      const double m = swx / sw;
+      double sv = 0.0;
+      for (int n = 0; n < N; ++n) {
+        const double w = s_wt[n];
+        if (w > 0.0) {
+          const double dx = dadd((double)cand0[(size_t)n * KA + e], -m);
+          sv = dadd(sv, dmul(w, dmul(dx, dx)));
+        }
+      }
+      const double v = sv / sw;
+      const double s = dadd(dmul(keep, sqrt(v)), dmul(mom, (double)std_in));
+      mean_out = (float)dadd(dmul(keep, m), dmul(mom, (double)mean_in));
+      std_out = (float)(s < d.min_std ? d.min_std : s);
+    }
+    d.mean_out[o] = mean_out;
+    d.std_out[o] = std_out;
+    d.best_actions[o] = cand0[(size_t)best * KA + e];
+  }
+  if (tid == 0) {
+    d.best[p] = best;
+    d.n_feasible[p] = nf;
+    d.best_score[p] = s_score[best];
+    d.best_cert[p] = s_cert[best];
+    d.best_feasible[p] = s_cls[best] == 0 ? 1 : 0;
+  }
+}
+
+}  // namespace drpo
+
+using namespace drpo;
+
+DRPO_API int drpo_plan_sample(const drpo_plan_sample_t* d, drpo_stream_t stream_) {
+  const char* who = "drpo_plan_sample";
+  DRPO_REQUIRE(d, "%s: null descriptor", who);
+  DRPO_REQUIRE(d->P >= 0, "%s: P=%d is negative", who, d->P);
+  DRPO_REQUIRE(d->N >= 2 && d->N <= DRPO_PLAN_MAX_CANDIDATES, "%s: N=%d outside 2..%d", who, d->N,
+               DRPO_PLAN_MAX_CANDIDATES);
+  DRPO_REQUIRE(d->K >= 1, "%s: K=%d, need K >= 1", who, d->K);
+  DRPO_REQUIRE(d->A >= 1, "%s: A=%d, need A >= 1", who, d->A);
+  DRPO_REQUIRE(d->lo <= d->hi, "%s: clamp [%g, %g] is empty or NaN", who, (double)d->lo, (double)d->hi);
+  DRPO_REQUIRE(d->mean && d->std && d->incumbent && d->cand, "%s: null pointer", who);
+  if (d->P == 0) return DRPO_OK;
+  // (K * A may not overflow the 64-bit product: each factor is below 2^31, P * N below 2^41)
+  const double total = (double)d->P * d->N * d->K * d->A;
+  DRPO_REQUIRE(total < 1099511627776.0, "%s: P*N*K*A = %.0f elements exceed one grid (2^40)", who, total);
+  const int64_t n = (int64_t)d->P * d->N * d->K * d->A;
+  plan_sample_kernel<<<(unsigned)((n + PLAN_NT - 1) / PLAN_NT), PLAN_NT, 0, (hipStream_t)stream_>>>(*d);
+  DRPO_LAUNCH_CHECK("plan_sample");
+  return DRPO_OK;
+}
+
+DRPO_API int drpo_plan_refit(const drpo_plan_refit_t* d, drpo_stream_t stream_) {
+  const char* who = "drpo_plan_refit";
+  DRPO_REQUIRE(d, "%s: null descriptor", who);
+  DRPO_REQUIRE(d->P >= 0, "%s: P=%d is negative", who, d->P);
+  DRPO_REQUIRE(d->N >= 2 && d->N <= DRPO_PLAN_MAX_CANDIDATES, "%s: N=%d outside 2..%d", who, d->N,
+               DRPO_PLAN_MAX_CANDIDATES);
+  DRPO_REQUIRE((int64_t)d->P * d->N <= INT32_MAX, "%s: P*N = %lld rows exceed int32", who,
+               (long long)((int64_t)d->P * d->N));
+  DRPO_REQUIRE(d->H >= 1 && d->H <= DRPO_ROLLOUT_FUSED_MAX_H, "%s: H=%d outside 1..%d", who, d->H,
+               DRPO_ROLLOUT_FUSED_MAX_H);
+  DRPO_REQUIRE(d->K >= 1 && d->K <= d->H, "%s: K=%d outside 1..H=%d", who, d->K, d->H);
+  DRPO_REQUIRE(d->A >= 1, "%s: A=%d, need A >= 1", who, d->A);
+  DRPO_REQUIRE((int64_t)d->K * d->A <= INT32_MAX, "%s: K*A exceeds int32", who);
+  DRPO_REQUIRE(d->C >= 1, "%s: C=%d, need C >= 1", who, d->C);
+  DRPO_REQUIRE(d->mode == 0 || d->mode == 1, "%s: mode %d (0 reachability, 1 cost)", who, d->mode);
+  DRPO_REQUIRE(isfinite(d->gamma) && d->gamma >= 0.0 && d->gamma <= 1.0, "%s: gamma %g outside [0, 1]", who, d->gamma);
+  DRPO_REQUIRE(d->elites >= 1 && d->elites <= d->N, "%s: elites=%d outside 1..N=%d", who, d->elites, d->N);
+  DRPO_REQUIRE(d->temperature > 0.0, "%s: temperature %g, need > 0 (+inf allowed)", who, d->temperature);
+  DRPO_REQUIRE(d->momentum >= 0.0 && d->momentum < 1.0, "%s: momentum %g outside [0, 1)", who, d->momentum);
+  DRPO_REQUIRE(isfinite(d->min_std) && d->min_std >= 0.0, "%s: min_std %g, need finite and >= 0", who, d->min_std);
+  DRPO_REQUIRE(d->threshold == d->threshold, "%s: threshold is NaN", who);
+  DRPO_REQUIRE(d->rewards && d->constraint_values && d->dones && d->lengths && d->terminated && d->weights &&
+                   d->terminal_q && d->terminal_qc && d->cand && d->mean_in && d->std_in,
+               "%s: null input pointer", who);
+  DRPO_REQUIRE(d->mode == 0 || d->violations, "%s: null violations in cost mode", who);
+  DRPO_REQUIRE(d->mean_out && d->std_out && d->best_actions && d->best && d->n_feasible && d->best_score &&
+                   d->best_cert && d->best_feasible,
+               "%s: null per-state output pointer", who);
+  if (d->P == 0) return DRPO_OK;
+  plan_refit_kernel<<<(unsigned)d->P, PLAN_NT, plan_lds_bytes(d->N, d->H), (hipStream_t)stream_>>>(*d);
+  DRPO_LAUNCH_CHECK("plan_refit");
+  return DRPO_OK;
+}

@@ -735,28 +735,14 @@ def _lookahead_request(alg, lookahead):
     raise ValueError(f"lookahead: {lookahead!r} (None, True or 'bound')")
 
 
-def lookahead(alg, policy, im, kind, gamma, *, reward_scale=None, alive_bonus=None, constraint_scale=None,
-              constraint_offset=None):
-    """What the two critics say along and at the end of the imagined trajectories ``im`` (one
-    run, cut or not): fills the group 'lookahead' (imagine(lookahead=)). The stand-alone
-    forwards of solver.critic (min over its nets) and solver.constraint_critic (kind 'mean': its
-    mean, 'bound': mean + std_ratio * std) at every (states[i, t], actions[i, t]) and at the
-    state a row ends in (under ``policy``'s and actor_safe's mean action), masked to zero
-    beyond the lengths and for terminated rows; then one drpo_rollout_lookahead launch for the
-    k-step expansions, k = 0..H. Dead rows are evaluated and masked, not compacted. Makes no
-    draw and moves no counter. gamma: the discount; the four scales (src/smbpo.py:260-270)
-    default to the trainer's config."""
-    from ._abi import RolloutLookahead
+def _critic_forwards(alg, kind):
+    """(qmin, qc) of the lookahead: the stand-alone forwards of solver.critic (min over its nets)
+    and solver.constraint_critic (kind 'mean': its mean, 'bound': mean + std_ratio * std; always
+    [rows, C]). Neither draws."""
     global _NO_DRAW
     assert kind in ('mean', 'bound'), kind
     sol, cc = alg.solver, alg.solver.constraint_critic
-    B, H = im.rewards.shape
-    S, A, C = alg.state_dim, alg.action_dim, cc.output_dim
-    dev = im.rewards.device
-    _lib.require_device(im.rewards, im.states, im.actions)
-    cfg = {'reward_scale': reward_scale, 'alive_bonus': alive_bonus, 'constraint_scale': constraint_scale,
-           'constraint_offset': constraint_offset}
-    cfg = {k: float(getattr(alg, k) if v is None else v) for k, v in cfg.items()}
+    C = cc.output_dim
     if kind == 'bound' and _NO_DRAW is None:
         from .rng import DeviceNoise
         _NO_DRAW = DeviceNoise(0, rank=0, world=1)
@@ -771,18 +757,62 @@ def lookahead(alg, policy, im, kind, gamma, *, reward_scale=None, alive_bonus=No
         for other in qs[1:]:
             q = torch.min(q, other)
         return q
+    return qmin, qc
+
+
+def _terminal_critics(alg, policy, im, kind, forwards=None):
+    """(terminal_q [B], terminal_qc [B, C]) of the imagined trajectories ``im``: the two critics at
+    the state a row ends in, states[i, lengths[i]], under ``policy``'s and actor_safe's mean
+    action; zero for terminated rows. What ops.lookahead closes its expansions with and all that
+    SMBPO.plan's score (k = H) needs of the critics. forwards: _critic_forwards(alg, kind), if the
+    caller has them."""
+    qmin, qc = _critic_forwards(alg, kind) if forwards is None else forwards
+    B, H = im.rewards.shape
+    S = alg.state_dim
+    zero = 0.0      # (a scalar operand of torch.where: no fill launch)
+    at = im.lengths.clamp(0, H).to(torch.int64).reshape(B, 1, 1).expand(B, 1, S)
+    last = torch.gather(im.states, 1, at).reshape(B, S)
+    alive = ~im.terminated.view(torch.bool)
+    terminal_q = torch.where(alive, qmin(last, policy.act(last, eval=True)).reshape(B), zero)
+    terminal_qc = torch.where(alive.unsqueeze(-1), qc(last, alg.actor_safe.act(last, eval=True)), zero)
+    return terminal_q, terminal_qc
+
+
+def _lookahead_scales(alg, reward_scale=None, alive_bonus=None, constraint_scale=None, constraint_offset=None):
+    """The four scales of the critics' training units (src/smbpo.py:260-270): the trainer's config
+    where not given."""
+    cfg = {'reward_scale': reward_scale, 'alive_bonus': alive_bonus, 'constraint_scale': constraint_scale,
+           'constraint_offset': constraint_offset}
+    return {k: float(getattr(alg, k) if v is None else v) for k, v in cfg.items()}
+
+
+def lookahead(alg, policy, im, kind, gamma, *, reward_scale=None, alive_bonus=None, constraint_scale=None,
+              constraint_offset=None):
+    """What the two critics say along and at the end of the imagined trajectories ``im`` (one
+    run, cut or not): fills the group 'lookahead' (imagine(lookahead=)). The stand-alone
+    forwards of solver.critic (min over its nets) and solver.constraint_critic (kind 'mean': its
+    mean, 'bound': mean + std_ratio * std) at every (states[i, t], actions[i, t]) and at the
+    state a row ends in (under ``policy``'s and actor_safe's mean action; _terminal_critics),
+    masked to zero beyond the lengths and for terminated rows; then one drpo_rollout_lookahead
+    launch for the k-step expansions, k = 0..H. Dead rows are evaluated and masked, not
+    compacted. Makes no draw and moves no counter. gamma: the discount; the four scales
+    (src/smbpo.py:260-270) default to the trainer's config."""
+    from ._abi import RolloutLookahead
+    assert kind in ('mean', 'bound'), kind
+    sol, cc = alg.solver, alg.solver.constraint_critic
+    B, H = im.rewards.shape
+    S, A, C = alg.state_dim, alg.action_dim, cc.output_dim
+    dev = im.rewards.device
+    _lib.require_device(im.rewards, im.states, im.actions)
+    cfg = _lookahead_scales(alg, reward_scale, alive_bonus, constraint_scale, constraint_offset)
+    qmin, qc = _critic_forwards(alg, kind)
 
     mask = im.mask
     s, a = im.states[:, :-1].reshape(B * H, S), im.actions.reshape(B * H, A)
     zero = torch.zeros((), device=dev)
     step_q = torch.where(mask, qmin(s, a).reshape(B, H), zero)
     step_qc = torch.where(mask.unsqueeze(-1), qc(s, a).reshape(B, H, C), zero)
-    # the state a row ends in: states[i, lengths[i]]
-    at = im.lengths.clamp(0, H).to(torch.int64).reshape(B, 1, 1).expand(B, 1, S)
-    last = torch.gather(im.states, 1, at).reshape(B, S)
-    alive = ~im.terminated.view(torch.bool)
-    terminal_q = torch.where(alive, qmin(last, policy.act(last, eval=True)).reshape(B), zero)
-    terminal_qc = torch.where(alive.unsqueeze(-1), qc(last, alg.actor_safe.act(last, eval=True)), zero)
+    terminal_q, terminal_qc = _terminal_critics(alg, policy, im, kind, (qmin, qc))
 
     w = torch.as_tensor(np.power(np.float64(gamma), np.arange(H + 1, dtype=np.float64))).to(dev)
     value = torch.empty(B, H + 1, device=dev)
@@ -802,6 +832,106 @@ def lookahead(alg, policy, im, kind, gamma, *, reward_scale=None, alive_bonus=No
     im.set_group('lookahead', step_q=step_q, step_qc=step_qc, terminal_q=terminal_q, terminal_qc=terminal_qc,
                  value_lookahead=value, certificate_lookahead=cert, lookahead_kind=kind)
     return im
+
+
+# ---------------------------------------------------------------------------
+# planning on the model (SMBPO.plan): the two launches of an iteration
+# ---------------------------------------------------------------------------
+# the limits and the draw site of csrc/plan.hip (literals so that this module imports before the
+# library loads: tests/test_plan_checks.py pins them to drpo_abi_const)
+PLAN_MAX_CANDIDATES = 1024
+PLAN_SITE = 0x91a7
+
+
+class PlanResult:
+    """What SMBPO.plan found for P start states, N candidates of K given steps each:
+
+      actions [P, K, A]          the best action sequence of the last iteration (its rank 0)
+      action [P, A]              actions[:, 0], the action to take now
+      score [P]                  its planning score, value_lookahead[:, H] of its trajectory
+      certificate [P]            the largest of its certificate_lookahead[:, H, :]
+      feasible [P] bool          certificate <= threshold (and neither is NaN)
+      n_feasible [P] int32       feasible candidates of the last iteration
+      mean, std [P, K, A]        the sampling distribution after the last refit
+      history_score, history_certificate, history_feasible [iterations, P]   the best row of each iteration
+    and of the last iteration:
+      candidates [P, N, K, A]; scores, certificates [P, N]; ranks [P, N] int32 (0 the best)
+      imagined                   the ImaginedRollout of its P * N rows (row p * N + n)
+    ``threshold`` is the certificate threshold as compared (float32), ``lookahead_kind`` 'mean'
+    or 'bound'."""
+    FIELDS = ('actions', 'action', 'score', 'certificate', 'feasible', 'n_feasible', 'mean', 'std', 'history_score',
+              'history_certificate', 'history_feasible', 'candidates', 'scores', 'certificates', 'ranks', 'imagined',
+              'threshold', 'lookahead_kind')
+
+    def __init__(self, **fields):
+        assert set(fields) == set(self.FIELDS), sorted(set(fields) ^ set(self.FIELDS))
+        self.__dict__.update(fields)
+
+
+def plan_sample(mean, std, incumbent, candidates, seed, ctr, lo=-1.0, hi=1.0):
+    """The candidates of one planning iteration (drpo_plan_sample): [P * N, K, A] from mean, std
+    and incumbent (contiguous float32 device tensors [P, K, A]). Candidate 0 of every state is
+    its incumbent; the others are mean + std * z clamped to [lo, hi], z the Philox normals of
+    (seed, ctr, PLAN_SITE). lo / hi default to the post-tanh range."""
+    from ._abi import PlanSample
+    _lib.require_device(mean, std, incumbent)
+    P, K, A = mean.shape
+    for t in (mean, std, incumbent):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (P, K, A), 'plan_sample: [P, K, A]'
+    cand = torch.empty(P * int(candidates), K, A, device=mean.device)
+    d = PlanSample()
+    d.P, d.N, d.K, d.A, d.lo, d.hi = P, int(candidates), K, A, float(lo), float(hi)
+    d.seed, d.ctr = int(seed) & 0xFFFFFFFFFFFFFFFF, int(ctr) & 0xFFFFFFFFFFFFFFFF
+    d.mean, d.std, d.incumbent, d.cand = mean.data_ptr(), std.data_ptr(), incumbent.data_ptr(), cand.data_ptr()
+    _lib.check(_lib.lib().drpo_plan_sample(ctypes.byref(d), _lib.stream()), 'plan_sample')
+    return cand
+
+
+def plan_refit(alg, im, terminal_q, terminal_qc, cand, mean, std, gamma, *, candidates, threshold, elites,
+               temperature, momentum, min_std, reward_scale=None, alive_bonus=None, constraint_scale=None,
+               constraint_offset=None):
+    """Scores, ranks and refits one planning iteration (drpo_plan_refit) on the run ``im`` of
+    P * N rows under ``cand`` [P * N, K, A], with the terminal critics' values of
+    _terminal_critics. mean / std [P, K, A] are read, not written. Returns a dict of fresh
+    tensors: mean, std, best_actions [P, K, A]; best, n_feasible (int32), best_score, best_cert,
+    best_feasible (bool) [P]; score, cert, rank (int32), weight [P, N]."""
+    from ._abi import PlanRefit
+    sol = alg.solver
+    B, H = im.rewards.shape
+    N = int(candidates)
+    P, K, A = mean.shape
+    C = sol.constraint_critic.output_dim
+    assert B == P * N and tuple(cand.shape) == (B, K, A), 'plan_refit: cand is [P * N, K, A]'
+    dev = im.rewards.device
+    w = torch.as_tensor(np.power(np.float64(gamma), np.arange(H + 1, dtype=np.float64))).to(dev)
+    keep = [t.contiguous() for t in (im.rewards, im.constraint_values, im.dones, im.violations, im.lengths,
+                                     im.terminated, terminal_q, terminal_qc, cand, mean, std)]
+    _lib.require_device(*keep)
+    f32, i32 = torch.float32, torch.int32
+    out = {'mean': torch.empty(P, K, A, device=dev), 'std': torch.empty(P, K, A, device=dev),
+           'best_actions': torch.empty(P, K, A, device=dev), 'best': torch.empty(P, dtype=i32, device=dev),
+           'n_feasible': torch.empty(P, dtype=i32, device=dev), 'best_score': torch.empty(P, device=dev),
+           'best_cert': torch.empty(P, device=dev), 'best_feasible': torch.empty(P, dtype=torch.uint8, device=dev),
+           'score': torch.empty(P, N, device=dev), 'cert': torch.empty(P, N, device=dev),
+           'rank': torch.empty(P, N, dtype=i32, device=dev), 'weight': torch.empty(P, N, device=dev)}
+    d = PlanRefit()
+    d.P, d.N, d.H, d.K, d.A, d.C, d.elites = P, N, H, K, A, C, int(elites)
+    d.mode, d.gamma = 0 if sol.constrained_fcn == 'reachability' else 1, float(gamma)
+    for k, v in _lookahead_scales(alg, reward_scale, alive_bonus, constraint_scale, constraint_offset).items():
+        setattr(d, k, v)
+    d.temperature, d.momentum, d.min_std, d.threshold = float(temperature), float(momentum), float(min_std), threshold
+    if d.mode == 0:
+        assert tuple(im.constraint_values.shape) == (B, H, C), 'constraint_values: one column per critic output'
+    (d.rewards, d.constraint_values, d.dones, d.violations, d.lengths, d.terminated, d.terminal_q, d.terminal_qc,
+     d.cand, d.mean_in, d.std_in) = (t.data_ptr() for t in keep)
+    d.weights = w.data_ptr()
+    d.mean_out, d.std_out = out['mean'].data_ptr(), out['std'].data_ptr()
+    for k in ('best_actions', 'best', 'n_feasible', 'best_score', 'best_cert', 'best_feasible', 'score', 'cert',
+              'rank', 'weight'):
+        setattr(d, k, out[k].data_ptr())
+    _lib.check(_lib.lib().drpo_plan_refit(ctypes.byref(d), _lib.stream()), 'plan_refit')
+    out['best_feasible'] = out['best_feasible'].view(torch.bool)
+    return out
 
 
 def rollout_host_env(alg, policy, initial_states, noise):

@@ -442,6 +442,141 @@ class SMBPO(Configurable, Module):
         # max_disagreement: >= 0, and 0 beyond a row's length
         im.set_group('uncertainty', max_disagreement=vals['disagreement'].max(dim=-1).values, **vals)
 
+    PLAN_SALT = 0x91A7
+
+    def plan(self, states, horizon=None, *, candidates=64, iterations=4, steps=None, elites=None,
+             temperature=float('inf'), momentum=0.0, init=None, init_std=0.5, min_std=0.05, threshold=None,
+             lookahead=True, policy=None, members=None, model_noise=False, discount=None, noise=None):
+        """The best of sampled action sequences from each of the P ``states``, by the model and the
+        two critics: an MPPI / CEM planner whose score is imagine(actions=, lookahead=)'s
+        value_lookahead[:, H] and whose constraint is its certificate_lookahead[:, H] (the
+        largest output) <= ``threshold``: "the best sequence whose unrolled certificate stays
+        under the shield's threshold". Returns an ops.PlanResult. Per iteration: one launch
+        that draws ``candidates`` sequences per state around the current mean (candidate 0 is
+        the incumbent, the best so far), one imagine(actions=, deterministic=True) of
+        P * candidates rows, the critics at the states the rows end in, and one launch that
+        scores, ranks and refits (drpo_plan_sample, drpo_plan_refit have the definitions).
+        Nothing syncs with the host inside the loop, and nothing of the training state changes:
+        not the trainer's stream, the buffers, steps_sampled or imagine's private stream.
+
+        horizon      H, default self.horizon (<= 128); steps: K, the planned steps, 1..H, default
+                     H. From step K on the policy's mean action continues the row.
+        candidates   N per state, 2..1024; iterations >= 1.
+        elites       the rows a refit uses, 1..N; default max(1, N // 8). A refit takes the best
+                     feasible rows (certificate <= threshold) by score; a state without a
+                     feasible row the rows of the least certificate.
+        temperature  > 0: an elite's weight is exp((score - best score) / temperature); the
+                     default inf weighs the elites alike (CEM), small values approach the best
+                     row alone (MPPI's exponential weights over the elites).
+        momentum     in [0, 1): the share of the old mean and std a refit keeps.
+        init         None: a zero mean; 'policy': the first K mean actions of the policy's own
+                     deterministic trajectory (one more imagine run); or a [P, K, A] tensor.
+                     The first incumbent is the initial mean. init_std > 0: the initial std of
+                     every action; min_std >= 0: the floor of every refit.
+        threshold    default self.safe_shield_threshold; -inf: no row is feasible and the result
+                     is the least certificate; +inf: the argmax of the score.
+        lookahead    True: the constraint critic's mean; 'bound': its distributional bound.
+        policy, members, model_noise, discount   as imagine's. members=None draws one elite per
+                     step anew in every iteration, so scores of different iterations are then
+                     not comparable; an int or H ints fix the model. Not 'each'.
+        noise        default a stream private to plan, derived from the trainer's seed. Each
+                     sample launch takes one noise.next(), and imagine runs on the same object.
+        Not with a recorded tape; NotImplementedError for an env without device constraint
+        functions, as imagine. halt= / shield= inside the planner, time-correlated noise and a
+        shifted warm start are not built."""
+        from . import ops
+        from .rng import _mix64
+        if self.env_params is None:
+            raise NotImplementedError('plan needs the constraint functions on the device, as imagine does: give the '
+                                      'env a ConstraintProgram (drpo_constraint_program, see INTEGRATION.md)')
+
+        def is_int(x):
+            return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+        def is_num(x):
+            return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+        H = self.horizon if horizon is None else horizon
+        if not (is_int(H) and 1 <= H <= ops.TRAJ_MAX_H):
+            raise ValueError(f'horizon: {H!r} (an int, 1..{ops.TRAJ_MAX_H})')
+        N, K = candidates, H if steps is None else steps
+        if not (is_int(N) and 2 <= N <= ops.PLAN_MAX_CANDIDATES):
+            raise ValueError(f'candidates: {N!r} (an int, 2..{ops.PLAN_MAX_CANDIDATES})')
+        if not (is_int(iterations) and iterations >= 1):
+            raise ValueError(f'iterations: {iterations!r} (an int >= 1)')
+        if not (is_int(K) and 1 <= K <= H):
+            raise ValueError(f'steps: {K!r} (an int, 1..horizon {H})')
+        elites = max(1, N // 8) if elites is None else elites
+        if not (is_int(elites) and 1 <= elites <= N):
+            raise ValueError(f'elites: {elites!r} (an int, 1..candidates {N})')
+        if not (is_num(temperature) and temperature > 0):
+            raise ValueError(f'temperature: {temperature!r} (> 0; inf weighs the elites alike)')
+        if not (is_num(momentum) and 0 <= momentum < 1):
+            raise ValueError(f'momentum: {momentum!r} (in [0, 1))')
+        if not (is_num(min_std) and 0 <= min_std < float('inf')):
+            raise ValueError(f'min_std: {min_std!r} (finite, >= 0)')
+        if not (is_num(init_std) and 0 < init_std < float('inf')):
+            raise ValueError(f'init_std: {init_std!r} (finite, > 0)')
+        threshold = self.safe_shield_threshold if threshold is None else threshold
+        if not (is_num(threshold) and threshold == threshold):
+            raise ValueError(f'threshold: {threshold!r} (a number; -inf and inf are allowed)')
+        threshold = float(np.float32(threshold))
+        look = ops._lookahead_request(self, lookahead)
+        if look is None:
+            raise ValueError(f"lookahead: {lookahead!r} (plan scores with the critics: True or 'bound')")
+        if isinstance(members, str):
+            raise ValueError(f"members: {members!r} (None, an int or {H} ints; 'each' is not for plan)")
+        if noise is not None and noise.parity:
+            raise ValueError('plan with a recorded tape: a tape fixes the draws of one rollout, not of a planner')
+        if states is None:
+            raise ValueError('plan needs start states')
+        states = torch.as_tensor(states, dtype=torch.float32).reshape(-1, self.state_dim)
+        P, A = len(states), self.action_dim
+        if isinstance(init, str) and init != 'policy' or not (init is None or isinstance(init, str) or
+                                                                torch.is_tensor(init) or isinstance(init, np.ndarray)):
+            raise ValueError(f"init: {init!r} (None, 'policy' or a [P, K, A] tensor)")
+        if init is not None and not isinstance(init, str):
+            init = torch.as_tensor(init, dtype=torch.float32)
+            if tuple(init.shape) != (P, K, A):
+                raise ValueError(f'init: shape {tuple(init.shape)} is not [{P}, {K}, {A}]')
+
+        # the device work
+        dev = self.device
+        states = states.to(dev)
+        policy = self.actor if policy is None else policy
+        if noise is None:
+            if self.__dict__.get('_plan_noise') is None:
+                self._plan_noise = DeviceNoise(_mix64(self.noise.base_seed ^ self.PLAN_SALT), rank=0, world=1)
+            noise = self._plan_noise
+        gamma = float(self.solver.discount if discount is None else discount)
+        run = dict(members=members, deterministic=True, model_noise=model_noise, discount=gamma, noise=noise)
+        if init is None:
+            mean = torch.zeros(P, K, A, device=dev)
+        elif isinstance(init, str):
+            mean = self.imagine(states, policy, H, **run).actions[:, :K].contiguous()
+        else:
+            mean = init.to(dev).contiguous()
+        std = torch.full((P, K, A), float(init_std), device=dev)
+        incumbent = mean
+        tiled = states.repeat_interleave(N, dim=0)
+        history = []
+        for _ in range(iterations):
+            cand = ops.plan_sample(mean, std, incumbent, N, noise.seed, noise.next())
+            im = self.imagine(tiled, policy, H, actions=cand, **run)
+            terminal_q, terminal_qc = ops._terminal_critics(self, policy, im, look)
+            fit = ops.plan_refit(self, im, terminal_q, terminal_qc, cand, mean, std, gamma, candidates=N,
+                                 threshold=threshold, elites=elites, temperature=temperature, momentum=momentum,
+                                 min_std=min_std)
+            mean, std, incumbent = fit['mean'], fit['std'], fit['best_actions']
+            history.append((fit['best_score'], fit['best_cert'], fit['best_feasible']))
+        return ops.PlanResult(
+            actions=incumbent, action=incumbent[:, 0], score=fit['best_score'], certificate=fit['best_cert'],
+            feasible=fit['best_feasible'], n_feasible=fit['n_feasible'], mean=mean, std=std,
+            history_score=torch.stack([h[0] for h in history]),
+            history_certificate=torch.stack([h[1] for h in history]),
+            history_feasible=torch.stack([h[2] for h in history]),
+            candidates=cand.reshape(P, N, K, A), scores=fit['score'], certificates=fit['cert'], ranks=fit['rank'],
+            imagined=im, threshold=threshold, lookahead_kind=look)
+
     def update_models(self, model_steps, noise=None):
         """src/smbpo.py:214-227."""
         log.message(f'Fitting models @ t = {self.steps_sampled.item()}')

@@ -90,7 +90,9 @@ enum {
   DRPO_OPTIM_MAX_SEGS = 8,        /* segments of one drpo_optim_step */
   DRPO_MLP_MULTI_MAX_JOBS = 8,    /* jobs of one drpo_mlp_forward_multi / drpo_mlp_backward_multi* */
   DRPO_MLP_MULTI_MAX_SLOTS = 16,  /* (job, net) workgroup slots of such a launch */
-  DRPO_MLP_FB_MAX_JOBS = 4        /* jobs of one drpo_mlp_fb_multi */
+  DRPO_MLP_FB_MAX_JOBS = 4,       /* jobs of one drpo_mlp_fb_multi */
+  DRPO_PLAN_MAX_CANDIDATES = 1024, /* candidates per start state of drpo_plan_sample / drpo_plan_refit */
+  DRPO_PLAN_SITE = 0x91a7         /* the Philox site (third counter word) of drpo_plan_sample's draws */
 };
 
 /* ---------------------------------------------------------------- library */
@@ -386,6 +388,105 @@ typedef struct {
 } drpo_rollout_lookahead_t;
 
 int drpo_rollout_lookahead(const drpo_rollout_lookahead_t* d /* host */, drpo_stream_t stream);
+
+/* Sampling-based planning on the learned model (MPPI / CEM over action sequences, for P start
+ * states at once): the two launches around one drpo_rollout_trajectories_given run of
+ * B = P * N rows and the terminal critic forwards. The reference has no counterpart on the
+ * device (its MPC baseline, src/viz_tracking/opt_controller.py, solves one state at a time on
+ * the host).
+ *
+ * drpo_plan_sample: the candidates cand[P * N][K][A] of one iteration from mean, std and
+ * incumbent (each [P][K][A]). Row r = p * N + n, element (r, t, a):
+ *   n == 0: incumbent[p][t][a], copied bit for bit;
+ *   n >= 1: x = fmaf(std[p][t][a], z, mean[p][t][a]); x = x < lo ? lo : x; x = x > hi ? hi : x
+ *           (selects: a NaN stays), z = normal_at(idx = (r * K + t) * A + a, seed, ctr,
+ *           DRPO_PLAN_SITE), the generator of every normal_at site (counter words
+ *           (idx >> 2, idx >> 34, site, ctr), lane idx & 3).
+ * Every element of cand is written. DRPO_EINVAL before any launch: a null descriptor or
+ * pointer, P < 0, N outside 2..DRPO_PLAN_MAX_CANDIDATES, K < 1, A < 1, lo > hi or either NaN, or
+ * more elements than one grid (2^40). P == 0: DRPO_OK without a launch. */
+typedef struct {
+  int P, N, K, A;          /* start states, candidates per state, given steps, action dim */
+  float lo, hi;            /* the clamp of the drawn candidates */
+  uint64_t seed, ctr;
+  const float* mean;       /* [P][K][A], device */
+  const float* std;        /* [P][K][A] */
+  const float* incumbent;  /* [P][K][A] */
+  float* cand;             /* [P * N][K][A], out */
+} drpo_plan_sample_t;
+
+int drpo_plan_sample(const drpo_plan_sample_t* d /* host */, drpo_stream_t stream);
+
+/* drpo_plan_refit: scores and ranks the candidates of every start state and refits mean and
+ * std, on the trajectory-major tensors that the run of B = P * N rows (row r = p * N + n) and
+ * horizon H under cand left. One workgroup serves one start state.
+ * a. Score. score[r] is exactly value[r][H] of drpo_rollout_lookahead above (the critics'
+ *    training units of src/smbpo.py:260-270, the backup of src/ssac.py:284-294), and cert[r]
+ *    the maximum over c (a NaN stays) of its certificate[r][H][c]: at k = H a row's bootstrap
+ *    is its terminal one (kk = min(H, len_r) = len_r), so step_q / step_qc are not inputs.
+ *    The same ordered double operations, nothing contracted, lengths clamped to 0..H as read;
+ *    each rounded to float32 once, a NaN stored as 0x7FC00000.
+ * b. Order, on the float32 values as stored. A row is valid if neither its score nor its cert
+ *    is NaN, feasible if valid and cert <= threshold. A state's order: the feasible rows by
+ *    score descending, then the valid infeasible rows by cert ascending, then the invalid rows;
+ *    ties to the lower n. rank[r]: the row's position; n_feasible[p]; best[p]: n of rank 0.
+ * c. Elites. Ke = min(elites, n_feasible) if n_feasible > 0, else min(elites, n_valid); the
+ *    elites are the rows of rank < Ke. With key = score if the state has a feasible row, else
+ *    -cert, an elite's weight is w = exp(((double)key - (double)key_best) / temperature),
+ *    where the difference of equal keys is 0 (two infinities included) and temperature +inf
+ *    gives w = 1 exactly. Every other row has w = 0.
+ * d. Refit, per (t, a) of the K given steps, over the rows with w > 0 in the order n = 0..N-1,
+ *    in ordered double arithmetic (nothing contracted):
+ *      m = sum(w * x) / sum(w);  v = sum(w * ((x - m) * (x - m))) / sum(w),  x = cand[r][t][a]
+ *      mean_out = (1 - momentum) * m + momentum * mean_in
+ *      std_out = (1 - momentum) * sqrt(v) + momentum * std_in, raised to min_std if below it
+ *    stored as float32. With no valid row, or when sum(w) is not positive, mean_in and std_in
+ *    pass through; with no valid row best = 0. mean_out / std_out may alias their inputs.
+ * e. best_actions[p] = cand[p * N + best[p]], copied; best_score, best_cert, best_feasible.
+ * Every element of every given output is written; nothing else is. DRPO_EINVAL before any
+ * launch: a null descriptor, input or per-state output (violations may be NULL in mode 0), P < 0
+ * or P * N beyond int32, N outside 2..DRPO_PLAN_MAX_CANDIDATES, H outside
+ * 1..DRPO_ROLLOUT_FUSED_MAX_H, K outside 1..H, A < 1, C < 1, a mode other than 0 / 1, gamma not
+ * finite or outside [0, 1], elites outside 1..N, temperature not > 0 (+inf is allowed), momentum
+ * outside [0, 1), min_std negative or not finite, a NaN threshold. P == 0: DRPO_OK without a
+ * launch. */
+typedef struct {
+  int P, N, H, K, A, C, mode, elites;
+  double gamma;
+  double reward_scale, alive_bonus, constraint_scale, constraint_offset;
+  double temperature, momentum, min_std;
+  float threshold;
+  int pad_;
+  /* inputs, device, not written while the call runs (mean_in / std_in excepted, see d.) */
+  const float* rewards;            /* [B][H] */
+  const float* constraint_values;  /* [B][H][C]; required, though mode 1 does not read it */
+  const uint8_t* dones;            /* [B][H] */
+  const uint8_t* violations;       /* [B][H]; read in mode 1 only, may be NULL in mode 0 */
+  const int32_t* lengths;          /* [B]; clamped to 0..H as read */
+  const uint8_t* terminated;       /* [B] */
+  const double* weights;           /* [H + 1]: gamma^k */
+  const float* terminal_q;         /* [B] */
+  const float* terminal_qc;        /* [B][C] */
+  const float* cand;               /* [B][K][A] */
+  const float* mean_in;            /* [P][K][A] */
+  const float* std_in;             /* [P][K][A] */
+  /* outputs, device */
+  float* mean_out;                 /* [P][K][A] */
+  float* std_out;                  /* [P][K][A] */
+  float* best_actions;             /* [P][K][A] */
+  int32_t* best;                   /* [P] */
+  int32_t* n_feasible;             /* [P] */
+  float* best_score;               /* [P] */
+  float* best_cert;                /* [P] */
+  uint8_t* best_feasible;          /* [P] */
+  /* per row; each may be NULL */
+  float* score;                    /* [B] */
+  float* cert;                     /* [B] */
+  int32_t* rank;                   /* [B] */
+  float* weight;                   /* [B]: w rounded to float32 */
+} drpo_plan_refit_t;
+
+int drpo_plan_refit(const drpo_plan_refit_t* d /* host */, drpo_stream_t stream);
 
 /* batched env constraint functions, e.g. PointRobot.get_constraint_values /
  * check_violation / check_done (src/env/point_robot.py:96-131); h is [n][C] */
