@@ -175,6 +175,8 @@ PROTOTYPES = {
                                                    P]),
     'drpo_rollout_trajectories_linear': (c_int, [POINTER(RolloutDesc), POINTER(RolloutShield), POINTER(RolloutLinear),
                                                  POINTER(RolloutTraj), P]),
+    'drpo_rollout_trajectories_proposed': (c_int, [POINTER(RolloutDesc), POINTER(RolloutGiven), POINTER(RolloutShield),
+                                                   POINTER(RolloutLinear), POINTER(RolloutTraj), P]),
     'drpo_rollout_stage': (c_int, [POINTER(RolloutDesc), P]),
     'drpo_rollout_emit_cut': (c_int, [POINTER(RolloutDesc), POINTER(RolloutCut), P]),
     'drpo_rollout_trajectories_cut': (c_int, [POINTER(RolloutDesc), POINTER(RolloutCut), POINTER(RolloutTraj), P]),

@@ -772,6 +772,12 @@ constexpr int PERSIST_L2_LDS = 3;
 // certificate fails try the blends j = 1 .. K-2 between the two actions one certificate
 // pass each, closest to the policy's first, and take the first that passes or, at K-1,
 // the safe action. The passes end as soon as no alive row of the tile is undecided.
+// GA && SH: the shield judges the given actions (drpo_rollout_trajectories_proposed). At a
+// step t < n_given the given action is the proposal: it is in act / xin before the shield's
+// first barrier as the actor's sample is at any other step, and everything behind that
+// barrier is the SH step unchanged (certificate of the proposal, decision, safe actor,
+// select or blend). Steps t >= n_given are the SH kernel's steps. With n_given == H the
+// host leaves LW off, and the safe actor streams from its packed mirrors as it always does.
 template <int RB, int NW, bool LW, int PM, bool PG = false, bool GA = false, bool SH = false>
 __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p) {
   constexpr int ROWS = RB * 16;
@@ -941,7 +947,9 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
         // ---- the shield (src/smbpo.py:124-136) on [s_raw, a]: xin's states are still raw.
         //      All weights streamed from the packed mirrors; h1 / h2 / h3, dout / lout and
         //      red are free between the actor and the member ----
-        lds_barrier();   // act / xin[.., S + d] of every row; the sampling threads are done with red
+        // act / xin[.., S + d] of every row (GA: at a given step the proposal, written above by
+        // the same tid < ROWS * A threads); the sampling threads are done with red
+        lds_barrier();
         const int Hc = PARG(Hc), Cq = PARG(Cq);
         const bool dist = PARG(sh_dist) != 0;
         // LK candidates (0: the threshold shield, one pass). Pass j scores candidate j of the
@@ -1034,7 +1042,8 @@ __global__ __launch_bounds__(NW * 64) void rollout_persist_kernel(PersistArgs p)
               const float a = fast_tanh(narrow_sum<NW, RB>(red, r, d) + bmu);
               if (LK) {
                 // linear: both ends of the blend stay in LDS for the passes to come (read
-                // back below by the thread that writes them)
+                // back below by the thread that writes them). GA: at a given step the
+                // policy's end is the proposal
                 float* ab = smem + PARG(sh_ab);
                 ab[r * 8 + d] = act[r * 8 + d];
                 ab[ROWS * 8 + r * 8 + d] = a;
@@ -1694,20 +1703,23 @@ static void launch_persist_ga(bool paired, bool pg, const PersistArgs& a, size_t
   k<<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
 }
 
-// the shield instantiations (GA = false: given actions and the shield do not combine)
-template <int RB, bool LW>
+// the shield instantiations (GA: the shield judges the given actions of the first steps,
+// drpo_rollout_trajectories_proposed)
+template <int RB, bool LW, bool GA>
 static void launch_persist_sh(bool paired, bool pg, const PersistArgs& a, size_t lds_bytes, hipStream_t stream) {
-  auto k = paired ? (pg ? rollout_persist_kernel<RB, 8, LW, 1, true, false, true>
-                        : rollout_persist_kernel<RB, 8, LW, 1, false, false, true>)
-                  : (pg ? rollout_persist_kernel<RB, 8, LW, 0, true, false, true>
-                        : rollout_persist_kernel<RB, 8, LW, 0, false, false, true>);
+  auto k = paired ? (pg ? rollout_persist_kernel<RB, 8, LW, 1, true, GA, true>
+                        : rollout_persist_kernel<RB, 8, LW, 1, false, GA, true>)
+                  : (pg ? rollout_persist_kernel<RB, 8, LW, 0, true, GA, true>
+                        : rollout_persist_kernel<RB, 8, LW, 0, false, GA, true>);
   k<<<a.ntiles, 8 * 64, lds_bytes, stream>>>(a);
 }
 
-// a.cW1: the shield instantiations; a.n_given > 0: the given-actions instantiations
+// a.cW1: the shield instantiations; a.n_given > 0: the given-actions instantiations; both:
+// their product
 template <int RB, bool LW>
 static void launch_persist(bool paired, bool pg, const PersistArgs& a, size_t lds_bytes, hipStream_t stream) {
-  if (a.cW1) launch_persist_sh<RB, LW>(paired, pg, a, lds_bytes, stream);
+  if (a.cW1 && a.n_given > 0) launch_persist_sh<RB, LW, true>(paired, pg, a, lds_bytes, stream);
+  else if (a.cW1) launch_persist_sh<RB, LW, false>(paired, pg, a, lds_bytes, stream);
   else if (a.n_given > 0) launch_persist_ga<RB, LW, true>(paired, pg, a, lds_bytes, stream);
   else launch_persist_ga<RB, LW, false>(paired, pg, a, lds_bytes, stream);
 }
@@ -1716,7 +1728,8 @@ static void launch_persist(bool paired, bool pg, const PersistArgs& a, size_t ld
 // Fills `a`, which the tails read too. self_emit: the kernel copies the buffer pointer for
 // rollout_emit_self_kernel; without it the kernel touches neither the buffer nor its pointer.
 // given: actions for the first given->steps steps (nullptr or steps == 0: none).
-// shield: the safety shield inside the step (checked by the caller; not together with given).
+// shield: the safety shield inside the step (checked by the caller). With given, the shield
+// judges the given actions too (the GA && SH instantiations).
 // linear: the shield is the linear one (with shield only; checked by the caller).
 static int persist_run(const drpo_rollout_desc_t* d, const RolloutWs& w, int rpt, int64_t rlen, bool self_emit,
                        const char* who, hipStream_t stream, PersistArgs& a,
@@ -2015,6 +2028,20 @@ DRPO_API int drpo_rollout_trajectories_linear(const drpo_rollout_desc_t* d, cons
                                               const drpo_rollout_linear_t* linear, const drpo_rollout_traj_t* out,
                                               drpo_stream_t stream) {
   return rollout_trajectories(d, nullptr, shield, linear, out, "drpo_rollout_trajectories_linear", (hipStream_t)stream);
+}
+
+// Given actions as proposals: the shield (either one) judges the first given->steps steps'
+// given actions as it judges the actor's samples (the GA && SH instantiations). Without
+// given actions or without a shield the call is one of the four above, and refused here.
+DRPO_API int drpo_rollout_trajectories_proposed(const drpo_rollout_desc_t* d, const drpo_rollout_given_t* given,
+                                                const drpo_rollout_shield_t* shield,
+                                                const drpo_rollout_linear_t* linear, const drpo_rollout_traj_t* out,
+                                                drpo_stream_t stream) {
+  const char* who = "drpo_rollout_trajectories_proposed";
+  DRPO_REQUIRE(given && given->steps != 0, "%s: no given actions (NULL or steps == 0): without proposals the call "
+               "is drpo_rollout_trajectories_shielded / _linear", who);
+  DRPO_REQUIRE(shield, "%s: null shield: without one the call is drpo_rollout_trajectories_given", who);
+  return rollout_trajectories(d, given, shield, linear, out, who, (hipStream_t)stream);
 }
 
 // ---- halting: stage, then cut + emit; or cut + the trajectory tail ------------------

@@ -351,7 +351,10 @@ class ImaginedRollout:
 
     Everything at or beyond a row's length is zero. ``members`` is the ensemble member
     of each step. members='each' stacks the runs on a new leading axis. ``given_steps``:
-    the leading steps whose actions the caller gave (0: every action is the policy's).
+    the leading steps whose actions the caller gave (0: every action is the policy's),
+    executed as given (imagine(actions=)) or proposed to the shield (imagine(proposals=):
+    ``actions`` then holds what the shield let the row execute, ``certificate`` at those steps
+    the proposal's).
 
     Under the shield (imagine(shield=)) three attributes are set, None otherwise:
       interventions [B, H] bool  the step took the safe actor's action
@@ -508,6 +511,23 @@ def _shield_request(alg, noise, actions, shield, candidates, uncertainty):
     return float(shield), None if candidates is None else int(candidates), bool(uncertainty)
 
 
+def _proposal_request(noise, actions, proposals, shield):
+    """Every refusal of rollout_trajectories' ``proposals`` (its docstring), before anything
+    touches a device. Returns whether the call is the proposals form."""
+    if proposals is None:
+        return False
+    if actions is not None:
+        raise ValueError('proposals with actions: a leading step is either executed as given (actions=) or '
+                         'proposed to the shield (proposals=), not both')
+    if shield is None:
+        raise ValueError('proposals without shield: a proposal is what the shield judges; actions= executes the '
+                         'given actions as they are')
+    if noise.parity:
+        raise ValueError('proposals with a recorded tape: a tape fixes the policy\'s draws, and the reference '
+                         'rollout it records has no shield')
+    return True
+
+
 def _shield_desc(alg, policy, B, H, threshold, dist):
     """drpo_rollout_shield_t of alg's shield: alg.actor_safe, alg.constraint_critic (dist:
     its distributional bound; False: its mean, the log-std head left out), fresh [B, H]
@@ -545,22 +565,23 @@ def _shield_desc(alg, policy, B, H, threshold, dist):
     return sh, keep
 
 
-def _given_actions(actions, B, H, A):
-    """rollout_trajectories' ``actions`` checked. Returns (actions [B, K, A] or None, K; 0 without)."""
+def _given_actions(actions, B, H, A, name='actions'):
+    """rollout_trajectories' ``actions`` (or, under ``name``, its ``proposals``) checked. Returns
+    (actions [B, K, A] or None, K; 0 without)."""
     if actions is None:
         return None, 0
     if not torch.is_tensor(actions) or actions.dtype != torch.float32 or not actions.is_contiguous():
-        raise ValueError('actions: a contiguous float32 tensor [B, K, A] (or [B, A])')
+        raise ValueError(f'{name}: a contiguous float32 tensor [B, K, A] (or [B, A])')
     _lib.require_device(actions)
     if actions.dim() == 2:
         actions = actions.unsqueeze(1)
     if actions.dim() != 3 or actions.shape[2] != A:
-        raise ValueError(f'actions: shape {tuple(actions.shape)} is not [B, K, {A}]')
+        raise ValueError(f'{name}: shape {tuple(actions.shape)} is not [B, K, {A}]')
     if actions.shape[0] != B:
-        raise ValueError(f'actions: {actions.shape[0]} rows for {B} trajectories')
+        raise ValueError(f'{name}: {actions.shape[0]} rows for {B} trajectories')
     K = actions.shape[1]
     if not 1 <= K <= H:
-        raise ValueError(f'actions: {K} given steps, need 1 <= K <= horizon {H}')
+        raise ValueError(f'{name}: {K} given steps, need 1 <= K <= horizon {H}')
     return actions, K
 
 
@@ -584,7 +605,7 @@ def _traj_outputs(out, spec, dev):
 
 def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, eps_a=None, eps_m=None, eps_layout=1,
                          weights=None, out=None, horizon=None, ctr=None, actions=None, timer=None, shield=None,
-                         shield_candidates=None, shield_uncertainty=None):
+                         shield_candidates=None, shield_uncertainty=None, proposals=None):
     """One imagined rollout (src/smbpo.py:229-249) kept per trajectory: the fused horizon
     kernel and the trajectory tail (drpo_rollout_trajectories). Never touches
     alg.virt_buffer. Mirrors ``rollout``: the same start states, members and draws for
@@ -619,7 +640,16 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
     if none is. The result carries blend and shield_candidates too.
     shield_uncertainty: whether the certificate is the critic's distributional bound.
     Default: solver.distributional_qc for the threshold shield, False for the linear one
-    (the evaluation scores its candidates by the mean). True needs a distributional critic."""
+    (the evaluation scores its candidates by the mean). True needs a distributional critic.
+
+    proposals: ``actions``' shape and checks, with ``shield`` (either one): steps 0 .. K-1 of
+    trajectory i propose proposals[i, t] to the shield in place of the policy's sample, as
+    _shielded_action passes a proposed action through the certificate, and take what the
+    shield lets through (drpo_rollout_trajectories_proposed): the proposal, or the safe
+    actor's action (the linear shield: the first passing blend between the two). The result's
+    ``actions`` are the executed ones, ``certificate`` at a given step is the proposal's,
+    ``given_steps`` is K. No draw is made or moved. Not with ``actions``, without ``shield``
+    (that is ``actions``) or with a recorded tape."""
     from ._abi import RolloutGiven, RolloutLinear, RolloutTraj
     dev = alg.device
     H = alg.horizon if horizon is None else int(horizon)
@@ -629,13 +659,14 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
     # the requests, checked
     if actions is not None and noise.parity:
         raise ValueError('actions with a recorded tape: a tape fixes the policy\'s draws')
+    proposed = _proposal_request(noise, actions, proposals, shield)
     request = _shield_request(alg, noise, actions, shield, shield_candidates, shield_uncertainty)
     _lib.require_device(policy.group.data, model.group.data, initial_states)
 
     # inputs (the noise object is consumed here, in _members_and_draws' order)
     start = _start_states(alg, initial_states, noise, dev)
     B = start[-1]
-    actions, K = _given_actions(actions, B, H, A)
+    actions, K = _given_actions(proposals, B, H, A, 'proposals') if proposed else _given_actions(actions, B, H, A)
     _lib.require_device(eps_a, eps_m)
     mem, _, eps_a, eps_m = _members_and_draws(model, noise, H, B, A, S + 1, dev, members, eps_a, eps_m)
     ctr = noise.next() if ctr is None else ctr
@@ -675,10 +706,13 @@ def rollout_trajectories(alg, policy, initial_states, noise, *, members=None, ep
             lin.candidates, lin.blend = candidates, blend.data_ptr()
             im.set_group('linear', blend=blend, shield_candidates=candidates)
             entry, extra = 'rollout_trajectories_linear', (sh, lin)
+        if proposed:      # (NULL linear: the threshold shield)
+            entry, extra = 'rollout_trajectories_proposed', (given, sh, lin if candidates is not None else None)
 
     # launch
     launch = getattr(_lib.lib(), 'drpo_' + entry)
-    _lib.check(launch(ctypes.byref(d), *map(ctypes.byref, extra), ctypes.byref(t), _lib.stream()), entry)
+    _lib.check(launch(ctypes.byref(d), *(None if x is None else ctypes.byref(x) for x in extra), ctypes.byref(t),
+                      _lib.stream()), entry)
     return im
 
 
@@ -858,14 +892,23 @@ class PlanResult:
       candidates [P, N, K, A]; scores, certificates [P, N]; ranks [P, N] int32 (0 the best)
       imagined                   the ImaginedRollout of its P * N rows (row p * N + n)
     ``threshold`` is the certificate threshold as compared (float32), ``lookahead_kind`` 'mean'
-    or 'bound'."""
+    or 'bound'.
+
+    Under plan(safety_filter=) every candidate ran behind the shield, and ``actions`` /
+    ``action`` stay the proposals. Four more, None otherwise, of the best row:
+      executed_actions [P, H, A] what the shield let it execute (all H steps of its trajectory)
+      safe_action [P, A]         executed_actions[:, 0], the action to hand to the environment
+      interventions [P, H] bool  the steps at which the shield stepped in
+      filter_threshold           the shield's threshold, as imagine's shield_threshold"""
     FIELDS = ('actions', 'action', 'score', 'certificate', 'feasible', 'n_feasible', 'mean', 'std', 'history_score',
               'history_certificate', 'history_feasible', 'candidates', 'scores', 'certificates', 'ranks', 'imagined',
               'threshold', 'lookahead_kind')
+    FILTER_FIELDS = ('executed_actions', 'safe_action', 'interventions', 'filter_threshold')
 
-    def __init__(self, **fields):
+    def __init__(self, executed_actions=None, safe_action=None, interventions=None, filter_threshold=None, **fields):
         assert set(fields) == set(self.FIELDS), sorted(set(fields) ^ set(self.FIELDS))
-        self.__dict__.update(fields)
+        self.__dict__.update(fields, executed_actions=executed_actions, safe_action=safe_action,
+                             interventions=interventions, filter_threshold=filter_threshold)
 
 
 def plan_sample(mean, std, incumbent, candidates, seed, ctr, lo=-1.0, hi=1.0):

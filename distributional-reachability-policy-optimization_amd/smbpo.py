@@ -265,7 +265,7 @@ class SMBPO(Configurable, Module):
 
     def imagine(self, states=None, policy=None, horizon=None, *, members=None, deterministic=False,
                 model_noise=True, discount=None, noise=None, actions=None, shield=None,
-                shield_uncertainty=None, uncertainty=None, halt=None, lookahead=None):
+                shield_uncertainty=None, uncertainty=None, halt=None, lookahead=None, proposals=None):
         """What the model predicts happens from ``states`` under ``policy``: the rollout of
         src/smbpo.py:229-249 kept per trajectory (ops.ImaginedRollout: row i of every tensor
         is the trajectory from start state i), on the fused horizon kernel. Nothing of the
@@ -291,6 +291,19 @@ class SMBPO(Configurable, Module):
                    policy acts from step K on, with the draws it would have had anyway.
                    With K = horizon the policy is never evaluated. The result's
                    ``given_steps`` is K.
+        proposals  ``actions``' shape, with ``shield`` in any of its spellings: "from this
+                   state, if THIS is what the controller proposes". Steps 0 .. K-1 of row i
+                   pass proposals[i, t] through the shield in place of the policy's sample,
+                   as _shielded_action passes a proposed action through the certificate, and
+                   execute what it lets through: the proposal, or actor_safe's mean action
+                   (the linear shield: the first passing blend between the two, blend 0 the
+                   proposal). The shielded policy acts from step K on. The result's
+                   ``actions`` are the executed ones, ``certificate`` at a given step is the
+                   proposal's, ``interventions`` / ``blend`` say where the shield stepped
+                   in, ``given_steps`` is K. As draw-free as its parents: at threshold inf
+                   the run is imagine(actions=)'s, and from the policy's own sample at
+                   K = 1 it is imagine(shield=)'s. Not with ``actions``, without ``shield``
+                   (that is ``actions``) or with a recorded tape (ValueError).
         shield     None / False: the policy alone. True: the controller that drives the real
                    environment, the policy behind the safety shield (_shielded_action,
                    src/smbpo.py:124-136) at self.safe_shield_threshold; a float: at that
@@ -383,12 +396,16 @@ class SMBPO(Configurable, Module):
         B = self.rollout_batch_size if states is None else len(states)
         if actions is not None:
             actions = torch.as_tensor(actions, dtype=torch.float32).to(self.device).contiguous()
+        if proposals is not None:
+            proposals = torch.as_tensor(proposals, dtype=torch.float32).to(self.device).contiguous()
 
         each = isinstance(members, str)
         if each and members != 'each':
             raise ValueError(f"members: {members!r} (None, an int, {H} ints or 'each')")
         # the shield's shorthand as ops' threshold and candidates; ops._shield_request refuses and defaults
         kw = {'actions': actions, 'shield_uncertainty': shield_uncertainty}
+        if proposals is not None:     # (off: ops sees the call it saw before)
+            kw['proposals'] = proposals
         if isinstance(shield, (str, tuple, list)):
             from .sampling import LINEAR_SHIELD_CANDIDATES
             kind, thr, K = (shield, None, None) if isinstance(shield, str) else (tuple(shield) + (None,) * 3)[:3]
@@ -446,7 +463,8 @@ class SMBPO(Configurable, Module):
 
     def plan(self, states, horizon=None, *, candidates=64, iterations=4, steps=None, elites=None,
              temperature=float('inf'), momentum=0.0, init=None, init_std=0.5, min_std=0.05, threshold=None,
-             lookahead=True, policy=None, members=None, model_noise=False, discount=None, noise=None):
+             lookahead=True, policy=None, members=None, model_noise=False, discount=None, noise=None,
+             safety_filter=None):
         """The best of sampled action sequences from each of the P ``states``, by the model and the
         two critics: an MPPI / CEM planner whose score is imagine(actions=, lookahead=)'s
         value_lookahead[:, H] and whose constraint is its certificate_lookahead[:, H] (the
@@ -481,9 +499,24 @@ class SMBPO(Configurable, Module):
                      not comparable; an int or H ints fix the model. Not 'each'.
         noise        default a stream private to plan, derived from the trainer's seed. Each
                      sample launch takes one noise.next(), and imagine runs on the same object.
+        safety_filter   None / False: the candidates are executed as given, as above. Else the
+                     shield of the real controller runs inside the planner, safe MPC: every
+                     iteration's run is imagine(proposals=candidates, shield=...), so a
+                     candidate is scored and ranked on the trajectory the shield would let it
+                     run, and from step K on the shielded policy continues the row. True: the
+                     threshold shield at self.safe_shield_threshold; a float: at that
+                     threshold; 'linear', ('linear', thr) or ('linear', thr, K): the linear
+                     shield, as imagine's ``shield``. The refit, ``mean`` / ``std`` and the
+                     incumbent stay over the proposals (a trajectory is a function of the
+                     state and the proposals once the model is fixed, so the incumbent's key
+                     still never decreases), and ``actions`` / ``action`` of the result are
+                     proposals. The result carries ``executed_actions``, ``safe_action``
+                     (the filtered first action, the one to hand to the environment),
+                     ``interventions`` and ``filter_threshold`` of the best row. Independent
+                     of ``threshold``, the planner's constraint on the unrolled certificate.
         Not with a recorded tape; NotImplementedError for an env without device constraint
-        functions, as imagine. halt= / shield= inside the planner, time-correlated noise and a
-        shifted warm start are not built."""
+        functions, as imagine. halt= inside the planner, time-correlated noise and a shifted
+        warm start are not built."""
         from . import ops
         from .rng import _mix64
         if self.env_params is None:
@@ -527,6 +560,24 @@ class SMBPO(Configurable, Module):
             raise ValueError(f"members: {members!r} (None, an int or {H} ints; 'each' is not for plan)")
         if noise is not None and noise.parity:
             raise ValueError('plan with a recorded tape: a tape fixes the draws of one rollout, not of a planner')
+        # the filter as imagine's ``shield`` (None: off), every spelling checked here
+        filt = None if safety_filter is None or safety_filter is False else safety_filter
+        if isinstance(filt, (str, tuple, list)):
+            kind, thr, cands = (filt, None, None) if isinstance(filt, str) else (tuple(filt) + (None,) * 3)[:3]
+            if kind != 'linear' or (not isinstance(filt, str) and not 1 <= len(filt) <= 3) or \
+                    not (thr is None or is_num(thr) and thr == thr) or \
+                    not (cands is None or is_int(cands) and 2 <= cands <= 32):
+                raise ValueError(f"safety_filter: {safety_filter!r} (None, True, a threshold, 'linear', ('linear', "
+                                 "threshold) or ('linear', threshold, candidates 2..32))")
+            filt = ('linear', float(self.safe_shield_threshold if thr is None else thr)) + \
+                (() if cands is None else (int(cands),))
+        elif filt is True:
+            filt = float(self.safe_shield_threshold)
+        elif filt is not None:
+            if not (is_num(filt) and filt == filt):
+                raise ValueError(f'safety_filter: {safety_filter!r} (None, True, a threshold (-inf and inf are '
+                                 "allowed, NaN is not) or 'linear')")
+            filt = float(filt)
         if states is None:
             raise ValueError('plan needs start states')
         states = torch.as_tensor(states, dtype=torch.float32).reshape(-1, self.state_dim)
@@ -561,14 +612,25 @@ class SMBPO(Configurable, Module):
         history = []
         for _ in range(iterations):
             cand = ops.plan_sample(mean, std, incumbent, N, noise.seed, noise.next())
-            im = self.imagine(tiled, policy, H, actions=cand, **run)
+            if filt is None:
+                im = self.imagine(tiled, policy, H, actions=cand, **run)
+            else:     # the candidates as proposals: scored on what the shield lets them run
+                im = self.imagine(tiled, policy, H, proposals=cand, shield=filt, **run)
             terminal_q, terminal_qc = ops._terminal_critics(self, policy, im, look)
             fit = ops.plan_refit(self, im, terminal_q, terminal_qc, cand, mean, std, gamma, candidates=N,
                                  threshold=threshold, elites=elites, temperature=temperature, momentum=momentum,
                                  min_std=min_std)
             mean, std, incumbent = fit['mean'], fit['std'], fit['best_actions']
             history.append((fit['best_score'], fit['best_cert'], fit['best_feasible']))
+        filtered = {}
+        if filt is not None:
+            # the best row's filtered trajectory, gathered on the device (row p * N + best[p])
+            rows = torch.arange(P, device=dev, dtype=torch.int64) * N + fit['best'].to(torch.int64)
+            executed = im.actions.index_select(0, rows)
+            filtered = dict(executed_actions=executed, safe_action=executed[:, 0],
+                            interventions=im.interventions.index_select(0, rows), filter_threshold=im.shield_threshold)
         return ops.PlanResult(
+            **filtered,
             actions=incumbent, action=incumbent[:, 0], score=fit['best_score'], certificate=fit['best_cert'],
             feasible=fit['best_feasible'], n_feasible=fit['n_feasible'], mean=mean, std=std,
             history_score=torch.stack([h[0] for h in history]),

@@ -277,6 +277,32 @@ int drpo_rollout_trajectories_linear(const drpo_rollout_desc_t* d /* host */,
                                      const drpo_rollout_linear_t* linear /* host; NULL: the threshold shield */,
                                      const drpo_rollout_traj_t* out /* host */, drpo_stream_t stream);
 
+/* The imagined rollout under the shielded controller from proposed actions: "what would the
+ * controller execute if this is what is proposed". SMBPO._shielded_action (src/smbpo.py:124-136)
+ * passes a proposed action through the certificate before the environment sees it; here the
+ * proposal of steps t < given->steps of trajectory i is given->actions[i][t] in place of the
+ * actor's sample, and the shield of the step is the one of the two calls above: the
+ * threshold shield (linear == NULL), or the linear shield (src/sampling.py:430-437), whose
+ * blend j = 0 is then the proposal. Steps t >= given->steps are those calls' steps.
+ *   - Everything of drpo_rollout_trajectories_given and of drpo_rollout_trajectories_shielded
+ *     (linear != NULL: of drpo_rollout_trajectories_linear) holds: their descriptors, outputs
+ *     and checks. given == NULL, given->steps == 0 or shield == NULL are those calls and are
+ *     refused here: DRPO_EINVAL before any launch or memset.
+ *   - drpo_rollout_traj_t.actions holds the executed actions: the proposal where the shield
+ *     let it pass, else the safe actor's (or the blend's). A proposal is judged as given,
+ *     neither clamped nor squashed.
+ *   - At a step t < given->steps shield->certificate is the certificate of the proposal,
+ *     shield->interventions and linear->blend mean what they mean in the calls above.
+ *   - No draw is made or moved: a given step makes no action draw and shifts no other, the
+ *     shield draws nothing. At threshold +inf the call computes what
+ *     drpo_rollout_trajectories_given computes; with given->steps == H the actor is never
+ *     evaluated, the safe actor only in tiles with an intervening row. */
+int drpo_rollout_trajectories_proposed(const drpo_rollout_desc_t* d /* host */,
+                                       const drpo_rollout_given_t* given /* host; steps >= 1 */,
+                                       const drpo_rollout_shield_t* shield /* host */,
+                                       const drpo_rollout_linear_t* linear /* host; NULL: the threshold shield */,
+                                       const drpo_rollout_traj_t* out /* host */, drpo_stream_t stream);
+
 /* Halting the imagined rollout (src/smbpo.py:229-249) where a per-step score says the
  * model should not be trusted. The reference has a fixed horizon and no counterpart. With
  * score[i][t] = scores[i * row_stride + t * step_stride] and len_i the row's natural length:
@@ -318,7 +344,7 @@ int drpo_rollout_emit_cut(const drpo_rollout_desc_t* d /* host */, const drpo_ro
                           drpo_stream_t stream);
 
 /* The trajectory tail (src/smbpo.py:229-249 per trajectory) again under a cut, on the
- * staging of the preceding drpo_rollout_trajectories* call in any of its four forms:
+ * staging of the preceding drpo_rollout_trajectories* call in any of its five forms:
  * rewrites every output given as drpo_rollout_trajectories defines it with len[i] the new
  * length, 0..H. A halted row's terminated is 0 and its first_violation -1 unless it lies
  * before the cut; ret sums the kept steps in the same double order. A row of length 0:
