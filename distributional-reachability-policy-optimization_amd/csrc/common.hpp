@@ -1195,7 +1195,7 @@ __device__ __forceinline__ void tile_dense_catk(const float* in1, const float* i
 }
 
 // Which head (bit 2) and which base block (bits 0-1) a wave of an 8-wave workgroup runs in
-// the paired 200-wide heads (rollout.hip pair_split_heads, fit.hip's heads phase): the diff
+// the paired 200-wide heads (rollout_persist.hpp pair_split_heads, fit.hip's heads phase): the diff
 // head on waves 0, 1, 2, 7 (bases 0, 1, 2, 3), the log-var head on waves 3-6 (bases 0-3).
 // Base 0 owns 4 of the 13 blocks, so SIMD 0 (waves 0 / 4) and SIMD 3 (waves 3 / 7) carry 7
 // blocks each, the older wave the 4-block one on both. The round-5 map (head by wave half,

@@ -167,7 +167,7 @@ __device__ __forceinline__ void ff_bias2(const float* __restrict__ bias, int N, 
   }
 }
 
-// the heads phase (rollout.hip pair_split_core's schedule): a wave owns blocks base,
+// the heads phase (rollout_persist.hpp pair_split_core's schedule): a wave owns blocks base,
 // base + 4, ... (3-4) of its head's hidden layer, then its split-K share of the head's
 // output layer from exactly those columns. Ring, output-layer fragments and biases are
 // preloaded for 4 blocks (a 4th past the layer clamped and unused).

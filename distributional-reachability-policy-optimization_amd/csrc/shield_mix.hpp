@@ -1,5 +1,5 @@
 // The linear shield's candidate action (src/sampling.py:430-434), one definition for
-// drpo_shield_mix (shield.hip) and the shield inside the fused rollout (rollout.hip).
+// drpo_shield_mix (shield.hip) and the shield inside the fused rollout (rollout_persist.hpp).
 #pragma once
 
 namespace drpo {

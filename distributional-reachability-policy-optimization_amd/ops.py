@@ -497,8 +497,8 @@ def _shield_request(alg, noise, actions, shield, candidates, uncertainty):
             raise ValueError('shield_candidates / shield_uncertainty without shield')
         return None
     if actions is not None:
-        raise ValueError('shield with actions: a given action is taken as it is (the shielded given-actions '
-                         'kernels are not built)')
+        raise ValueError('shield with actions: a given action is taken as it is (to have the shield judge '
+                         'given actions, pass them as proposals=)')
     if noise.parity:
         raise ValueError('shield with a recorded tape: the reference rollout a tape records has no shield')
     if candidates is not None and not (isinstance(candidates, (int, np.integer)) and
