@@ -155,6 +155,15 @@ struct OptimArgs {
 };
 static_assert(sizeof(OptimArgs) <= 4096, "optimizer kernarg");
 
+// x[i] for a per-lane i, by bit masks (a select chain is turned back into an indexed
+// private array, i.e. scratch memory)
+__device__ __forceinline__ float pick4(const float (&x)[4], int i) {
+  unsigned r = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) r |= __float_as_uint(x[k]) & (0u - (unsigned)(i == k));
+  return __uint_as_float(r);
+}
+
 // Packed-mirror refresh for the n (<= 4) consecutive flat elements i0.. of one thread.
 // The weight matrix holding i0 is found once; the (member, row, column) coordinates
 // are divided out once and then stepped (consecutive elements are consecutive
@@ -164,34 +173,53 @@ static_assert(sizeof(OptimArgs) <= 4096, "optimizer kernarg");
 __device__ __forceinline__ void pack_write4(const drpo_pack_map_t* mp, int64_t i0, int n, const float (&pv)[4],
                                             const float (&tv)[4], bool has_t) {
   const int nl = mp->nlayers;
-  int l = 0;
-  int64_t rel64 = 0;
-  for (; l < nl; ++l) {
-    rel64 = i0 - mp->off[l];
-    if (rel64 >= 0 && rel64 < (int64_t)mp->din[l] * mp->dout[l] * mp->nbatch[l]) break;
-  }
-  if (l == nl) return;
-  const int din = mp->din[l], dout = mp->dout[l], nb = mp->nbatch[l];
-  const int msz = din * dout;                         // group tensors are < 2^31 floats
-  const int rel = (int)rel64;
-  int z = rel / msz;
-  const int w = rel - z * msz;
-  int o = w / din, k = w - o * din;
-  const int ncb = pack_frags(dout), nks = pack_frags(din);
   float* P = mp->P;
   float* Pt = has_t ? mp->Pt : nullptr;
   float* PT = mp->PT;
-  for (int e = 0; e < n; ++e) {
-    const int64_t base = pack_member_base(mp->poff[l], z, ncb, nks);
-    const int64_t pi = base + pack_fwd_index(o, k, nks);
-    if (P) P[pi] = pv[e];
-    if (Pt) Pt[pi] = tv[e];
-    if (PT) PT[base + pack_tr_index(o, k, ncb)] = pv[e];
-    if (++k == din) {
-      k = 0;
-      if (++o == dout) {
-        o = 0;
-        if (++z == nb) return;
+  // A run need not lie in one matrix: a flat range may begin at any offset (the end of a
+  // matrix whose size is no multiple of 4, a segment's own start), so the run can begin
+  // in the vector before a matrix, or leave one matrix and enter the next. Each pass
+  // takes the matrix holding element e, or skips to the nearest one starting inside the run.
+  int e = 0;
+  while (e < n) {
+    const int64_t i = i0 + e;
+    int l = 0, ln = -1;
+    int64_t rel64 = 0, gap = n - e;
+    for (; l < nl; ++l) {
+      rel64 = i - mp->off[l];
+      const int64_t sz = (int64_t)mp->din[l] * mp->dout[l] * mp->nbatch[l];
+      if (rel64 >= 0 && rel64 < sz) break;
+      if (sz > 0 && rel64 < 0 && -rel64 < gap) {
+        gap = -rel64;
+        ln = l;
+      }
+    }
+    if (l == nl) {
+      if (ln < 0) return;
+      l = ln;
+      e += (int)gap;
+      rel64 = 0;
+    }
+    const int din = mp->din[l], dout = mp->dout[l], nb = mp->nbatch[l];
+    const int msz = din * dout;                         // group tensors are < 2^31 floats
+    const int rel = (int)rel64;
+    int z = rel / msz;
+    const int w = rel - z * msz;
+    int o = w / din, k = w - o * din;
+    const int ncb = pack_frags(dout), nks = pack_frags(din);
+    for (bool in = true; in && e < n; ++e) {
+      const int64_t base = pack_member_base(mp->poff[l], z, ncb, nks);
+      const int64_t pi = base + pack_fwd_index(o, k, nks);
+      const float pe = pick4(pv, e);
+      if (P) P[pi] = pe;
+      if (Pt) Pt[pi] = pick4(tv, e);
+      if (PT) PT[base + pack_tr_index(o, k, ncb)] = pe;
+      if (++k == din) {
+        k = 0;
+        if (++o == dout) {
+          o = 0;
+          in = ++z < nb;
+        }
       }
     }
   }
@@ -200,15 +228,6 @@ __device__ __forceinline__ void pack_write4(const drpo_pack_map_t* mp, int64_t i
 // EMA of one target element (one explicit fma: both task kinds round alike)
 __device__ __forceinline__ float ema_elem(const drpo_optim_seg_t& S, float p, float t) {
   return fmaf(S.ema_rate, p, S.ema_keep * t);
-}
-
-// x[i] for a per-lane i, by bit masks (a select chain is turned back into an indexed
-// private array, i.e. scratch memory)
-__device__ __forceinline__ float pick4(const float (&x)[4], int i) {
-  unsigned r = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) r |= __float_as_uint(x[k]) & (0u - (unsigned)(i == k));
-  return __uint_as_float(r);
 }
 
 // One 4x4 block of a weight matrix per 4 adjacent lanes: lane rr = tid & 3 owns row

@@ -120,6 +120,47 @@ def test_fit_fb_refuses_shapes_outside_its_kernel(kw, what):
     assert _err().startswith('drpo_ens_fit_fb: needs the ensemble trunk'), (what, _err())
 
 
+def _full_list_segment():
+    """A segment over 16 matrices with a vector before, between and after them: 33 tasks as
+    4x4-block work, 31 once plan_segment (csrc/optim.hip) has turned the last matrix into a flat
+    range."""
+    mp = _abi.PackMap()
+    mp.nlayers, off = 16, 64
+    for l in range(16):
+        mp.off[l], mp.din[l], mp.dout[l], mp.nbatch[l], mp.poff[l] = off, 4, 4, 1, 256 * l
+        off += 64
+    mp.P = mp.PT = P
+    sg = _abi.OptimSeg()
+    sg.p = sg.g = sg.m = sg.v = sg.map = P
+    sg.start, sg.end, sg.adam, sg.bc2_sqrt, sg.grad_scale = 0, off, 1, 1.0, 1.0
+    sg.map_host = ctypes.addressof(mp)
+    return sg, mp
+
+
+def test_optim_step_refuses_what_its_task_list_cannot_hold():
+    """Two full segments still fit (31 tasks, then one flat task); the third does not: refused
+    before any launch, by name."""
+    segs = [_full_list_segment() for _ in range(3)]
+    arr = (_abi.OptimSeg * 3)(*[s for s, _ in segs])
+    assert _lib.lib().drpo_optim_step(arr, 3, None) == EINVAL
+    assert _err().startswith('drpo_optim_step: more than 32 tasks'), _err()
+    assert _lib.lib().drpo_optim_step(arr, 9, None) == EINVAL
+    assert _err().startswith('drpo_optim_step: at most 8 segments'), _err()
+
+
+@pytest.mark.parametrize('brk,what', [(dict(nsums=5), '0..4 sums'), (dict(part=0), 'sum 1'), (dict(out=0), 'sum 1'),
+                                      (dict(n=-1), 'sum 1')])
+def test_wgrad_sums_refuses_bad_sums(brk, what):
+    sums = (_abi.SumDesc * 5)()
+    for s in sums:
+        s.part, s.n, s.out = P, 3, P
+    nsums = brk.pop('nsums', 2)
+    for k, v in brk.items():
+        setattr(sums[1], k, v)
+    assert _lib.lib().drpo_mlp_wgrad_sums(None, 0, sums, nsums, None, 0, None) == EINVAL
+    assert _err().startswith('drpo_mlp_wgrad_sums: ' + what), _err()
+
+
 def test_loss_refuses_gD_without_gLVR():
     L = _lib.lib()
     up, red, out = _up(), _red(), _abi.EnsReduce()

@@ -21,6 +21,7 @@ import torch
 import drpo_amd  # noqa: F401
 from drpo_amd.optim import Adam, ema_segment, fused_step, grad_sumsq, grad_sumsq_multi
 from drpo_amd.params import FlatGroup
+from optim_reference import adam_ref, clip_coef_ref
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda')
@@ -74,13 +75,9 @@ def reference(g0, sc, clip, rng, ema):
     s0, s1 = rng
     p, gr, m, v = (g0[k].double().cpu().clone() for k in 'pgmv')
     gs = gr[s0:s1]
-    coef = 1.0
-    if clip:
-        coef = min(1.0, 0.5 / (float(gs.float().pow(2).sum()) ** 0.5 + 1e-6))
-    ge = gs * coef + 1e-4 * p[s0:s1]
-    m[s0:s1] = m[s0:s1] + (ge - m[s0:s1]) * (1 - 0.9)
-    v[s0:s1] = v[s0:s1] * 0.999 + (1 - 0.999) * ge * ge
-    p[s0:s1] = p[s0:s1] - sc[0] * (m[s0:s1] / (v[s0:s1].sqrt() / sc[1] + 1e-8))
+    coef = clip_coef_ref(float(gs.float().pow(2).sum()), 0.5) if clip else 1.0
+    p[s0:s1], m[s0:s1], v[s0:s1] = adam_ref(p[s0:s1], gs, m[s0:s1], v[s0:s1], sc[0], sc[1], (0.9, 0.999), 1e-8,
+                                            1e-4, coef=coef)
     t = None
     if ema:
         t = g0['t'].double().cpu().clone()
