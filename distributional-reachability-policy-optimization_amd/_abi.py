@@ -83,6 +83,18 @@ class PlanSample(ctypes.Structure):
                 ('seed', c_uint64), ('ctr', c_uint64), ('mean', P), ('std', P), ('incumbent', P), ('cand', P)]
 
 
+class PlanSampleAr(ctypes.Structure):
+    """drpo_plan_sample_ar_t"""
+    _fields_ = PlanSample._fields_ + [('corr', c_double), ('innov', c_double)]
+
+
+class PlanShift(ctypes.Structure):
+    """drpo_plan_shift_t"""
+    _fields_ = [('P', c_int), ('K', c_int), ('A', c_int), ('shift', c_int), ('fresh_std', c_float),
+                ('std_floor', c_float), ('mean', P), ('std', P), ('incumbent', P), ('reset', P), ('tail', P),
+                ('mean_out', P), ('std_out', P), ('incumbent_out', P)]
+
+
 class PlanRefit(ctypes.Structure):
     """drpo_plan_refit_t"""
     _fields_ = [('P', c_int), ('N', c_int), ('H', c_int), ('K', c_int), ('A', c_int), ('C', c_int), ('mode', c_int),
@@ -183,6 +195,8 @@ PROTOTYPES = {
     'drpo_rollout_staging_offsets': (c_int, [c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     'drpo_rollout_lookahead': (c_int, [POINTER(RolloutLookahead), P]),
     'drpo_plan_sample': (c_int, [POINTER(PlanSample), P]),
+    'drpo_plan_sample_ar': (c_int, [POINTER(PlanSampleAr), P]),
+    'drpo_plan_shift': (c_int, [POINTER(PlanShift), P]),
     'drpo_plan_refit': (c_int, [POINTER(PlanRefit), P]),
     'drpo_env_constraints': (c_int, [c_int, c_int, c_int, c_double, c_double, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_constraints_program': (c_int, [P, c_int, P, c_int64, c_int, P, P, P, P]),

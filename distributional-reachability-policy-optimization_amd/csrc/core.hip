@@ -19,7 +19,7 @@ void drpo_set_error(const char* fmt, ...) {
 
 DRPO_API const char* drpo_last_error(void) { return g_err; }
 
-DRPO_API int drpo_version(void) { return 14; }
+DRPO_API int drpo_version(void) { return 15; }
 
 // HIP event helpers so hosts without a HIP binding (ctypes/cgo/JNI) can time
 // individual kernels on the stream they run on. The events are timing-only: created
@@ -84,6 +84,7 @@ DRPO_API int64_t drpo_abi_sizeof(const char* name) {
       {"drpo_rollout_linear_t", sizeof(drpo_rollout_linear_t)}, {"drpo_ens_spread_t", sizeof(drpo_ens_spread_t)},
       {"drpo_rollout_cut_t", sizeof(drpo_rollout_cut_t)},     {"drpo_rollout_lookahead_t", sizeof(drpo_rollout_lookahead_t)},
       {"drpo_plan_sample_t", sizeof(drpo_plan_sample_t)},     {"drpo_plan_refit_t", sizeof(drpo_plan_refit_t)},
+      {"drpo_plan_sample_ar_t", sizeof(drpo_plan_sample_ar_t)}, {"drpo_plan_shift_t", sizeof(drpo_plan_shift_t)},
   };
   for (const E& e : table)
     if (strcmp(e.n, name) == 0) return (int64_t)e.s;

@@ -1,6 +1,7 @@
 // Sampling-based planning on the learned model (drpo_plan_sample, drpo_plan_refit;
 // include/drpo_hip.h has the definitions): the two launches of an MPPI / CEM iteration around
-// one given-actions rollout of P * N rows and the terminal critic forwards. The score of a
+// one given-actions rollout of P * N rows and the terminal critic forwards, and the two of
+// receding-horizon control (drpo_plan_sample_ar, drpo_plan_shift). The score of a
 // candidate is entry k = H of the model-based lookahead (src/ssac.py:284-294 unrolled along the
 // trajectory, in the units of src/smbpo.py:260-270), from the per-step pieces of
 // lookahead_rows.hpp that csrc/lookahead.hip runs for every k.
@@ -37,6 +38,71 @@ __global__ __launch_bounds__(PLAN_NT) void plan_sample_kernel(drpo_plan_sample_t
   x = x < d.lo ? d.lo : x;
   x = x > d.hi ? d.hi : x;
   d.cand[e] = x;
+}
+
+// ---------------------------------------------------------------------------
+// plan_sample_ar_kernel. One lane per series (r, a) of cand[P * N][K][A], walking t = 0..K-1: the
+// recursion is sequential in t, and a lane per element would redraw its whole prefix. Lane
+// r * A + a stores element (r * K + t) * A + a at step t: the A lanes of a row store A
+// consecutive floats, rows K * A apart, and over its K steps a workgroup fills one contiguous
+// range of cand. mean / std / incumbent are read the same way. Untuned (profiles/plan_mpc).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(PLAN_NT) void plan_sample_ar_kernel(drpo_plan_sample_ar_t d) {
+  const int64_t series = (int64_t)d.P * d.N * d.A;
+  const int64_t s = (int64_t)blockIdx.x * PLAN_NT + threadIdx.x;
+  if (s >= series) return;
+  const int64_t r = s / d.A;
+  const int a = (int)(s - r * d.A);
+  const int64_t p = r / d.N;
+  const int n = (int)(r - p * d.N);
+  const int64_t KA = (int64_t)d.K * d.A;
+  const int64_t e0 = r * KA + a, src0 = p * KA + a;
+  if (n == 0) {
+    for (int t = 0; t < d.K; ++t) d.cand[e0 + (int64_t)t * d.A] = d.incumbent[src0 + (int64_t)t * d.A];
+    return;
+  }
+  double u = 0.0;
+  for (int t = 0; t < d.K; ++t) {
+    const int64_t e = e0 + (int64_t)t * d.A, src = src0 + (int64_t)t * d.A;
+    const double z = (double)normal_at(nullptr, e, d.seed, d.ctr, (uint32_t)DRPO_PLAN_SITE);
+    u = t == 0 ? z : dadd(dmul(d.corr, u), dmul(d.innov, z));
+    float x = fmaf(d.std[src], (float)u, d.mean[src]);
+    x = x < d.lo ? d.lo : x;
+    x = x > d.hi ? d.hi : x;
+    d.cand[e] = x;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// plan_shift_kernel. One lane per element (p, t, a) of the three outputs [P][K][A]; consecutive
+// lanes read and store consecutive addresses (the kept steps are the inputs shift * A further on).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(PLAN_NT) void plan_shift_kernel(drpo_plan_shift_t d) {
+  const int64_t KA = (int64_t)d.K * d.A;
+  const int64_t total = (int64_t)d.P * KA;
+  const int64_t e = (int64_t)blockIdx.x * PLAN_NT + threadIdx.x;
+  if (e >= total) return;
+  const int64_t p = e / KA, j = e - p * KA;
+  const int t = (int)(j / d.A), a = (int)(j - (int64_t)t * d.A);
+  float m, inc, s;
+  if (d.reset && d.reset[p]) {
+    m = inc = d.tail ? d.tail[p * d.A + a] : 0.0f;
+    s = d.fresh_std;
+  } else if (t + d.shift < d.K) {      // (t < K and shift <= K: no overflow)
+    const int64_t src = e + (int64_t)d.shift * d.A;
+    m = d.mean[src];
+    inc = d.incumbent[src];
+    s = d.std[src];
+    s = s < d.std_floor ? d.std_floor : s;
+  } else {
+    const int64_t last = p * KA + (int64_t)(d.K - 1) * d.A + a;
+    m = d.tail ? d.tail[p * d.A + a] : d.mean[last];
+    inc = d.tail ? d.tail[p * d.A + a] : d.incumbent[last];
+    s = d.fresh_std;
+  }
+  d.mean_out[e] = m;
+  d.incumbent_out[e] = inc;
+  d.std_out[e] = s;
 }
 
 // ---------------------------------------------------------------------------
@@ -216,8 +282,9 @@ __global__ __launch_bounds__(PLAN_NT) void plan_refit_kernel(drpo_plan_refit_t d
 
 using namespace drpo;
 
-DRPO_API int drpo_plan_sample(const drpo_plan_sample_t* d, drpo_stream_t stream_) {
-  const char* who = "drpo_plan_sample";
+// what drpo_plan_sample and drpo_plan_sample_ar refuse alike (D: either descriptor)
+template <typename D>
+static int plan_sample_check(const char* who, const D* d) {
   DRPO_REQUIRE(d, "%s: null descriptor", who);
   DRPO_REQUIRE(d->P >= 0, "%s: P=%d is negative", who, d->P);
   DRPO_REQUIRE(d->N >= 2 && d->N <= DRPO_PLAN_MAX_CANDIDATES, "%s: N=%d outside 2..%d", who, d->N,
@@ -226,13 +293,57 @@ DRPO_API int drpo_plan_sample(const drpo_plan_sample_t* d, drpo_stream_t stream_
   DRPO_REQUIRE(d->A >= 1, "%s: A=%d, need A >= 1", who, d->A);
   DRPO_REQUIRE(d->lo <= d->hi, "%s: clamp [%g, %g] is empty or NaN", who, (double)d->lo, (double)d->hi);
   DRPO_REQUIRE(d->mean && d->std && d->incumbent && d->cand, "%s: null pointer", who);
-  if (d->P == 0) return DRPO_OK;
   // (K * A may not overflow the 64-bit product: each factor is below 2^31, P * N below 2^41)
   const double total = (double)d->P * d->N * d->K * d->A;
-  DRPO_REQUIRE(total < 1099511627776.0, "%s: P*N*K*A = %.0f elements exceed one grid (2^40)", who, total);
+  DRPO_REQUIRE(d->P == 0 || total < 1099511627776.0, "%s: P*N*K*A = %.0f elements exceed one grid (2^40)", who,
+               total);
+  return DRPO_OK;
+}
+
+DRPO_API int drpo_plan_sample(const drpo_plan_sample_t* d, drpo_stream_t stream_) {
+  if (const int rc = plan_sample_check("drpo_plan_sample", d)) return rc;
+  if (d->P == 0) return DRPO_OK;
   const int64_t n = (int64_t)d->P * d->N * d->K * d->A;
   plan_sample_kernel<<<(unsigned)((n + PLAN_NT - 1) / PLAN_NT), PLAN_NT, 0, (hipStream_t)stream_>>>(*d);
   DRPO_LAUNCH_CHECK("plan_sample");
+  return DRPO_OK;
+}
+
+DRPO_API int drpo_plan_sample_ar(const drpo_plan_sample_ar_t* d, drpo_stream_t stream_) {
+  const char* who = "drpo_plan_sample_ar";
+  if (const int rc = plan_sample_check(who, d)) return rc;
+  DRPO_REQUIRE(d->corr >= 0.0 && d->corr < 1.0, "%s: corr %g outside [0, 1)", who, d->corr);
+  DRPO_REQUIRE(d->innov > 0.0 && d->innov <= 1.0, "%s: innov %g outside (0, 1]", who, d->innov);
+  if (d->P == 0) return DRPO_OK;
+  const int64_t n = (int64_t)d->P * d->N * d->A;      // one lane per series
+  plan_sample_ar_kernel<<<(unsigned)((n + PLAN_NT - 1) / PLAN_NT), PLAN_NT, 0, (hipStream_t)stream_>>>(*d);
+  DRPO_LAUNCH_CHECK("plan_sample_ar");
+  return DRPO_OK;
+}
+
+DRPO_API int drpo_plan_shift(const drpo_plan_shift_t* d, drpo_stream_t stream_) {
+  const char* who = "drpo_plan_shift";
+  DRPO_REQUIRE(d, "%s: null descriptor", who);
+  DRPO_REQUIRE(d->P >= 0, "%s: P=%d is negative", who, d->P);
+  DRPO_REQUIRE(d->K >= 1, "%s: K=%d, need K >= 1", who, d->K);
+  DRPO_REQUIRE(d->A >= 1, "%s: A=%d, need A >= 1", who, d->A);
+  DRPO_REQUIRE(d->shift >= 0 && d->shift <= d->K, "%s: shift=%d outside 0..K=%d", who, d->shift, d->K);
+  DRPO_REQUIRE(isfinite(d->fresh_std) && d->fresh_std > 0.f, "%s: fresh_std %g, need finite and > 0", who,
+               (double)d->fresh_std);
+  DRPO_REQUIRE(d->std_floor >= 0.f, "%s: std_floor %g is negative or NaN", who, (double)d->std_floor);
+  DRPO_REQUIRE(d->mean && d->std && d->incumbent && d->mean_out && d->std_out && d->incumbent_out,
+               "%s: null pointer", who);
+  const void* const in[] = {d->mean, d->std, d->incumbent, d->reset, d->tail};
+  const void* const out[] = {d->mean_out, d->std_out, d->incumbent_out};
+  for (const void* o : out)
+    for (const void* i : in)
+      DRPO_REQUIRE(o != i, "%s: an output aliases an input (a shifted read races an in-place write)", who);
+  const double total = (double)d->P * d->K * d->A;
+  DRPO_REQUIRE(d->P == 0 || total < 1099511627776.0, "%s: P*K*A = %.0f elements exceed one grid (2^40)", who, total);
+  if (d->P == 0) return DRPO_OK;
+  const int64_t n = (int64_t)d->P * d->K * d->A;
+  plan_shift_kernel<<<(unsigned)((n + PLAN_NT - 1) / PLAN_NT), PLAN_NT, 0, (hipStream_t)stream_>>>(*d);
+  DRPO_LAUNCH_CHECK("plan_shift");
   return DRPO_OK;
 }
 

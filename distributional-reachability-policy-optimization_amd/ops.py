@@ -4,6 +4,7 @@ Everything here only marshals pointers, shapes and noise; all arithmetic runs in
 the HIP kernels. No CPU fallback: a missing library or non-device tensors raise.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -899,35 +900,131 @@ class PlanResult:
       executed_actions [P, H, A] what the shield let it execute (all H steps of its trajectory)
       safe_action [P, A]         executed_actions[:, 0], the action to hand to the environment
       interventions [P, H] bool  the steps at which the shield stepped in
-      filter_threshold           the shield's threshold, as imagine's shield_threshold"""
-    FIELDS = ('actions', 'action', 'score', 'certificate', 'feasible', 'n_feasible', 'mean', 'std', 'history_score',
+      filter_threshold           the shield's threshold, as imagine's shield_threshold
+
+    How the call drew and started, None from a caller that does not say (MPC_FIELDS):
+      noise_beta                 the lag-1 correlation of the candidates' noise (0.0: white)
+      warm_started               whether it started from a previous result (plan(warm_start=))
+      shift                      the steps that warm start dropped, None for a cold start"""
+    FIELDS =('actions', 'action', 'score', 'certificate', 'feasible', 'n_feasible', 'mean', 'std', 'history_score',
               'history_certificate', 'history_feasible', 'candidates', 'scores', 'certificates', 'ranks', 'imagined',
               'threshold', 'lookahead_kind')
     FILTER_FIELDS = ('executed_actions', 'safe_action', 'interventions', 'filter_threshold')
 
-    def __init__(self, executed_actions=None, safe_action=None, interventions=None, filter_threshold=None, **fields):
+    MPC_FIELDS = ('noise_beta', 'warm_started', 'shift')
+
+    def __init__(self, executed_actions=None, safe_action=None, interventions=None, filter_threshold=None,
+                 noise_beta=None, warm_started=None, shift=None, **fields):
         assert set(fields) == set(self.FIELDS), sorted(set(fields) ^ set(self.FIELDS))
         self.__dict__.update(fields, executed_actions=executed_actions, safe_action=safe_action,
-                             interventions=interventions, filter_threshold=filter_threshold)
+                             interventions=interventions, filter_threshold=filter_threshold,
+                             noise_beta=noise_beta, warm_started=warm_started, shift=shift)
 
 
-def plan_sample(mean, std, incumbent, candidates, seed, ctr, lo=-1.0, hi=1.0):
+def plan_sample(mean, std, incumbent, candidates, seed, ctr, lo=-1.0, hi=1.0, corr=0.0):
     """The candidates of one planning iteration (drpo_plan_sample): [P * N, K, A] from mean, std
     and incumbent (contiguous float32 device tensors [P, K, A]). Candidate 0 of every state is
     its incumbent; the others are mean + std * z clamped to [lo, hi], z the Philox normals of
-    (seed, ctr, PLAN_SITE). lo / hi default to the post-tanh range."""
-    from ._abi import PlanSample
+    (seed, ctr, PLAN_SITE). lo / hi default to the post-tanh range. corr in (0, 1): the noise of
+    a candidate is AR(1) along its steps with that lag-1 correlation and unit variance
+    (drpo_plan_sample_ar, over the same draws); corr == 0 is the white launch itself."""
+    from ._abi import PlanSample, PlanSampleAr
     _lib.require_device(mean, std, incumbent)
     P, K, A = mean.shape
     for t in (mean, std, incumbent):
         assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (P, K, A), 'plan_sample: [P, K, A]'
     cand = torch.empty(P * int(candidates), K, A, device=mean.device)
-    d = PlanSample()
+    white = corr == 0
+    d = PlanSample() if white else PlanSampleAr()
     d.P, d.N, d.K, d.A, d.lo, d.hi = P, int(candidates), K, A, float(lo), float(hi)
     d.seed, d.ctr = int(seed) & 0xFFFFFFFFFFFFFFFF, int(ctr) & 0xFFFFFFFFFFFFFFFF
     d.mean, d.std, d.incumbent, d.cand = mean.data_ptr(), std.data_ptr(), incumbent.data_ptr(), cand.data_ptr()
-    _lib.check(_lib.lib().drpo_plan_sample(ctypes.byref(d), _lib.stream()), 'plan_sample')
+    if white:
+        _lib.check(_lib.lib().drpo_plan_sample(ctypes.byref(d), _lib.stream()), 'plan_sample')
+    else:
+        d.corr, d.innov = float(corr), math.sqrt(1.0 - float(corr) * float(corr))
+        _lib.check(_lib.lib().drpo_plan_sample_ar(ctypes.byref(d), _lib.stream()), 'plan_sample_ar')
     return cand
+
+
+def plan_shift(mean, std, incumbent, *, shift, fresh_std, std_floor, reset=None, tail=None):
+    """The warm start of the next control step (drpo_plan_shift, one launch): three fresh
+    [P, K, A] tensors (mean, std, incumbent) from those of the previous step, moved ``shift``
+    steps towards the front. The kept steps' std is raised to ``std_floor``; the fresh steps at
+    the end repeat the last kept step (or ``tail`` [P, A]) with std ``fresh_std``. States whose
+    ``reset`` [P] (bool) is set start cold: zero (or ``tail``) and ``fresh_std`` at every step."""
+    from ._abi import PlanShift
+    P, K, A = mean.shape
+    for t in (mean, std, incumbent):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (P, K, A), 'plan_shift: [P, K, A]'
+    keep = [mean, std, incumbent]
+    d = PlanShift()
+    if reset is not None:
+        assert reset.dtype in (torch.bool, torch.uint8) and reset.is_contiguous() and tuple(reset.shape) == (P,), \
+            'plan_shift: reset is [P] bool'
+        keep.append(reset)
+        d.reset = reset.data_ptr()
+    if tail is not None:
+        assert tail.dtype == torch.float32 and tail.is_contiguous() and tuple(tail.shape) == (P, A), \
+            'plan_shift: tail is [P, A]'
+        keep.append(tail)
+        d.tail = tail.data_ptr()
+    _lib.require_device(*keep)
+    out = [torch.empty(P, K, A, device=mean.device) for _ in range(3)]
+    d.P, d.K, d.A, d.shift, d.fresh_std, d.std_floor = P, K, A, int(shift), float(fresh_std), float(std_floor)
+    d.mean, d.std, d.incumbent = mean.data_ptr(), std.data_ptr(), incumbent.data_ptr()
+    d.mean_out, d.std_out, d.incumbent_out = (t.data_ptr() for t in out)
+    _lib.check(_lib.lib().drpo_plan_shift(ctypes.byref(d), _lib.stream()), 'plan_shift')
+    return tuple(out)
+
+
+class PlanController:
+    """Receding-horizon control on SMBPO.plan (SMBPO.mpc builds one): one plan per act(), warm
+    started from the previous one.
+
+      act(states, reset=None)   actions [P, A] on the device for the P states, in the same order
+                                at every call. A cold plan on the first call, after reset() and
+                                when P changes; else plan(warm_start=last, shift=shift, reset=).
+                                ``reset`` [P] bool: the states that do not continue the previous
+                                call's (a new episode), which start cold.
+      reset()                   forget the last result: the next act() starts cold.
+      last                      the PlanResult of the last act(); steps: the calls so far.
+
+    The action is the result's safe_action under safety_filter, else its action. fallback='safe':
+    a state whose best row is not feasible takes the safe actor's mean action instead (a select
+    on the device); fallback=None: the planner's action whatever its certificate. Nothing syncs
+    with the host. The draws come from the ``noise`` given to mpc(), else from plan's private
+    stream: the trainer's stream, the buffers and steps_sampled do not move."""
+
+    def __init__(self, alg, fallback, shift, warm_std, plan_kwargs):
+        self.alg, self.fallback, self.shift, self.warm_std = alg, fallback, shift, warm_std
+        self.plan_kwargs = dict(plan_kwargs)
+        self.last, self.steps = None, 0
+
+    def reset(self):
+        self.last = None
+
+    def act(self, states, reset=None):
+        alg = self.alg
+        states = torch.as_tensor(states, dtype=torch.float32).reshape(-1, alg.state_dim)
+        warm = self.last is not None and len(self.last.actions) == len(states)
+        if warm:
+            res = alg.plan(states, warm_start=self.last, shift=self.shift, warm_std=self.warm_std, reset=reset,
+                           **self.plan_kwargs)
+        else:
+            kw = dict(self.plan_kwargs)
+            tail = kw.pop('tail', None)
+            if tail is not None:        # what plan_shift gives a reset state: the tail at every step
+                K = kw.get('steps') or kw.get('horizon') or alg.horizon
+                kw['init'] = torch.as_tensor(tail, dtype=torch.float32).unsqueeze(1).repeat(1, K, 1)
+            res = alg.plan(states, **kw)
+        action = res.action if res.safe_action is None else res.safe_action
+        if self.fallback == 'safe':
+            safe = alg.solver.actor_safe.act(states.to(alg.device), eval=True)
+            action = torch.where(res.feasible.unsqueeze(-1), action, safe)
+        self.last = res
+        self.steps += 1
+        return action
 
 
 def plan_refit(alg, im, terminal_q, terminal_qc, cand, mean, std, gamma, *, candidates, threshold, elites,

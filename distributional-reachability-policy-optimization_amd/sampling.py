@@ -59,9 +59,13 @@ def shielded_actions(policy, states, eval, safe_shield_threshold, shield_type, n
                              a_safe, mixes)
 
 
-def sample_episodes_batched(env, policy, n_traj, eval=False, safe_shield_threshold=-0.1, shield_type="linear"):
+def sample_episodes_batched(env, policy, n_traj, eval=False, safe_shield_threshold=-0.1, shield_type="linear",
+                            controller=None):
     """src/sampling.py:409-464: step a batch of envs until n_traj episodes complete;
-    returns their SafetySampleBuffers in completion order."""
+    returns their SafetySampleBuffers in completion order. ``controller`` (an
+    ops.PlanController): a step's actions are controller.act(states, reset=mask) instead of the
+    shielded policy's, mask[i] set at the first step and wherever env i's state came from a
+    partial_reset, so that a new episode's plan starts cold."""
     if not hasattr(env, 'n_envs'):
         env = ProductEnv([env])
     S, A, _ = env_dims(env)
@@ -70,8 +74,14 @@ def sample_episodes_batched(env, policy, n_traj, eval=False, safe_shield_thresho
     complete = []
     states = env.reset()
     dev = states.device
+    fresh = list(range(env.n_envs))     # the envs whose state starts an episode (controller only)
     while True:
-        actions = shielded_actions(policy, states, eval, safe_shield_threshold, shield_type)
+        if controller is None:
+            actions = shielded_actions(policy, states, eval, safe_shield_threshold, shield_type)
+        else:
+            mask = torch.zeros(env.n_envs, dtype=torch.bool)
+            mask[fresh] = True
+            actions = controller.act(states, reset=mask.to(dev))
         next_states, rewards, dones, infos = env.step(actions)
         violations = [bool(info['violation']) for info in infos]
         _next_states = next_states.clone()
@@ -87,7 +97,7 @@ def sample_episodes_batched(env, policy, n_traj, eval=False, safe_shield_thresho
                 trajs[i] = _Trajectory()
         if reset_indices:
             _next_states[reset_indices] = env.partial_reset(reset_indices)
-        states = _next_states
+        states, fresh = _next_states, reset_indices
 
 
 def stat_forwards(solver, states, actions, distributional, mlp_multiplier):

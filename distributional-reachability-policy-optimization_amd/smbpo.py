@@ -464,7 +464,7 @@ class SMBPO(Configurable, Module):
     def plan(self, states, horizon=None, *, candidates=64, iterations=4, steps=None, elites=None,
              temperature=float('inf'), momentum=0.0, init=None, init_std=0.5, min_std=0.05, threshold=None,
              lookahead=True, policy=None, members=None, model_noise=False, discount=None, noise=None,
-             safety_filter=None):
+             safety_filter=None, warm_start=None, shift=1, reset=None, tail=None, warm_std=None, noise_beta=0.0):
         """The best of sampled action sequences from each of the P ``states``, by the model and the
         two critics: an MPPI / CEM planner whose score is imagine(actions=, lookahead=)'s
         value_lookahead[:, H] and whose constraint is its certificate_lookahead[:, H] (the
@@ -514,11 +514,106 @@ class SMBPO(Configurable, Module):
                      (the filtered first action, the one to hand to the environment),
                      ``interventions`` and ``filter_threshold`` of the best row. Independent
                      of ``threshold``, the planner's constraint on the unrolled certificate.
+        noise_beta   in [0, 1): the lag-1 correlation of a candidate's noise along its steps
+                     (AR(1) at unit variance, drpo_plan_sample_ar, over the white launch's own
+                     draws), in every sample launch of the call. 0: white noise through the
+                     white launch. Correlated noise gives smoother candidates, which is what a
+                     controller that re-plans at every step wants.
+        warm_start   the previous control step's PlanResult (or any object with ``mean``,
+                     ``std`` and ``actions`` [P, K, A]) over the same P states in order and the
+                     same K; not with ``init``. The call starts from ops.plan_shift of the three
+                     (drpo_plan_shift, one launch): the sequences moved ``shift`` steps (0..K,
+                     default 1) towards the front, and the first incumbent is the shifted
+                     ``actions``, not the mean. shift=0 re-plans at the same states. The fresh
+                     steps at the end repeat the last kept step, or take ``tail`` [P, A], with
+                     std init_std. warm_std: the floor of the kept steps' std, default min_std
+                     (a converged plan's std sits at min_std, so a controller that should keep
+                     exploring wants it larger, a fraction of init_std). reset [P] bool: the
+                     states that start cold (a zero mean, or ``tail``, and init_std), as a new
+                     episode does; all of them set is the cold call, bit for bit. reset, tail
+                     and warm_std need a warm_start.
+                     With a fixed member and model_noise=False, shift=0 and the same states, the
+                     best key is never below warm_start's: candidate 0 is its best row, run
+                     again from the same state. With shift >= 1 nothing of the kind holds: the
+                     shifted sequence is scored from another state.
         Not with a recorded tape; NotImplementedError for an env without device constraint
-        functions, as imagine. halt= inside the planner, time-correlated noise and a shifted
-        warm start are not built."""
+        functions, as imagine. SMBPO.mpc wraps the warm start in a controller. halt= inside the
+        planner is not built."""
+        q = dict(locals())
+        del q['self']
+        q = self._plan_checks(**q)
         from . import ops
         from .rng import _mix64
+        H, N, K, P, A = q['H'], q['N'], q['K'], q['P'], q['A']
+        states, init, elites, threshold, look, filt = (q[k] for k in ('states', 'init', 'elites', 'threshold', 'look',
+                                                                      'filt'))
+
+        # the device work
+        dev = self.device
+        states = states.to(dev)
+        policy = self.actor if policy is None else policy
+        if noise is None:
+            if self.__dict__.get('_plan_noise') is None:
+                self._plan_noise = DeviceNoise(_mix64(self.noise.base_seed ^ self.PLAN_SALT), rank=0, world=1)
+            noise = self._plan_noise
+        gamma = float(self.solver.discount if discount is None else discount)
+        run = dict(members=members, deterministic=True, model_noise=model_noise, discount=gamma, noise=noise)
+        if warm_start is not None:
+            def on_dev(x, dtype=torch.float32):
+                return None if x is None else torch.as_tensor(x, dtype=dtype).to(dev).contiguous()
+            mean, std, incumbent = ops.plan_shift(
+                *(on_dev(getattr(warm_start, k)) for k in ('mean', 'std', 'actions')), shift=shift,
+                fresh_std=init_std, std_floor=min_std if warm_std is None else warm_std,
+                reset=on_dev(reset, torch.bool), tail=on_dev(tail))
+        else:
+            if init is None:
+                mean = torch.zeros(P, K, A, device=dev)
+            elif isinstance(init, str):
+                mean = self.imagine(states, policy, H, **run).actions[:, :K].contiguous()
+            else:
+                mean = init.to(dev).contiguous()
+            std = torch.full((P, K, A), float(init_std), device=dev)
+            incumbent = mean
+        corr = {} if noise_beta == 0 else {'corr': float(noise_beta)}
+        tiled = states.repeat_interleave(N, dim=0)
+        history = []
+        for _ in range(iterations):
+            cand = ops.plan_sample(mean, std, incumbent, N, noise.seed, noise.next(), **corr)
+            if filt is None:
+                im = self.imagine(tiled, policy, H, actions=cand, **run)
+            else:     # the candidates as proposals: scored on what the shield lets them run
+                im = self.imagine(tiled, policy, H, proposals=cand, shield=filt, **run)
+            terminal_q, terminal_qc = ops._terminal_critics(self, policy, im, look)
+            fit = ops.plan_refit(self, im, terminal_q, terminal_qc, cand, mean, std, gamma, candidates=N,
+                                 threshold=threshold, elites=elites, temperature=temperature, momentum=momentum,
+                                 min_std=min_std)
+            mean, std, incumbent = fit['mean'], fit['std'], fit['best_actions']
+            history.append((fit['best_score'], fit['best_cert'], fit['best_feasible']))
+        filtered = {}
+        if filt is not None:
+            # the best row's filtered trajectory, gathered on the device (row p * N + best[p])
+            rows = torch.arange(P, device=dev, dtype=torch.int64) * N + fit['best'].to(torch.int64)
+            executed = im.actions.index_select(0, rows)
+            filtered = dict(executed_actions=executed, safe_action=executed[:, 0],
+                            interventions=im.interventions.index_select(0, rows), filter_threshold=im.shield_threshold)
+        return ops.PlanResult(
+            **filtered, noise_beta=float(noise_beta), warm_started=warm_start is not None,
+            shift=None if warm_start is None else shift,
+            actions=incumbent, action=incumbent[:, 0], score=fit['best_score'], certificate=fit['best_cert'],
+            feasible=fit['best_feasible'], n_feasible=fit['n_feasible'], mean=mean, std=std,
+            history_score=torch.stack([h[0] for h in history]),
+            history_certificate=torch.stack([h[1] for h in history]),
+            history_feasible=torch.stack([h[2] for h in history]),
+            candidates=cand.reshape(P, N, K, A), scores=fit['score'], certificates=fit['cert'], ranks=fit['rank'],
+            imagined=im, threshold=threshold, lookahead_kind=look)
+
+    def _plan_checks(self, states, horizon, *, candidates, iterations, steps, elites, temperature, momentum, init,
+                     init_std, min_std, threshold, lookahead, policy, members, model_noise, discount, noise,
+                     safety_filter, warm_start, shift, reset, tail, warm_std, noise_beta, controller=False):
+        """Every refusal of plan's arguments, before any device work; returns what they resolve
+        to. controller=True (SMBPO.mpc, which has no states yet): shift, tail and warm_std are
+        checked as far as they can be without P and without a warm_start."""
+        from . import ops
         if self.env_params is None:
             raise NotImplementedError('plan needs the constraint functions on the device, as imagine does: give the '
                                       'env a ConstraintProgram (drpo_constraint_program, see INTEGRATION.md)')
@@ -578,10 +673,23 @@ class SMBPO(Configurable, Module):
                 raise ValueError(f'safety_filter: {safety_filter!r} (None, True, a threshold (-inf and inf are '
                                  "allowed, NaN is not) or 'linear')")
             filt = float(filt)
+        if not (is_num(noise_beta) and 0 <= noise_beta < 1):
+            raise ValueError(f'noise_beta: {noise_beta!r} (a number in [0, 1))')
+        if not (is_int(shift) and 0 <= shift <= K):
+            raise ValueError(f'shift: {shift!r} (an int, 0..steps {K})')
+        if not (warm_std is None or is_num(warm_std) and warm_std >= 0):
+            raise ValueError(f'warm_std: {warm_std!r} (None or a number >= 0)')
+        A = self.action_dim
+        if controller:
+            # mpc: no states, no P and no warm start yet (act() makes them)
+            if tail is not None and not ((torch.is_tensor(tail) or isinstance(tail, np.ndarray)) and tail.ndim == 2
+                                         and tail.shape[-1] == A):
+                raise ValueError(f'tail: {tail!r} (None or a [P, {A}] tensor)')
+            return None
         if states is None:
             raise ValueError('plan needs start states')
         states = torch.as_tensor(states, dtype=torch.float32).reshape(-1, self.state_dim)
-        P, A = len(states), self.action_dim
+        P = len(states)
         if isinstance(init, str) and init != 'policy' or not (init is None or isinstance(init, str) or
                                                                 torch.is_tensor(init) or isinstance(init, np.ndarray)):
             raise ValueError(f"init: {init!r} (None, 'policy' or a [P, K, A] tensor)")
@@ -590,54 +698,54 @@ class SMBPO(Configurable, Module):
             if tuple(init.shape) != (P, K, A):
                 raise ValueError(f'init: shape {tuple(init.shape)} is not [{P}, {K}, {A}]')
 
-        # the device work
-        dev = self.device
-        states = states.to(dev)
-        policy = self.actor if policy is None else policy
-        if noise is None:
-            if self.__dict__.get('_plan_noise') is None:
-                self._plan_noise = DeviceNoise(_mix64(self.noise.base_seed ^ self.PLAN_SALT), rank=0, world=1)
-            noise = self._plan_noise
-        gamma = float(self.solver.discount if discount is None else discount)
-        run = dict(members=members, deterministic=True, model_noise=model_noise, discount=gamma, noise=noise)
-        if init is None:
-            mean = torch.zeros(P, K, A, device=dev)
-        elif isinstance(init, str):
-            mean = self.imagine(states, policy, H, **run).actions[:, :K].contiguous()
+        def is_array(x):
+            return torch.is_tensor(x) or isinstance(x, np.ndarray)
+        if warm_start is None:
+            for name, v in (('reset', reset), ('tail', tail), ('warm_std', warm_std)):
+                if v is not None:
+                    raise ValueError(f'{name} without warm_start: it says how a warm start is made')
         else:
-            mean = init.to(dev).contiguous()
-        std = torch.full((P, K, A), float(init_std), device=dev)
-        incumbent = mean
-        tiled = states.repeat_interleave(N, dim=0)
-        history = []
-        for _ in range(iterations):
-            cand = ops.plan_sample(mean, std, incumbent, N, noise.seed, noise.next())
-            if filt is None:
-                im = self.imagine(tiled, policy, H, actions=cand, **run)
-            else:     # the candidates as proposals: scored on what the shield lets them run
-                im = self.imagine(tiled, policy, H, proposals=cand, shield=filt, **run)
-            terminal_q, terminal_qc = ops._terminal_critics(self, policy, im, look)
-            fit = ops.plan_refit(self, im, terminal_q, terminal_qc, cand, mean, std, gamma, candidates=N,
-                                 threshold=threshold, elites=elites, temperature=temperature, momentum=momentum,
-                                 min_std=min_std)
-            mean, std, incumbent = fit['mean'], fit['std'], fit['best_actions']
-            history.append((fit['best_score'], fit['best_cert'], fit['best_feasible']))
-        filtered = {}
-        if filt is not None:
-            # the best row's filtered trajectory, gathered on the device (row p * N + best[p])
-            rows = torch.arange(P, device=dev, dtype=torch.int64) * N + fit['best'].to(torch.int64)
-            executed = im.actions.index_select(0, rows)
-            filtered = dict(executed_actions=executed, safe_action=executed[:, 0],
-                            interventions=im.interventions.index_select(0, rows), filter_threshold=im.shield_threshold)
-        return ops.PlanResult(
-            **filtered,
-            actions=incumbent, action=incumbent[:, 0], score=fit['best_score'], certificate=fit['best_cert'],
-            feasible=fit['best_feasible'], n_feasible=fit['n_feasible'], mean=mean, std=std,
-            history_score=torch.stack([h[0] for h in history]),
-            history_certificate=torch.stack([h[1] for h in history]),
-            history_feasible=torch.stack([h[2] for h in history]),
-            candidates=cand.reshape(P, N, K, A), scores=fit['score'], certificates=fit['cert'], ranks=fit['rank'],
-            imagined=im, threshold=threshold, lookahead_kind=look)
+            if init is not None:
+                raise ValueError('warm_start together with init: a call starts from one of them')
+            for k in ('mean', 'std', 'actions'):
+                v = getattr(warm_start, k, None)
+                if not (is_array(v) and tuple(v.shape) == (P, K, A)):
+                    raise ValueError(f'warm_start: its {k} is {"missing" if v is None else "not"} a [{P}, {K}, {A}] '
+                                     'tensor (a PlanResult over the same states and steps)')
+            if reset is not None and not (is_array(reset) and tuple(reset.shape) == (P,) and
+                                          reset.dtype in (torch.bool, np.dtype(bool))):
+                raise ValueError(f'reset: {reset!r} (None or a [{P}] bool tensor)')
+            if tail is not None and not (is_array(tail) and tuple(tail.shape) == (P, A)):
+                raise ValueError(f'tail: {tail!r} (None or a [{P}, {A}] tensor)')
+        return dict(H=H, N=N, K=K, P=P, A=A, states=states, init=init, elites=elites, threshold=threshold, look=look,
+                    filt=filt)
+
+    def mpc(self, *, fallback='safe', shift=1, warm_std=None, **plan_kwargs):
+        """A receding-horizon controller on plan (an ops.PlanController): ``act(states)`` plans
+        once per control step and warm-starts each plan from the last one, moved ``shift`` steps.
+
+        fallback     'safe': a state whose best row is not feasible takes the safe actor's mean
+                     action, the fallback of the shielded policy; None: the planner's action
+                     whatever its certificate.
+        shift, warm_std   as plan's, of every warm start.
+        plan_kwargs  plan's own (horizon, candidates, iterations, noise_beta, safety_filter,
+                     noise, ...), checked here once by plan's checks; not states, init,
+                     warm_start or reset, which act() supplies. A ``tail`` [P, A] also starts
+                     the cold plans.
+        sampling.sample_episodes_batched(controller=) and evaluate(controller=) run one on the
+        real environment. Not built: the planner inside step_generator, halt= inside the
+        planner, data-parallel sharding of the states."""
+        import inspect
+        from . import ops
+        for k in ('states', 'init', 'warm_start', 'reset'):
+            if k in plan_kwargs:
+                raise ValueError(f'mpc: {k} is not a controller setting (act() supplies it)')
+        if fallback is not None and fallback != 'safe':
+            raise ValueError(f"fallback: {fallback!r} ('safe' or None)")
+        bound = inspect.signature(self.plan).bind(None, shift=shift, warm_std=warm_std, **plan_kwargs)
+        bound.apply_defaults()
+        self._plan_checks(**bound.arguments, controller=True)
+        return ops.PlanController(self, fallback, shift, warm_std, plan_kwargs)
 
     def update_models(self, model_steps, noise=None):
         """src/smbpo.py:214-227."""
@@ -700,12 +808,15 @@ class SMBPO(Configurable, Module):
         self.log_statistics()
         self.epochs_completed += 1
 
-    def evaluate(self):
-        """src/smbpo.py:421-440: N_EVAL_TRAJ shielded evaluation episodes."""
+    def evaluate(self, controller=None):
+        """src/smbpo.py:421-440: N_EVAL_TRAJ shielded evaluation episodes. ``controller`` (an
+        ops.PlanController of self.mpc): the episodes' actions are the controller's instead of
+        the shielded policy's; the same keys come back."""
         from .sampling import sample_episodes_batched
+        ctl = {} if controller is None else {'controller': controller}
         trajs = sample_episodes_batched(self.eval_env, self.solver, N_EVAL_TRAJ, eval=True,
                                         safe_shield_threshold=self.eval_shield_threshold,
-                                        shield_type=self.eval_shield_type)
+                                        shield_type=self.eval_shield_type, **ctl)
         lengths = [len(t) for t in trajs]
         returns = [t.get('rewards').sum().item() for t in trajs]
         violations = [t.get('violations').sum().item() for t in trajs]

@@ -443,6 +443,60 @@ typedef struct {
 
 int drpo_plan_sample(const drpo_plan_sample_t* d /* host */, drpo_stream_t stream);
 
+/* drpo_plan_sample_ar: drpo_plan_sample with AR(1) noise along the steps (time-correlated
+ * candidates for receding-horizon control). Row r = p * N + n, action dimension a:
+ *   n == 0: incumbent[p][t][a], copied bit for bit, for every t;
+ *   n >= 1: z_t = normal_at(idx = (r * K + t) * A + a, seed, ctr, DRPO_PLAN_SITE), the index and
+ *           site of drpo_plan_sample (the same draws), and in ordered double arithmetic, nothing
+ *           contracted:
+ *             u_0 = (double)z_0;  u_t = corr * u_{t-1} + innov * (double)z_t   (t = 1..K-1)
+ *             x_t = fmaf(std[p][t][a], (float)u_t, mean[p][t][a]);
+ *             x_t = x_t < lo ? lo : x_t; x_t = x_t > hi ? hi : x_t   (selects: a NaN stays).
+ * innov = sqrt(1 - corr^2) keeps u_t at unit variance; the relation is the caller's and is not
+ * checked. corr = 0, innov = 1 gives drpo_plan_sample's cand bit for bit. Every element of cand
+ * is written. DRPO_EINVAL before any launch: whatever drpo_plan_sample refuses, corr outside
+ * [0, 1) or NaN, innov outside (0, 1] or NaN. P == 0: DRPO_OK without a launch. */
+typedef struct {
+  int P, N, K, A;          /* start states, candidates per state, given steps, action dim */
+  float lo, hi;            /* the clamp of the drawn candidates */
+  uint64_t seed, ctr;
+  const float* mean;       /* [P][K][A], device */
+  const float* std;        /* [P][K][A] */
+  const float* incumbent;  /* [P][K][A] */
+  float* cand;             /* [P * N][K][A], out */
+  double corr, innov;      /* the lag-1 correlation and the innovation's scale */
+} drpo_plan_sample_ar_t;
+
+int drpo_plan_sample_ar(const drpo_plan_sample_ar_t* d /* host */, drpo_stream_t stream);
+
+/* drpo_plan_shift: the warm start of the next control step from mean, std and incumbent (each
+ * [P][K][A]) of the previous one, in one launch. Element (p, t, a):
+ *   reset && reset[p]:  mean_out = incumbent_out = tail ? tail[p][a] : 0.0f; std_out = fresh_std;
+ *   else t + shift < K: mean_out = mean[p][t + shift][a], incumbent_out = incumbent[p][t + shift][a],
+ *                       copied bit for bit; s = std[p][t + shift][a];
+ *                       std_out = s < std_floor ? std_floor : s   (a select: a NaN stays);
+ *   else:               mean_out = tail ? tail[p][a] : mean[p][K - 1][a],
+ *                       incumbent_out = tail ? tail[p][a] : incumbent[p][K - 1][a]; std_out = fresh_std.
+ * Copies and selects only. Every element of the three outputs is written; nothing else is.
+ * DRPO_EINVAL before any launch: a null descriptor or pointer (reset and tail may be NULL), P < 0,
+ * K < 1, A < 1, more than 2^40 elements, shift outside 0..K, fresh_std not finite or <= 0,
+ * std_floor NaN or negative, an output equal to an input (a shifted read races an in-place
+ * write). P == 0: DRPO_OK without a launch. */
+typedef struct {
+  int P, K, A, shift;            /* start states, given steps, action dim, steps to drop */
+  float fresh_std, std_floor;    /* the std of the fresh steps; the floor of the kept steps' */
+  const float* mean;             /* [P][K][A], device */
+  const float* std;              /* [P][K][A] */
+  const float* incumbent;        /* [P][K][A] */
+  const uint8_t* reset;          /* [P] or NULL: non-zero starts the state cold */
+  const float* tail;             /* [P][A] or NULL: the action of the fresh steps */
+  float* mean_out;               /* [P][K][A] */
+  float* std_out;                /* [P][K][A] */
+  float* incumbent_out;          /* [P][K][A] */
+} drpo_plan_shift_t;
+
+int drpo_plan_shift(const drpo_plan_shift_t* d /* host */, drpo_stream_t stream);
+
 /* drpo_plan_refit: scores and ranks the candidates of every start state and refits mean and
  * std, on the trajectory-major tensors that the run of B = P * N rows (row r = p * N + n) and
  * horizon H under cand left. One workgroup serves one start state.
