@@ -111,6 +111,15 @@ class PlanRefit(ctypes.Structure):
                 ('score', P), ('cert', P), ('rank', P), ('weight', P)]
 
 
+PLAN_MAX_PARTICLES = 32        # DRPO_PLAN_MAX_PARTICLES
+
+
+class PlanRefitParticles(ctypes.Structure):
+    """drpo_plan_refit_particles_t"""
+    _fields_ = PlanRefit._fields_ + [('G', c_int), ('score_tail', c_int), ('cert_mode', c_int), ('pad2_', c_int),
+                                     ('member_score', P), ('member_cert', P), ('score_spread', P)]
+
+
 ENV_PROGRAM = 4          # DRPO_ENV_PROGRAM
 PROG_AFFINE, PROG_BALLS = 0, 1
 PROG_MAX_ROWS = PROG_MAX_TERMS = PROG_MAX_CENTRES = PROG_MAX_BOX = 8
@@ -198,6 +207,7 @@ PROTOTYPES = {
     'drpo_plan_sample_ar': (c_int, [POINTER(PlanSampleAr), P]),
     'drpo_plan_shift': (c_int, [POINTER(PlanShift), P]),
     'drpo_plan_refit': (c_int, [POINTER(PlanRefit), P]),
+    'drpo_plan_refit_particles': (c_int, [POINTER(PlanRefitParticles), P]),
     'drpo_env_constraints': (c_int, [c_int, c_int, c_int, c_double, c_double, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_constraints_program': (c_int, [P, c_int, P, c_int64, c_int, P, P, P, P]),
     'drpo_env_program_check': (c_int, [POINTER(EnvProgram), c_int]),

@@ -19,7 +19,7 @@ void drpo_set_error(const char* fmt, ...) {
 
 DRPO_API const char* drpo_last_error(void) { return g_err; }
 
-DRPO_API int drpo_version(void) { return 15; }
+DRPO_API int drpo_version(void) { return 16; }
 
 // HIP event helpers so hosts without a HIP binding (ctypes/cgo/JNI) can time
 // individual kernels on the stream they run on. The events are timing-only: created
@@ -85,6 +85,7 @@ DRPO_API int64_t drpo_abi_sizeof(const char* name) {
       {"drpo_rollout_cut_t", sizeof(drpo_rollout_cut_t)},     {"drpo_rollout_lookahead_t", sizeof(drpo_rollout_lookahead_t)},
       {"drpo_plan_sample_t", sizeof(drpo_plan_sample_t)},     {"drpo_plan_refit_t", sizeof(drpo_plan_refit_t)},
       {"drpo_plan_sample_ar_t", sizeof(drpo_plan_sample_ar_t)}, {"drpo_plan_shift_t", sizeof(drpo_plan_shift_t)},
+      {"drpo_plan_refit_particles_t", sizeof(drpo_plan_refit_particles_t)},
   };
   for (const E& e : table)
     if (strcmp(e.n, name) == 0) return (int64_t)e.s;
@@ -105,7 +106,7 @@ DRPO_API int64_t drpo_abi_const(const char* name) {
       K(DRPO_UPSTREAM_ACTOR_CC), K(DRPO_UPSTREAM_SAFE_CC), K(DRPO_UPSTREAM_NEG_MEAN), K(DRPO_UPSTREAM_SQUASH),
       K(DRPO_UPSTREAM_SQUASH_SAFE),
       K(DRPO_ROLLOUT_FUSED_MAX_H), K(DRPO_OPTIM_MAX_SEGS), K(DRPO_MLP_MULTI_MAX_JOBS), K(DRPO_MLP_MULTI_MAX_SLOTS),
-      K(DRPO_MLP_FB_MAX_JOBS), K(DRPO_PLAN_MAX_CANDIDATES), K(DRPO_PLAN_SITE),
+      K(DRPO_MLP_FB_MAX_JOBS), K(DRPO_PLAN_MAX_CANDIDATES), K(DRPO_PLAN_SITE), K(DRPO_PLAN_MAX_PARTICLES),
   };
 #undef K
   for (const E& e : table)

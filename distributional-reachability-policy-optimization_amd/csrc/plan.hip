@@ -1,7 +1,8 @@
 // Sampling-based planning on the learned model (drpo_plan_sample, drpo_plan_refit;
 // include/drpo_hip.h has the definitions): the two launches of an MPPI / CEM iteration around
 // one given-actions rollout of P * N rows and the terminal critic forwards, and the two of
-// receding-horizon control (drpo_plan_sample_ar, drpo_plan_shift). The score of a
+// receding-horizon control (drpo_plan_sample_ar, drpo_plan_shift), and the refit over G runs of
+// the candidates, one per ensemble member (drpo_plan_refit_particles). The score of a
 // candidate is entry k = H of the model-based lookahead (src/ssac.py:284-294 unrolled along the
 // trajectory, in the units of src/smbpo.py:260-270), from the per-step pieces of
 // lookahead_rows.hpp that csrc/lookahead.hip runs for every k.
@@ -118,7 +119,7 @@ __global__ __launch_bounds__(PLAN_NT) void plan_shift_kernel(drpo_plan_shift_t d
 //      is uniform), so only the elites' actions are fetched.
 // Plain stores, no atomics, no waits between workgroups.
 // ---------------------------------------------------------------------------
-__host__ __device__ inline size_t plan_lds_bytes(int N, int H) {
+__host__ __device__ constexpr size_t plan_lds_bytes(int N, int H) {
   // w[H + 1], weight[N] doubles; score, cert, key [N] floats; class [N] bytes; 4 ints
   return sizeof(double) * ((size_t)(H + 1) + N) + sizeof(float) * 3 * (size_t)N + sizeof(int) * 4 + (size_t)N;
 }
@@ -129,66 +130,66 @@ __device__ __forceinline__ bool plan_precedes(int cm, float km, int m, int cn, f
   return cm < cn || (cm == cn && (km > kn || (km == kn && m < n)));
 }
 
-__global__ __launch_bounds__(PLAN_NT) void plan_refit_kernel(drpo_plan_refit_t d) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char plan_smem[];
-  const int N = d.N, H = d.H, C = d.C, tid = threadIdx.x;
-  const int KA = d.K * d.A;
-  double* s_w = reinterpret_cast<double*>(plan_smem);   // [H + 1]
-  double* s_wt = s_w + (H + 1);                         // [N]
-  float* s_score = reinterpret_cast<float*>(s_wt + N);  // [N]
-  float* s_cert = s_score + N;                          // [N]
-  float* s_key = s_cert + N;                            // [N]
-  int* s_int = reinterpret_cast<int*>(s_key + N);       // best, n_feasible, n_valid
-  unsigned char* s_cls = reinterpret_cast<unsigned char*>(s_int + 4);   // [N]
-
-  const size_t p = blockIdx.x;
-  const size_t row0 = p * (size_t)N;
+// score and cert of the row whose tensors start at flat row r (step a of drpo_plan_refit), each
+// rounded to float32 once. D: either refit descriptor; s_w: weights[H + 1] in LDS.
+template <typename D>
+__device__ __forceinline__ void plan_row_values(const D& d, const double* s_w, size_t r, float& sc, float& ce) {
+  const int H = d.H, C = d.C;
   const double g = d.gamma, one_minus_g = 1.0 - d.gamma;
   const double rs = d.reward_scale, ab = d.alive_bonus, cs = d.constraint_scale, co = d.constraint_offset;
   const bool cost = d.mode == 1;
-  const float thr = d.threshold;
-
-  for (int e = tid; e <= H; e += PLAN_NT) s_w[e] = d.weights[e];
-  __syncthreads();
-
-  // ---- A. score and cert of every candidate -------------------------------------
-  for (int n = tid; n < N; n += PLAN_NT) {
-    const size_t r = row0 + n;
-    const int len = min(max(d.lengths[r], 0), H);
-    const bool boot = d.terminated[r] == 0;
-    const float* rw = d.rewards + r * H;
-    const uint8_t* dn = d.dones + r * H;
-    double acc = 0.0;
-    for (int t = 0; t < len; ++t) acc = dadd(acc, dmul(s_w[t], look_reward(rw[t], rs, ab)));
-    if (boot) acc = dadd(acc, dmul(s_w[len], (double)d.terminal_q[r]));
-    double top = 0.0;
-    for (int c = 0; c < C; ++c) {
-      // a terminated row has no bootstrap: the scan starts from 0.0, which the done select of
-      // its last step replaces
-      double x = boot ? (double)d.terminal_qc[r * C + c] : 0.0;
-      if (cost) {
-        const uint8_t* vi = d.violations + r * H;
-        for (int t = len - 1; t >= 0; --t) x = look_cost_step((dn[t] ? 1u : 0u) | (vi[t] ? 2u : 0u), g, x);
-      } else {
-        const float* hv = d.constraint_values + r * H * C + c;
-        for (int t = len - 1; t >= 0; --t) {
-          const double h = look_hprime(hv[(size_t)t * C], cs, co);
-          x = look_reach_step(dn[t] != 0, h, dmul(one_minus_g, h), g, x);
-        }
+  const int len = min(max(d.lengths[r], 0), H);
+  const bool boot = d.terminated[r] == 0;
+  const float* rw = d.rewards + r * H;
+  const uint8_t* dn = d.dones + r * H;
+  double acc = 0.0;
+  for (int t = 0; t < len; ++t) acc = dadd(acc, dmul(s_w[t], look_reward(rw[t], rs, ab)));
+  if (boot) acc = dadd(acc, dmul(s_w[len], (double)d.terminal_q[r]));
+  double top = 0.0;
+  for (int c = 0; c < C; ++c) {
+    // a terminated row has no bootstrap: the scan starts from 0.0, which the done select of
+    // its last step replaces
+    double x = boot ? (double)d.terminal_qc[r * C + c] : 0.0;
+    if (cost) {
+      const uint8_t* vi = d.violations + r * H;
+      for (int t = len - 1; t >= 0; --t) x = look_cost_step((dn[t] ? 1u : 0u) | (vi[t] ? 2u : 0u), g, x);
+    } else {
+      const float* hv = d.constraint_values + r * H * C + c;
+      for (int t = len - 1; t >= 0; --t) {
+        const double h = look_hprime(hv[(size_t)t * C], cs, co);
+        x = look_reach_step(dn[t] != 0, h, dmul(one_minus_g, h), g, x);
       }
-      top = c == 0 ? x : look_max(top, x);
     }
-    const float sc = look_store(acc), ce = look_store(top);
-    const bool valid = sc == sc && ce == ce;
-    const int cls = valid ? (ce <= thr ? 0 : 1) : 2;
-    s_score[n] = sc;
-    s_cert[n] = ce;
-    s_cls[n] = (unsigned char)cls;
-    s_key[n] = cls == 0 ? sc : (cls == 1 ? -ce : 0.f);
-    if (d.score) d.score[r] = sc;
-    if (d.cert) d.cert[r] = ce;
+    top = c == 0 ? x : look_max(top, x);
   }
-  __syncthreads();
+  sc = look_store(acc);
+  ce = look_store(top);
+}
+
+// the float32 score and cert of candidate n of the workgroup's state as the order reads them
+// (LDS: score, cert, class, key) and as the caller gets them (score[r], cert[r])
+template <typename D>
+__device__ __forceinline__ void plan_row_keep(const D& d, size_t r, int n, float sc, float ce, float* s_score,
+                                              float* s_cert, float* s_key, unsigned char* s_cls) {
+  const bool valid = sc == sc && ce == ce;
+  const int cls = valid ? (ce <= d.threshold ? 0 : 1) : 2;
+  s_score[n] = sc;
+  s_cert[n] = ce;
+  s_cls[n] = (unsigned char)cls;
+  s_key[n] = cls == 0 ? sc : (cls == 1 ? -ce : 0.f);
+  if (d.score) d.score[r] = sc;
+  if (d.cert) d.cert[r] = ce;
+}
+
+// phases B-E of a refit kernel, from the candidates' score, cert, class and key in LDS (written
+// by every lane: the caller has synchronised). D: either refit descriptor.
+template <typename D>
+__device__ __forceinline__ void plan_order_refit(const D& d, double* s_wt, const float* s_score, const float* s_cert,
+                                                 const float* s_key, int* s_int, const unsigned char* s_cls) {
+  const int N = d.N, tid = threadIdx.x;
+  const int KA = d.K * d.A;
+  const size_t p = blockIdx.x;
+  const size_t row0 = p * (size_t)N;
 
   // ---- B. the order ---------------------------------------------------------------
   // every lane counts the classes itself (the same N reads as its ranks): no reduction
@@ -278,6 +279,117 @@ __global__ __launch_bounds__(PLAN_NT) void plan_refit_kernel(drpo_plan_refit_t d
   }
 }
 
+__global__ __launch_bounds__(PLAN_NT) void plan_refit_kernel(drpo_plan_refit_t d) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char plan_smem[];
+  const int N = d.N, H = d.H, tid = threadIdx.x;
+  double* s_w = reinterpret_cast<double*>(plan_smem);   // [H + 1]
+  double* s_wt = s_w + (H + 1);                         // [N]
+  float* s_score = reinterpret_cast<float*>(s_wt + N);  // [N]
+  float* s_cert = s_score + N;                          // [N]
+  float* s_key = s_cert + N;                            // [N]
+  int* s_int = reinterpret_cast<int*>(s_key + N);       // best, n_feasible, n_valid
+  unsigned char* s_cls = reinterpret_cast<unsigned char*>(s_int + 4);   // [N]
+  const size_t row0 = blockIdx.x * (size_t)N;
+
+  for (int e = tid; e <= H; e += PLAN_NT) s_w[e] = d.weights[e];
+  __syncthreads();
+
+  // ---- A. score and cert of every candidate -------------------------------------
+  for (int n = tid; n < N; n += PLAN_NT) {
+    float sc, ce;
+    plan_row_values(d, s_w, row0 + n, sc, ce);
+    plan_row_keep(d, row0 + n, n, sc, ce, s_score, s_cert, s_key, s_cls);
+  }
+  __syncthreads();
+  plan_order_refit(d, s_wt, s_score, s_cert, s_key, s_int, s_cls);
+}
+
+// ---------------------------------------------------------------------------
+// plan_refit_particles_kernel. plan_refit_kernel over G runs of the same candidates, one per
+// ensemble member, member-major [G][P * N]. One workgroup of 256 lanes per start state.
+//   A. One lane per candidate walks the members j = 0..G-1: the row's two chains at k = H on
+//      member j's tensors (plan_row_values), the float32 member score into the lane's own column
+//      of s_ms[G][256], the cert aggregated as it goes. Then the lane alone, on its column (no
+//      barrier: it reads what it wrote): the spread, and the score as the mean of the T lowest
+//      member scores, picked one after the other in (score, j) order so that the double sum runs
+//      in that order (T passes over the G values: no sorted copy, no private array).
+//   B-E. plan_order_refit on the aggregated float32 score and cert.
+// Plain stores, no atomics, no waits between workgroups.
+// ---------------------------------------------------------------------------
+__host__ __device__ constexpr size_t plan_particles_lds_bytes(int N, int H, int G) {
+  return plan_lds_bytes(N, H) + sizeof(float) * (size_t)G * PLAN_NT;
+}
+
+__global__ __launch_bounds__(PLAN_NT) void plan_refit_particles_kernel(drpo_plan_refit_particles_t d) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char plan_smem[];
+  const int N = d.N, H = d.H, G = d.G, T = d.score_tail, tid = threadIdx.x;
+  double* s_w = reinterpret_cast<double*>(plan_smem);   // [H + 1]
+  double* s_wt = s_w + (H + 1);                         // [N]
+  float* s_ms = reinterpret_cast<float*>(s_wt + N);     // [G][256]: a pass's member scores
+  float* s_score = s_ms + (size_t)G * PLAN_NT;          // [N]
+  float* s_cert = s_score + N;                          // [N]
+  float* s_key = s_cert + N;                            // [N]
+  int* s_int = reinterpret_cast<int*>(s_key + N);
+  unsigned char* s_cls = reinterpret_cast<unsigned char*>(s_int + 4);   // [N]
+  const size_t row0 = blockIdx.x * (size_t)N;
+  const size_t B = (size_t)d.P * N;
+  float* col = s_ms + tid;
+
+  for (int e = tid; e <= H; e += PLAN_NT) s_w[e] = d.weights[e];
+  __syncthreads();
+
+  // ---- A. member values and their aggregate, of every candidate --------------------
+  for (int n = tid; n < N; n += PLAN_NT) {
+    const size_t r = row0 + n;
+    double ctop = 0.0, csum = 0.0, ssum = 0.0;
+    bool nan = false;
+    for (int j = 0; j < G; ++j) {
+      float sc, ce;
+      plan_row_values(d, s_w, (size_t)j * B + r, sc, ce);
+      if (d.member_score) d.member_score[(size_t)j * B + r] = sc;
+      if (d.member_cert) d.member_cert[(size_t)j * B + r] = ce;
+      col[j * PLAN_NT] = sc;
+      nan |= sc != sc;
+      ssum = dadd(ssum, (double)sc);
+      csum = dadd(csum, (double)ce);
+      ctop = j == 0 ? (double)ce : look_max(ctop, (double)ce);
+    }
+    if (d.score_spread) {
+      const double m = ssum / (double)G;
+      double sq = 0.0;
+      for (int j = 0; j < G; ++j) {
+        const double dx = dadd((double)col[j * PLAN_NT], -m);
+        sq = dadd(sq, dmul(dx, dx));
+      }
+      d.score_spread[r] = look_store(sqrt(sq / (double)G));
+    }
+    // the T lowest member scores in (score, j) order: each pick is the least (score, j) above the last
+    double tail = 0.0;
+    float last_s = 0.f;
+    int last_j = -1;
+    for (int t = 0; t < T && !nan; ++t) {
+      float pick_s = 0.f;
+      int pick_j = -1;
+      for (int j = 0; j < G; ++j) {
+        const float s = col[j * PLAN_NT];
+        const bool after = last_j < 0 || s > last_s || (s == last_s && j > last_j);
+        if (after && (pick_j < 0 || s < pick_s)) {
+          pick_s = s;
+          pick_j = j;
+        }
+      }
+      tail = dadd(tail, (double)pick_s);
+      last_s = pick_s;
+      last_j = pick_j;
+    }
+    const float sc = nan ? __int_as_float(0x7FC00000) : look_store(tail / (double)T);
+    const float ce = look_store(d.cert_mode == 0 ? ctop : csum / (double)G);
+    plan_row_keep(d, r, n, sc, ce, s_score, s_cert, s_key, s_cls);
+  }
+  __syncthreads();
+  plan_order_refit(d, s_wt, s_score, s_cert, s_key, s_int, s_cls);
+}
+
 }  // namespace drpo
 
 using namespace drpo;
@@ -347,8 +459,9 @@ DRPO_API int drpo_plan_shift(const drpo_plan_shift_t* d, drpo_stream_t stream_) 
   return DRPO_OK;
 }
 
-DRPO_API int drpo_plan_refit(const drpo_plan_refit_t* d, drpo_stream_t stream_) {
-  const char* who = "drpo_plan_refit";
+// what drpo_plan_refit and drpo_plan_refit_particles refuse alike (D: either descriptor)
+template <typename D>
+static int plan_refit_check(const char* who, const D* d) {
   DRPO_REQUIRE(d, "%s: null descriptor", who);
   DRPO_REQUIRE(d->P >= 0, "%s: P=%d is negative", who, d->P);
   DRPO_REQUIRE(d->N >= 2 && d->N <= DRPO_PLAN_MAX_CANDIDATES, "%s: N=%d outside 2..%d", who, d->N,
@@ -375,8 +488,33 @@ DRPO_API int drpo_plan_refit(const drpo_plan_refit_t* d, drpo_stream_t stream_) 
   DRPO_REQUIRE(d->mean_out && d->std_out && d->best_actions && d->best && d->n_feasible && d->best_score &&
                    d->best_cert && d->best_feasible,
                "%s: null per-state output pointer", who);
+  return DRPO_OK;
+}
+
+DRPO_API int drpo_plan_refit(const drpo_plan_refit_t* d, drpo_stream_t stream_) {
+  if (const int rc = plan_refit_check("drpo_plan_refit", d)) return rc;
   if (d->P == 0) return DRPO_OK;
   plan_refit_kernel<<<(unsigned)d->P, PLAN_NT, plan_lds_bytes(d->N, d->H), (hipStream_t)stream_>>>(*d);
   DRPO_LAUNCH_CHECK("plan_refit");
+  return DRPO_OK;
+}
+
+DRPO_API int drpo_plan_refit_particles(const drpo_plan_refit_particles_t* d, drpo_stream_t stream_) {
+  const char* who = "drpo_plan_refit_particles";
+  if (const int rc = plan_refit_check(who, d)) return rc;
+  DRPO_REQUIRE(d->G >= 1 && d->G <= DRPO_PLAN_MAX_PARTICLES, "%s: G=%d outside 1..%d", who, d->G,
+               DRPO_PLAN_MAX_PARTICLES);
+  DRPO_REQUIRE(d->score_tail >= 1 && d->score_tail <= d->G, "%s: score_tail=%d outside 1..G=%d", who, d->score_tail,
+               d->G);
+  DRPO_REQUIRE(d->cert_mode == 0 || d->cert_mode == 1, "%s: cert_mode %d (0 max, 1 mean)", who, d->cert_mode);
+  DRPO_REQUIRE((int64_t)d->G * d->P * d->N <= INT32_MAX, "%s: G*P*N = %lld rows exceed int32", who,
+               (long long)((int64_t)d->G * d->P * d->N));
+  // (N <= 1024, H <= 128, G <= 32: at most 55,320 bytes, under the 64 KB a workgroup may take)
+  static_assert(plan_particles_lds_bytes(DRPO_PLAN_MAX_CANDIDATES, DRPO_ROLLOUT_FUSED_MAX_H, DRPO_PLAN_MAX_PARTICLES) <=
+                    65536, "plan_refit_particles: dynamic LDS beyond 64 KB");
+  if (d->P == 0) return DRPO_OK;
+  plan_refit_particles_kernel<<<(unsigned)d->P, PLAN_NT, plan_particles_lds_bytes(d->N, d->H, d->G),
+                                (hipStream_t)stream_>>>(*d);
+  DRPO_LAUNCH_CHECK("plan_refit_particles");
   return DRPO_OK;
 }

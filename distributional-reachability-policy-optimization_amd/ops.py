@@ -212,6 +212,34 @@ def _traj_members(model, members, H):
     return [int(m) for m in mem]
 
 
+def _particles_request(model, particles, members, noise):
+    """imagine(particles=) / plan(particles=) checked: None (off), else the member index of every
+    particle, 1..PLAN_MAX_PARTICLES ints ('elites': every elite in _elite_inds order; repeats are
+    allowed). Not with ``members`` (a particle is a member) or a recorded tape."""
+    if particles is None:
+        return None
+    if members is not None:
+        raise ValueError('particles together with members: a particle keeps its own member for the whole horizon')
+    if noise is not None and noise.parity:
+        raise ValueError('particles with a recorded tape: a tape fixes the members and the draws of one run')
+    E = model.ensemble_size
+    if isinstance(particles, str):
+        if particles != 'elites':
+            raise ValueError(f"particles: {particles!r} (None, 'elites' or 1..{PLAN_MAX_PARTICLES} member indices)")
+        ms = list(model._elite_inds)
+    else:
+        try:
+            ms = list(particles)
+        except TypeError:
+            raise ValueError(f"particles: {particles!r} (None, 'elites' or 1..{PLAN_MAX_PARTICLES} member indices)")
+    if not 1 <= len(ms) <= PLAN_MAX_PARTICLES:
+        raise ValueError(f'particles: {len(ms)} members (1..{PLAN_MAX_PARTICLES})')
+    for m in ms:
+        if not isinstance(m, (int, np.integer)) or isinstance(m, bool) or not 0 <= m < E:
+            raise ValueError(f'particles: {m!r} is not a member index of an ensemble of {E}')
+    return [int(m) for m in ms]
+
+
 def _fill_call(d, marr, alg, noise, start, members, eps_a, eps_m, ctr, engine, eps_layout, timer):
     """The per-call fields of a cached descriptor (_rollout_static), for drpo_rollout and the
     drpo_rollout_trajectories* calls alike. ``start``: _start_states' tuple. ``timer``: an
@@ -351,7 +379,9 @@ class ImaginedRollout:
       mask [B, H] bool           t < lengths[i]
 
     Everything at or beyond a row's length is zero. ``members`` is the ensemble member
-    of each step. members='each' stacks the runs on a new leading axis. ``given_steps``:
+    of each step. members='each' stacks the runs on a new leading axis, and so does particles=
+    (one run per particle, a member index each; ``particle_launches`` then says how many horizon
+    launches made them, None otherwise). ``given_steps``:
     the leading steps whose actions the caller gave (0: every action is the policy's),
     executed as given (imagine(actions=)) or proposed to the shield (imagine(proposals=):
     ``actions`` then holds what the shield let the row execute, ``certificate`` at those steps
@@ -408,6 +438,7 @@ class ImaginedRollout:
         assert set(tensors) == set(self.TENSORS)
         self.members = members
         self.given_steps = given_steps
+        self.particle_launches = None
         self.__dict__.update(self._UNSET, **tensors)
 
     def set_group(self, group, **values):
@@ -439,6 +470,12 @@ class ImaginedRollout:
                 out.set_group(group, **{k: torch.stack([getattr(r, k) for r in runs]) for k in per_run},
                               **{k: getattr(runs[0], k) for k in scalars})
         return out
+
+    def flat_runs(self):
+        """Of G stacked runs (members='each', particles=): the core tensors with the leading
+        axes [G, B] merged to G * B rows, run-major, as views (no copy); no optional group."""
+        return ImaginedRollout(self.members, self.given_steps,
+                               **{k: getattr(self, k).flatten(0, 1) for k in self.TENSORS})
 
 
 class EnsembleSpread:
@@ -876,6 +913,7 @@ def lookahead(alg, policy, im, kind, gamma, *, reward_scale=None, alive_bonus=No
 # library loads: tests/test_plan_checks.py pins them to drpo_abi_const)
 PLAN_MAX_CANDIDATES = 1024
 PLAN_SITE = 0x91a7
+PLAN_MAX_PARTICLES = 32
 
 
 class PlanResult:
@@ -905,20 +943,35 @@ class PlanResult:
     How the call drew and started, None from a caller that does not say (MPC_FIELDS):
       noise_beta                 the lag-1 correlation of the candidates' noise (0.0: white)
       warm_started               whether it started from a previous result (plan(warm_start=))
-      shift                      the steps that warm start dropped, None for a cold start"""
+      shift                      the steps that warm start dropped, None for a cold start
+
+    Under plan(particles=) every candidate ran under each of G ensemble members, and ``scores`` /
+    ``certificates`` / ``ranks``, the best row and the history are of the aggregate over them
+    (drpo_plan_refit_particles). ``imagined`` has the leading axis G; executed_actions is
+    [G, P, H, A] and interventions [G, P, H] (the best row under each member), safe_action
+    executed_actions[0, :, 0]: step 0 is the same in every group. Six more, None otherwise
+    (PARTICLE_FIELDS):
+      particles                  the member index of each particle, G ints
+      risk, cert_risk            as given: 'mean', 'worst' or ('cvar', alpha); 'max' or 'mean'
+      member_scores, member_certificates [G, P, N]   each member's score and certificate
+      score_spread [P, N]        the members' population std of a candidate's score"""
     FIELDS =('actions', 'action', 'score', 'certificate', 'feasible', 'n_feasible', 'mean', 'std', 'history_score',
               'history_certificate', 'history_feasible', 'candidates', 'scores', 'certificates', 'ranks', 'imagined',
               'threshold', 'lookahead_kind')
     FILTER_FIELDS = ('executed_actions', 'safe_action', 'interventions', 'filter_threshold')
 
     MPC_FIELDS = ('noise_beta', 'warm_started', 'shift')
+    PARTICLE_FIELDS = ('particles', 'risk', 'cert_risk', 'member_scores', 'member_certificates', 'score_spread')
 
     def __init__(self, executed_actions=None, safe_action=None, interventions=None, filter_threshold=None,
-                 noise_beta=None, warm_started=None, shift=None, **fields):
+                 noise_beta=None, warm_started=None, shift=None, particles=None, risk=None, cert_risk=None,
+                 member_scores=None, member_certificates=None, score_spread=None, **fields):
         assert set(fields) == set(self.FIELDS), sorted(set(fields) ^ set(self.FIELDS))
         self.__dict__.update(fields, executed_actions=executed_actions, safe_action=safe_action,
                              interventions=interventions, filter_threshold=filter_threshold,
-                             noise_beta=noise_beta, warm_started=warm_started, shift=shift)
+                             noise_beta=noise_beta, warm_started=warm_started, shift=shift,
+                             particles=particles, risk=risk, cert_risk=cert_risk, member_scores=member_scores,
+                             member_certificates=member_certificates, score_spread=score_spread)
 
 
 def plan_sample(mean, std, incumbent, candidates, seed, ctr, lo=-1.0, hi=1.0, corr=0.0):
@@ -1029,18 +1082,27 @@ class PlanController:
 
 def plan_refit(alg, im, terminal_q, terminal_qc, cand, mean, std, gamma, *, candidates, threshold, elites,
                temperature, momentum, min_std, reward_scale=None, alive_bonus=None, constraint_scale=None,
-               constraint_offset=None):
+               constraint_offset=None, particles=None, score_tail=None, cert_mode=0):
     """Scores, ranks and refits one planning iteration (drpo_plan_refit) on the run ``im`` of
     P * N rows under ``cand`` [P * N, K, A], with the terminal critics' values of
     _terminal_critics. mean / std [P, K, A] are read, not written. Returns a dict of fresh
     tensors: mean, std, best_actions [P, K, A]; best, n_feasible (int32), best_score, best_cert,
-    best_feasible (bool) [P]; score, cert, rank (int32), weight [P, N]."""
-    from ._abi import PlanRefit
+    best_feasible (bool) [P]; score, cert, rank (int32), weight [P, N].
+    particles=G: ``im`` and the terminal values hold G runs of the P * N rows, run-major
+    (ImaginedRollout.flat_runs of the stacked runs), and the launch is drpo_plan_refit_particles:
+    the score is the mean of the ``score_tail`` (default G) lowest member scores, the cert the
+    members' maximum (cert_mode 0) or mean (1). Three more tensors come back: member_score,
+    member_cert [G, P, N] and score_spread [P, N]."""
+    from ._abi import PlanRefit, PlanRefitParticles
     sol = alg.solver
     B, H = im.rewards.shape
     N = int(candidates)
     P, K, A = mean.shape
     C = sol.constraint_critic.output_dim
+    G = None if particles is None else int(particles)
+    if G is not None:
+        assert G >= 1 and B == G * P * N, 'plan_refit: particles runs of P * N rows each'
+        B //= G
     assert B == P * N and tuple(cand.shape) == (B, K, A), 'plan_refit: cand is [P * N, K, A]'
     dev = im.rewards.device
     w = torch.as_tensor(np.power(np.float64(gamma), np.arange(H + 1, dtype=np.float64))).to(dev)
@@ -1054,22 +1116,30 @@ def plan_refit(alg, im, terminal_q, terminal_qc, cand, mean, std, gamma, *, cand
            'best_cert': torch.empty(P, device=dev), 'best_feasible': torch.empty(P, dtype=torch.uint8, device=dev),
            'score': torch.empty(P, N, device=dev), 'cert': torch.empty(P, N, device=dev),
            'rank': torch.empty(P, N, dtype=i32, device=dev), 'weight': torch.empty(P, N, device=dev)}
-    d = PlanRefit()
+    d = PlanRefit() if G is None else PlanRefitParticles()
+    if G is not None:
+        out.update(member_score=torch.empty(G, P, N, device=dev), member_cert=torch.empty(G, P, N, device=dev),
+                   score_spread=torch.empty(P, N, device=dev))
+        d.G, d.score_tail, d.cert_mode = G, G if score_tail is None else int(score_tail), int(cert_mode)
     d.P, d.N, d.H, d.K, d.A, d.C, d.elites = P, N, H, K, A, C, int(elites)
     d.mode, d.gamma = 0 if sol.constrained_fcn == 'reachability' else 1, float(gamma)
     for k, v in _lookahead_scales(alg, reward_scale, alive_bonus, constraint_scale, constraint_offset).items():
         setattr(d, k, v)
     d.temperature, d.momentum, d.min_std, d.threshold = float(temperature), float(momentum), float(min_std), threshold
     if d.mode == 0:
-        assert tuple(im.constraint_values.shape) == (B, H, C), 'constraint_values: one column per critic output'
+        assert tuple(im.constraint_values.shape) == (im.rewards.shape[0], H, C), \
+            'constraint_values: one column per critic output'
     (d.rewards, d.constraint_values, d.dones, d.violations, d.lengths, d.terminated, d.terminal_q, d.terminal_qc,
      d.cand, d.mean_in, d.std_in) = (t.data_ptr() for t in keep)
     d.weights = w.data_ptr()
     d.mean_out, d.std_out = out['mean'].data_ptr(), out['std'].data_ptr()
-    for k in ('best_actions', 'best', 'n_feasible', 'best_score', 'best_cert', 'best_feasible', 'score', 'cert',
-              'rank', 'weight'):
-        setattr(d, k, out[k].data_ptr())
-    _lib.check(_lib.lib().drpo_plan_refit(ctypes.byref(d), _lib.stream()), 'plan_refit')
+    for k in out:
+        if k not in ('mean', 'std'):
+            setattr(d, k, out[k].data_ptr())
+    if G is None:
+        _lib.check(_lib.lib().drpo_plan_refit(ctypes.byref(d), _lib.stream()), 'plan_refit')
+    else:
+        _lib.check(_lib.lib().drpo_plan_refit_particles(ctypes.byref(d), _lib.stream()), 'plan_refit_particles')
     out['best_feasible'] = out['best_feasible'].view(torch.bool)
     return out
 

@@ -265,7 +265,8 @@ class SMBPO(Configurable, Module):
 
     def imagine(self, states=None, policy=None, horizon=None, *, members=None, deterministic=False,
                 model_noise=True, discount=None, noise=None, actions=None, shield=None,
-                shield_uncertainty=None, uncertainty=None, halt=None, lookahead=None, proposals=None):
+                shield_uncertainty=None, uncertainty=None, halt=None, lookahead=None, proposals=None,
+                particles=None):
         """What the model predicts happens from ``states`` under ``policy``: the rollout of
         src/smbpo.py:229-249 kept per trajectory (ops.ImaginedRollout: row i of every tensor
         is the trajectory from start state i), on the fused horizon kernel. Nothing of the
@@ -277,6 +278,13 @@ class SMBPO(Configurable, Module):
         members    None: one random elite per step, as ``rollout``; an int: that ensemble
                    member at every step; H ints; 'each': one launch per elite member with
                    common draws (same noise counter), stacked in _elite_inds order.
+        particles  None: off. The trajectories under each of G ensemble members, a particle
+                   each: 'elites' (every elite in _elite_inds order: members='each' bit for
+                   bit) or 1..32 member indices, repeats allowed. A particle keeps its member
+                   for the whole horizon and every particle sees the same draws (one noise
+                   counter, as 'each'). The result has 'each''s shape, a leading axis G on
+                   every tensor, and ``particle_launches``, the horizon launches that made it
+                   (G: one per particle). Not with ``members`` or a recorded tape (ValueError).
         deterministic   the policy's mean action; model_noise=False: the member's mean
                    prediction. (Recorded-draw inputs of the kernel: zeros for the
                    switched-off draw, device-generated normals for the other.)
@@ -399,8 +407,9 @@ class SMBPO(Configurable, Module):
         if proposals is not None:
             proposals = torch.as_tensor(proposals, dtype=torch.float32).to(self.device).contiguous()
 
-        each = isinstance(members, str)
-        if each and members != 'each':
+        parts = ops._particles_request(self.model_ensemble, particles, members, noise)
+        each = isinstance(members, str) or parts is not None
+        if isinstance(members, str) and members != 'each':
             raise ValueError(f"members: {members!r} (None, an int, {H} ints or 'each')")
         # the shield's shorthand as ops' threshold and candidates; ops._shield_request refuses and defaults
         kw = {'actions': actions, 'shield_uncertainty': shield_uncertainty}
@@ -442,7 +451,10 @@ class SMBPO(Configurable, Module):
                 ops.lookahead(self, policy, im, look, gamma)
             return im
         if each:
-            im = ops.ImaginedRollout.stack([run(int(m)) for m in self.model_ensemble._elite_inds])
+            ms = self.model_ensemble._elite_inds if parts is None else parts
+            im = ops.ImaginedRollout.stack([run(int(m)) for m in ms])
+            if parts is not None:
+                im.particle_launches = len(parts)
         else:
             im = run(members)
         if uncertainty and halt_thr is None:
@@ -464,7 +476,8 @@ class SMBPO(Configurable, Module):
     def plan(self, states, horizon=None, *, candidates=64, iterations=4, steps=None, elites=None,
              temperature=float('inf'), momentum=0.0, init=None, init_std=0.5, min_std=0.05, threshold=None,
              lookahead=True, policy=None, members=None, model_noise=False, discount=None, noise=None,
-             safety_filter=None, warm_start=None, shift=1, reset=None, tail=None, warm_std=None, noise_beta=0.0):
+             safety_filter=None, warm_start=None, shift=1, reset=None, tail=None, warm_std=None, noise_beta=0.0,
+             particles=None, risk='mean', cert_risk='max'):
         """The best of sampled action sequences from each of the P ``states``, by the model and the
         two critics: an MPPI / CEM planner whose score is imagine(actions=, lookahead=)'s
         value_lookahead[:, H] and whose constraint is its certificate_lookahead[:, H] (the
@@ -496,7 +509,28 @@ class SMBPO(Configurable, Module):
         lookahead    True: the constraint critic's mean; 'bound': its distributional bound.
         policy, members, model_noise, discount   as imagine's. members=None draws one elite per
                      step anew in every iteration, so scores of different iterations are then
-                     not comparable; an int or H ints fix the model. Not 'each'.
+                     not comparable; an int or H ints fix the model. Not 'each': that is
+                     ``particles``.
+        particles    None: off, the candidates are scored under one model, as above. Else
+                     planning over the ensemble: 'elites' or 1..32 member indices, as imagine's
+                     ``particles``. Every iteration's run is imagine(particles=): each candidate
+                     under each of the G members with common draws, a particle keeping its member
+                     for the whole horizon; the critics close the G * P * N rows at once and one
+                     launch (drpo_plan_refit_particles) aggregates the members' scores and
+                     certificates per candidate, then orders and refits on the aggregate as
+                     before. Not with ``members``. With fixed particles and model_noise=False
+                     the aggregate is a function of the state and the candidate, so the
+                     incumbent's key still never decreases. init='policy' takes the policy's
+                     trajectory under the first particle. The result carries ``particles``,
+                     ``risk``, ``cert_risk``, ``member_scores``, ``member_certificates`` and
+                     ``score_spread``; its ``imagined`` has the leading axis G, and under
+                     safety_filter so have ``executed_actions`` and ``interventions``
+                     (``safe_action`` is the first group's: step 0 is the same in all of them).
+        risk         of the score over the particles: 'mean' (every member counts alike), 'worst'
+                     (the lowest member score) or ('cvar', alpha), 0 < alpha <= 1: the mean of
+                     the max(1, ceil(alpha * G)) lowest member scores. cert_risk: 'max' (every
+                     member must certify: the largest member certificate is compared with
+                     ``threshold``) or 'mean'. Both need ``particles``.
         noise        default a stream private to plan, derived from the trainer's seed. Each
                      sample launch takes one noise.next(), and imagine runs on the same object.
         safety_filter   None / False: the candidates are executed as given, as above. Else the
@@ -547,6 +581,7 @@ class SMBPO(Configurable, Module):
         H, N, K, P, A = q['H'], q['N'], q['K'], q['P'], q['A']
         states, init, elites, threshold, look, filt = (q[k] for k in ('states', 'init', 'elites', 'threshold', 'look',
                                                                       'filt'))
+        parts = q['parts']
 
         # the device work
         dev = self.device
@@ -558,6 +593,11 @@ class SMBPO(Configurable, Module):
             noise = self._plan_noise
         gamma = float(self.solver.discount if discount is None else discount)
         run = dict(members=members, deterministic=True, model_noise=model_noise, discount=gamma, noise=noise)
+        refit = {}
+        if parts is not None:     # (off: imagine and plan_refit see the calls they saw before)
+            first = dict(run, members=parts[0])
+            run = dict(run, particles=parts)
+            refit = dict(particles=len(parts), score_tail=q['score_tail'], cert_mode=q['cert_mode'])
         if warm_start is not None:
             def on_dev(x, dtype=torch.float32):
                 return None if x is None else torch.as_tensor(x, dtype=dtype).to(dev).contiguous()
@@ -569,7 +609,7 @@ class SMBPO(Configurable, Module):
             if init is None:
                 mean = torch.zeros(P, K, A, device=dev)
             elif isinstance(init, str):
-                mean = self.imagine(states, policy, H, **run).actions[:, :K].contiguous()
+                mean = self.imagine(states, policy, H, **(run if parts is None else first)).actions[:, :K].contiguous()
             else:
                 mean = init.to(dev).contiguous()
             std = torch.full((P, K, A), float(init_std), device=dev)
@@ -583,19 +623,25 @@ class SMBPO(Configurable, Module):
                 im = self.imagine(tiled, policy, H, actions=cand, **run)
             else:     # the candidates as proposals: scored on what the shield lets them run
                 im = self.imagine(tiled, policy, H, proposals=cand, shield=filt, **run)
-            terminal_q, terminal_qc = ops._terminal_critics(self, policy, im, look)
-            fit = ops.plan_refit(self, im, terminal_q, terminal_qc, cand, mean, std, gamma, candidates=N,
+            rows = im if parts is None else im.flat_runs()      # the G * P * N rows, run-major
+            terminal_q, terminal_qc = ops._terminal_critics(self, policy, rows, look)
+            fit = ops.plan_refit(self, rows, terminal_q, terminal_qc, cand, mean, std, gamma, candidates=N,
                                  threshold=threshold, elites=elites, temperature=temperature, momentum=momentum,
-                                 min_std=min_std)
+                                 min_std=min_std, **refit)
             mean, std, incumbent = fit['mean'], fit['std'], fit['best_actions']
             history.append((fit['best_score'], fit['best_cert'], fit['best_feasible']))
         filtered = {}
         if filt is not None:
             # the best row's filtered trajectory, gathered on the device (row p * N + best[p])
             rows = torch.arange(P, device=dev, dtype=torch.int64) * N + fit['best'].to(torch.int64)
-            executed = im.actions.index_select(0, rows)
-            filtered = dict(executed_actions=executed, safe_action=executed[:, 0],
-                            interventions=im.interventions.index_select(0, rows), filter_threshold=im.shield_threshold)
+            ax = 0 if parts is None else 1                      # (particles: the best row under each member)
+            executed = im.actions.index_select(ax, rows)
+            filtered = dict(executed_actions=executed,
+                            safe_action=executed[:, 0] if parts is None else executed[0, :, 0],
+                            interventions=im.interventions.index_select(ax, rows), filter_threshold=im.shield_threshold)
+        if parts is not None:
+            filtered.update(particles=parts, risk=risk, cert_risk=cert_risk, member_scores=fit['member_score'],
+                            member_certificates=fit['member_cert'], score_spread=fit['score_spread'])
         return ops.PlanResult(
             **filtered, noise_beta=float(noise_beta), warm_started=warm_start is not None,
             shift=None if warm_start is None else shift,
@@ -609,7 +655,8 @@ class SMBPO(Configurable, Module):
 
     def _plan_checks(self, states, horizon, *, candidates, iterations, steps, elites, temperature, momentum, init,
                      init_std, min_std, threshold, lookahead, policy, members, model_noise, discount, noise,
-                     safety_filter, warm_start, shift, reset, tail, warm_std, noise_beta, controller=False):
+                     safety_filter, warm_start, shift, reset, tail, warm_std, noise_beta, particles, risk, cert_risk,
+                     controller=False):
         """Every refusal of plan's arguments, before any device work; returns what they resolve
         to. controller=True (SMBPO.mpc, which has no states yet): shift, tail and warm_std are
         checked as far as they can be without P and without a warm_start."""
@@ -655,6 +702,20 @@ class SMBPO(Configurable, Module):
             raise ValueError(f"members: {members!r} (None, an int or {H} ints; 'each' is not for plan)")
         if noise is not None and noise.parity:
             raise ValueError('plan with a recorded tape: a tape fixes the draws of one rollout, not of a planner')
+        # the particles as imagine's, and how their scores and certificates aggregate
+        parts = ops._particles_request(self.model_ensemble, particles, members, noise)
+        cvar = isinstance(risk, (tuple, list)) and len(risk) == 2 and risk[0] == 'cvar' and is_num(risk[1]) and \
+            0 < risk[1] <= 1
+        if not (cvar or isinstance(risk, str) and risk in ('mean', 'worst')):
+            raise ValueError(f"risk: {risk!r} ('mean', 'worst' or ('cvar', alpha) with 0 < alpha <= 1)")
+        if not (isinstance(cert_risk, str) and cert_risk in ('max', 'mean')):
+            raise ValueError(f"cert_risk: {cert_risk!r} ('max' or 'mean')")
+        if parts is None and (risk != 'mean' or cert_risk != 'max'):
+            raise ValueError('risk / cert_risk without particles: they say how the particles aggregate')
+        score_tail = None
+        if parts is not None:
+            G = len(parts)
+            score_tail = G if risk == 'mean' else 1 if risk == 'worst' else max(1, int(np.ceil(float(risk[1]) * G)))
         # the filter as imagine's ``shield`` (None: off), every spelling checked here
         filt = None if safety_filter is None or safety_filter is False else safety_filter
         if isinstance(filt, (str, tuple, list)):
@@ -718,7 +779,7 @@ class SMBPO(Configurable, Module):
             if tail is not None and not (is_array(tail) and tuple(tail.shape) == (P, A)):
                 raise ValueError(f'tail: {tail!r} (None or a [{P}, {A}] tensor)')
         return dict(H=H, N=N, K=K, P=P, A=A, states=states, init=init, elites=elites, threshold=threshold, look=look,
-                    filt=filt)
+                    filt=filt, parts=parts, score_tail=score_tail, cert_mode=0 if cert_risk == 'max' else 1)
 
     def mpc(self, *, fallback='safe', shift=1, warm_std=None, **plan_kwargs):
         """A receding-horizon controller on plan (an ops.PlanController): ``act(states)`` plans
@@ -729,7 +790,7 @@ class SMBPO(Configurable, Module):
                      whatever its certificate.
         shift, warm_std   as plan's, of every warm start.
         plan_kwargs  plan's own (horizon, candidates, iterations, noise_beta, safety_filter,
-                     noise, ...), checked here once by plan's checks; not states, init,
+                     noise, particles, risk, cert_risk, ...), checked here once by plan's checks; not states, init,
                      warm_start or reset, which act() supplies. A ``tail`` [P, A] also starts
                      the cold plans.
         sampling.sample_episodes_batched(controller=) and evaluate(controller=) run one on the

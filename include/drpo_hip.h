@@ -92,7 +92,8 @@ enum {
   DRPO_MLP_MULTI_MAX_SLOTS = 16,  /* (job, net) workgroup slots of such a launch */
   DRPO_MLP_FB_MAX_JOBS = 4,       /* jobs of one drpo_mlp_fb_multi */
   DRPO_PLAN_MAX_CANDIDATES = 1024, /* candidates per start state of drpo_plan_sample / drpo_plan_refit */
-  DRPO_PLAN_SITE = 0x91a7         /* the Philox site (third counter word) of drpo_plan_sample's draws */
+  DRPO_PLAN_SITE = 0x91a7,        /* the Philox site (third counter word) of drpo_plan_sample's draws */
+  DRPO_PLAN_MAX_PARTICLES = 32    /* runs (ensemble members) of one drpo_plan_refit_particles */
 };
 
 /* ---------------------------------------------------------------- library */
@@ -567,6 +568,73 @@ typedef struct {
 } drpo_plan_refit_t;
 
 int drpo_plan_refit(const drpo_plan_refit_t* d /* host */, drpo_stream_t stream);
+
+/* drpo_plan_refit_particles: drpo_plan_refit over G runs of the same candidates, one per
+ * ensemble member (particle): planning over the ensemble, risk-aware. Every per-row input is
+ * member-major [G][B][...], B = P * N (run j's row r at flat row j * B + r), the layout that G
+ * runs stacked leave; cand stays [B][K][A]. One workgroup serves one start state.
+ * Member values. member_score[j][r] and member_cert[j][r] are exactly score[r] and cert[r] of
+ *    drpo_plan_refit's step a on run j's tensors (the same operations), each rounded to float32
+ *    once, a NaN stored as 0x7FC00000. From them, as stored:
+ * Score. With T = score_tail (1..G), order the members by (member score ascending, j ascending);
+ *    score[r] is the double sum of the first T in that order, added in that order, nothing
+ *    contracted, divided by (double)T and rounded to float32 once. T = 1: the worst member;
+ *    T = G: the mean over all members; between them the mean of the lower tail (CVaR). A NaN
+ *    member score makes the score NaN (0x7FC00000).
+ * Cert. cert_mode 0: the maximum over j = 0..G-1 (a NaN stays): every member must certify.
+ *    cert_mode 1: the double sum in j order divided by (double)G, rounded to float32 once.
+ * Spread. With m = (sum_j s_j) / G in j order, score_spread[r] = sqrt(sum_j (s_j - m)^2 / G) in
+ *    ordered double arithmetic, stored as float32 (a NaN as 0x7FC00000).
+ * Steps b-e are drpo_plan_refit's on the aggregated float32 score and cert (the same code).
+ * With G = 1 every output is bit-equal to drpo_plan_refit's (score_spread is 0 or NaN).
+ * Every element of every given output is written; nothing else is. DRPO_EINVAL before any
+ * launch: whatever drpo_plan_refit refuses, G outside 1..DRPO_PLAN_MAX_PARTICLES, score_tail
+ * outside 1..G, a cert_mode other than 0 / 1, G * P * N beyond int32. P == 0: DRPO_OK without a
+ * launch. */
+typedef struct {
+  int P, N, H, K, A, C, mode, elites;
+  double gamma;
+  double reward_scale, alive_bonus, constraint_scale, constraint_offset;
+  double temperature, momentum, min_std;
+  float threshold;
+  int pad_;
+  /* inputs, device, as drpo_plan_refit_t's with G * B rows where it has B */
+  const float* rewards;            /* [G][B][H] */
+  const float* constraint_values;  /* [G][B][H][C] */
+  const uint8_t* dones;            /* [G][B][H] */
+  const uint8_t* violations;       /* [G][B][H]; read in mode 1 only, may be NULL in mode 0 */
+  const int32_t* lengths;          /* [G][B]; clamped to 0..H as read */
+  const uint8_t* terminated;       /* [G][B] */
+  const double* weights;           /* [H + 1]: gamma^k */
+  const float* terminal_q;         /* [G][B] */
+  const float* terminal_qc;        /* [G][B][C] */
+  const float* cand;               /* [B][K][A] */
+  const float* mean_in;            /* [P][K][A] */
+  const float* std_in;             /* [P][K][A] */
+  /* outputs, device, as drpo_plan_refit_t's: per state, and per row of the aggregate */
+  float* mean_out;                 /* [P][K][A] */
+  float* std_out;                  /* [P][K][A] */
+  float* best_actions;             /* [P][K][A] */
+  int32_t* best;                   /* [P] */
+  int32_t* n_feasible;             /* [P] */
+  float* best_score;               /* [P] */
+  float* best_cert;                /* [P] */
+  uint8_t* best_feasible;          /* [P] */
+  float* score;                    /* [B], may be NULL */
+  float* cert;                     /* [B], may be NULL */
+  int32_t* rank;                   /* [B], may be NULL */
+  float* weight;                   /* [B], may be NULL */
+  /* the particles */
+  int G;                           /* runs, 1..DRPO_PLAN_MAX_PARTICLES */
+  int score_tail;                  /* T: the score is the mean of the T lowest member scores */
+  int cert_mode;                   /* 0: max over the members; 1: their mean */
+  int pad2_;
+  float* member_score;             /* [G][B], may be NULL */
+  float* member_cert;              /* [G][B], may be NULL */
+  float* score_spread;             /* [B], may be NULL */
+} drpo_plan_refit_particles_t;
+
+int drpo_plan_refit_particles(const drpo_plan_refit_particles_t* d /* host */, drpo_stream_t stream);
 
 /* batched env constraint functions, e.g. PointRobot.get_constraint_values /
  * check_violation / check_done (src/env/point_robot.py:96-131); h is [n][C] */
