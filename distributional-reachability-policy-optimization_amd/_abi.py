@@ -73,6 +73,15 @@ class RolloutLookahead(ctypes.Structure):
                 ('terminal_qc', P), ('value', P), ('certificate', P)]
 
 
+class RolloutAdjoint(ctypes.Structure):
+    """drpo_rollout_adjoint_t"""
+    _fields_ = [('B', c_int64), ('H', c_int), ('S', c_int), ('A', c_int), ('Hm', c_int), ('E', c_int),
+                ('mW1', P), ('mb1', P), ('mW2', P), ('mb2', P), ('dW1', P), ('db1', P),
+                ('mT1', P), ('mT2', P), ('dT1', P), ('dT2', P), ('norm_mean', P), ('norm_std', P),
+                ('members', POINTER(c_int)), ('states', P), ('actions', P), ('lengths', P),
+                ('g_states', P), ('g_rewards', P), ('grad_actions', P), ('grad_start', P)]
+
+
 PLAN_MAX_CANDIDATES = 1024     # DRPO_PLAN_MAX_CANDIDATES
 PLAN_SITE = 0x91a7             # DRPO_PLAN_SITE
 
@@ -203,6 +212,7 @@ PROTOTYPES = {
     'drpo_rollout_trajectories_cut': (c_int, [POINTER(RolloutDesc), POINTER(RolloutCut), POINTER(RolloutTraj), P]),
     'drpo_rollout_staging_offsets': (c_int, [c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     'drpo_rollout_lookahead': (c_int, [POINTER(RolloutLookahead), P]),
+    'drpo_rollout_adjoint': (c_int, [POINTER(RolloutAdjoint), P]),
     'drpo_plan_sample': (c_int, [POINTER(PlanSample), P]),
     'drpo_plan_sample_ar': (c_int, [POINTER(PlanSampleAr), P]),
     'drpo_plan_shift': (c_int, [POINTER(PlanShift), P]),
@@ -373,4 +383,5 @@ PROTOTYPES.update({
     'drpo_mlp_fb_ok': (c_int, [c_int] + [POINTER(MlpNet)] * 6 + [c_int]),
     'drpo_ens_fit_paths': (c_int, [POINTER(MlpFwd), POINTER(MlpBwd), POINTER(EnsUpstream)]),
     'drpo_rollout_engine': (c_int, [POINTER(RolloutDesc)]),
+    'drpo_rollout_adjoint_ok': (c_int, [c_int, c_int, c_int]),
 })

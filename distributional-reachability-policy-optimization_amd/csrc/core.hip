@@ -19,7 +19,7 @@ void drpo_set_error(const char* fmt, ...) {
 
 DRPO_API const char* drpo_last_error(void) { return g_err; }
 
-DRPO_API int drpo_version(void) { return 16; }
+DRPO_API int drpo_version(void) { return 17; }
 
 // HIP event helpers so hosts without a HIP binding (ctypes/cgo/JNI) can time
 // individual kernels on the stream they run on. The events are timing-only: created
@@ -86,6 +86,7 @@ DRPO_API int64_t drpo_abi_sizeof(const char* name) {
       {"drpo_plan_sample_t", sizeof(drpo_plan_sample_t)},     {"drpo_plan_refit_t", sizeof(drpo_plan_refit_t)},
       {"drpo_plan_sample_ar_t", sizeof(drpo_plan_sample_ar_t)}, {"drpo_plan_shift_t", sizeof(drpo_plan_shift_t)},
       {"drpo_plan_refit_particles_t", sizeof(drpo_plan_refit_particles_t)},
+      {"drpo_rollout_adjoint_t", sizeof(drpo_rollout_adjoint_t)},
   };
   for (const E& e : table)
     if (strcmp(e.n, name) == 0) return (int64_t)e.s;
@@ -180,3 +181,5 @@ DRPO_API int drpo_ens_fit_paths(const drpo_mlp_fwd_t* fwd, const drpo_mlp_bwd_t*
 }
 
 DRPO_API int drpo_rollout_engine(const drpo_rollout_desc_t* d) { return d ? rollout_engine(d) : 0; }
+
+DRPO_API int drpo_rollout_adjoint_ok(int S, int A, int Hm) { return rollout_adjoint_shapes(S, A, Hm); }

@@ -145,4 +145,10 @@ inline int rollout_engine(const drpo_rollout_desc_t* d) {
   return (d->eps_a && d->eps_layout == 0) || d->H > DRPO_ROLLOUT_FUSED_MAX_H ? 1 : 2;
 }
 
+// drpo_rollout_adjoint: the ensemble's trunk [S+A <= 64 -> H -> H] and diff head [H -> H -> S+1 <= 16]
+// (the widths drpo_ens_fit_fb takes: H = 200 | 256, swish)
+inline bool rollout_adjoint_shapes(int S, int A, int Hm) {
+  return S >= 1 && A >= 1 && S + A <= 64 && S + 1 <= 16 && (Hm == 200 || Hm == 256);
+}
+
 }  // namespace drpo

@@ -907,6 +907,241 @@ def lookahead(alg, policy, im, kind, gamma, *, reward_scale=None, alive_bonus=No
 
 
 # ---------------------------------------------------------------------------
+# gradients through imagined rollouts (drpo_rollout_adjoint)
+# ---------------------------------------------------------------------------
+# which implementation rollout_vjp(path=None) takes where the fused kernel admits the shapes: the
+# fused launch, whose p90 is below the per-step path's p10 at 512 and at 4096 rows
+# (profiles/rollout_adjoint: 212 / 228 us against 800 / 845 us)
+VJP_DEFAULT_PATH = 'fused'
+
+
+def rollout_adjoint_ok(alg):
+    """Whether drpo_rollout_adjoint admits the trainer's model (drpo_rollout_adjoint_ok: the
+    condition the entry point itself checks)."""
+    return bool(_lib.lib().drpo_rollout_adjoint_ok(alg.state_dim, alg.action_dim, alg.model_ensemble.hidden_dim))
+
+
+def _vjp_inputs(alg, im, grad_states, grad_rewards):
+    """The stored run and the upstream gradients of rollout_vjp as contiguous float32 device
+    tensors, shapes checked. Returns (states, actions, lengths, g_states or None, g_rewards or
+    None, members)."""
+    if im.rewards.dim() != 2:
+        raise ValueError('rollout_vjp: im must be one run, not stacked runs')
+    B, H = im.rewards.shape
+    S, A = alg.state_dim, alg.action_dim
+    members = _traj_members(alg.model_ensemble, im.members, H)
+    states, actions = im.states.contiguous(), im.actions.contiguous()
+    lengths = im.lengths.contiguous()
+    if tuple(states.shape) != (B, H + 1, S) or tuple(actions.shape) != (B, H, A) or tuple(lengths.shape) != (B,) \
+            or states.dtype != torch.float32 or actions.dtype != torch.float32 or lengths.dtype != torch.int32:
+        raise ValueError('rollout_vjp: im holds states [B, H+1, S], actions [B, H, A] float32 and lengths [B] int32')
+    gs = gr = None
+    if grad_states is not None:
+        if tuple(grad_states.shape) != (B, H + 1, S):
+            raise ValueError(f'grad_states: shape {tuple(grad_states.shape)}, not {(B, H + 1, S)}')
+        gs = grad_states.contiguous().float()
+    if grad_rewards is not None:
+        if tuple(grad_rewards.shape) != (B, H):
+            raise ValueError(f'grad_rewards: shape {tuple(grad_rewards.shape)}, not {(B, H)}')
+        gr = grad_rewards.contiguous().float()
+    _lib.require_device(*[t for t in (states, actions, lengths, gs, gr) if t is not None])
+    return states, actions, lengths, gs, gr, members
+
+
+def _vjp_fused(alg, states, actions, lengths, gs, gr, members, out=None):
+    """drpo_rollout_adjoint: the whole reverse sweep in one launch. out: (grad_actions, grad_start)
+    buffers to write (contiguous float32 [B, H, A] and [B, S]); None: fresh ones."""
+    from ._abi import RolloutAdjoint
+    model = alg.model_ensemble
+    mg, norm = model.group, model.state_normalizer
+    mg.ensure_packed()
+    B, H1, S = states.shape
+    H, A = H1 - 1, actions.shape[2]
+    dev = states.device
+    ga, g0 = (torch.empty(B, H, A, device=dev), torch.empty(B, S, device=dev)) if out is None else out
+    assert ga.is_contiguous() and g0.is_contiguous() and tuple(ga.shape) == (B, H, A) and tuple(g0.shape) == (B, S)
+
+    def fwd(key):
+        return mg.pview(key + '.weight')[0].data_ptr(), mg.view(key + '.bias').data_ptr()
+
+    def tr(key):
+        return mg.pview(key + '.weight', True)[0].data_ptr()
+    d = RolloutAdjoint()
+    d.B, d.H, d.S, d.A, d.Hm, d.E = B, H, S, A, model.hidden_dim, model.ensemble_size
+    (d.mW1, d.mb1), (d.mW2, d.mb2), (d.dW1, d.db1) = fwd('trunk.0'), fwd('trunk.2'), fwd('diff_head.0')
+    d.mT1, d.mT2, d.dT1, d.dT2 = tr('trunk.0'), tr('trunk.2'), tr('diff_head.0'), tr('diff_head.2')
+    d.norm_mean, d.norm_std = norm.mean.data_ptr(), norm.std.data_ptr()
+    marr = (ctypes.c_int * H)(*members)
+    d.members = marr
+    d.states, d.actions, d.lengths = states.data_ptr(), actions.data_ptr(), lengths.data_ptr()
+    d.g_states, d.g_rewards = _lib.ptr(gs), _lib.ptr(gr)
+    d.grad_actions, d.grad_start = ga.data_ptr(), g0.data_ptr()
+    _lib.check(_lib.lib().drpo_rollout_adjoint(ctypes.byref(d), _lib.stream()), 'rollout_adjoint')
+    return ga, g0
+
+
+def _vjp_steps(alg, states, actions, lengths, gs, gr, members):
+    """The same definition composed from the stand-alone launches, H times: the member's trunk and
+    diff head forward with its pre-activation saves (drpo_mlp_forward), then its backward-data
+    from the upstream [lam | g_r] to all S + A input columns (drpo_mlp_backward); the lam update
+    in torch. No host sync: every step runs over all rows, a row's dead steps masked."""
+    from .mlp_desc import UPSTREAM_GOUT, fill_bwd
+    L = _lib.lib()
+    model = alg.model_ensemble
+    eng, norm = model.engine, model.state_normalizer
+    model.group.ensure_packed()
+    B, H1, S = states.shape
+    H, A = H1 - 1, actions.shape[2]
+    dev = states.device
+    Hm = model.hidden_dim
+    if gs is None:
+        gs = torch.zeros(B, H + 1, S, device=dev)
+    if gr is None:
+        gr = torch.zeros(B, H, device=dev)
+    lens = lengths.clamp(0, H).to(torch.int64).unsqueeze(-1)
+    scale = norm.std + 1e-6
+    ga = torch.empty(B, H, A, device=dev)
+    lam = torch.zeros(B, S, device=dev)
+    zero = 0.0      # (a scalar operand of torch.where: no fill launch)
+    dx = torch.empty(B, S + A, device=dev)
+    saves = [torch.empty(B, Hm, device=dev) for _ in range(3)]
+    out = torch.empty(B, S + 1, device=dev)
+    for t in range(H - 1, -1, -1):
+        nets, _ = eng._nets(member=members[t])
+        trunk, diff = nets[0], nets[1]
+        trunk.sz[0], trunk.sz[1], diff.sz[0], diff.sy[1] = saves[0], saves[1], saves[2], out
+        st, at = states[:, t], actions[:, t]
+        f = fill_fwd([trunk, diff], [(st, S), (at, A)], B, trunk=True, norm=(norm.mean, norm.std))
+        f.ld[0], f.ld[1] = (H + 1) * S, H * A     # rows of the trajectory-major tensors
+        _lib.check(L.drpo_mlp_forward(ctypes.byref(f), _lib.stream()), 'mlp_forward')
+        active = t < lens
+        used = torch.where(t == lens - 1, gs[:, t + 1], lam)
+        gout = torch.where(active, torch.cat([used, gr[:, t:t + 1]], dim=1), zero)
+        b = fill_bwd([trunk, diff], [None, gout], B, trunk=True, dx={0: (dx, 0, S + A, False)},
+                     upstream=UPSTREAM_GOUT)
+        _lib.check(L.drpo_mlp_backward(ctypes.byref(b), _lib.stream()), 'mlp_backward')
+        ga[:, t] = torch.where(active, dx[:, S:], zero)
+        lam = torch.where(active, (gs[:, t] + used) + dx[:, :S] / scale, lam)
+    g0 = torch.where(lens == 0, gs[:, 0], lam)
+    return ga, g0
+
+
+def rollout_vjp(alg, im, grad_states=None, grad_rewards=None, *, path=None):
+    """The vector-Jacobian product of the imagined rollout ``im`` (one run of the deterministic
+    model step: imagine(model_noise=False)): upstream gradients grad_states [B, H+1, S] and
+    grad_rewards [B, H] (None: zeros) backed along the stored trajectories to (grad_actions
+    [B, H, A], grad_start [B, S]); drpo_rollout_adjoint has the definition. Lengths, dones and
+    constraint checks are constants; nothing is drawn.
+    path: 'fused' the one-launch kernel (a ValueError where drpo_rollout_adjoint_ok refuses the
+    model's shapes), 'steps' the same definition from H forward + backward launches, None
+    VJP_DEFAULT_PATH where the fused kernel admits the shapes and 'steps' elsewhere."""
+    if path not in (None, 'fused', 'steps'):
+        raise ValueError(f"path: {path!r} (None, 'fused' or 'steps')")
+    args = _vjp_inputs(alg, im, grad_states, grad_rewards)
+    ok = rollout_adjoint_ok(alg)
+    if path == 'fused' and not ok:
+        raise ValueError(f"path='fused': drpo_rollout_adjoint does not take S={alg.state_dim}, A={alg.action_dim}, "
+                         f"hidden width {alg.model_ensemble.hidden_dim} (path='steps' does)")
+    if path is None:
+        path = VJP_DEFAULT_PATH if ok else 'steps'
+    return (_vjp_fused if path == 'fused' else _vjp_steps)(alg, *args)
+
+
+class ValueGradient:
+    """What SMBPO.value_gradient found for B rows under H given actions, all from one run:
+
+      grad_actions [B, H, A]     d value / d actions (zero at and beyond a row's length)
+      grad_states [B, S]         d value / d start state
+      value [B]                  the run's value_lookahead[:, H]: sum_{t<len} discount^t r'_t, closed
+                                 with discount^len min Q at the state a row ends in unless it terminated
+      imagined                   the ImaginedRollout of the run (with its lookahead group)
+      critic_index [B] int64     the critic whose Q was the minimum at the row's last state (the
+                                 one differentiated; a constant of the gradient)"""
+
+    def __init__(self, grad_actions, grad_states, value, imagined, critic_index):
+        self.grad_actions, self.grad_states, self.value = grad_actions, grad_states, value
+        self.imagined, self.critic_index = imagined, critic_index
+
+
+def _saved_net(group, prefix, spec, rows):
+    """_net with the saves a backward reads: every hidden layer's y and z, and the output."""
+    net = _net(group, prefix, spec, rows)
+    dev = group.data.device
+    for l, lay in enumerate(net.layers[:-1]):
+        net.sy[l] = torch.empty(rows, lay.dout, device=dev)
+        net.sz[l] = torch.empty(rows, lay.dout, device=dev)
+    return net
+
+
+def _backward_dx(nets, gouts, rows, din):
+    """One drpo_mlp_backward of up to three nets on one input (DRPO_UPSTREAM_GOUT): each net's
+    gradient with respect to all ``din`` input columns, [rows, din] per net."""
+    from .mlp_desc import UPSTREAM_GOUT, fill_bwd
+    dxs = [torch.empty(rows, din, device=g.device) for g in gouts]
+    b = fill_bwd(nets, gouts, rows, dx={j: (dx, 0, din, False) for j, dx in enumerate(dxs)}, upstream=UPSTREAM_GOUT)
+    _lib.check(_lib.lib().drpo_mlp_backward(ctypes.byref(b), _lib.stream()), 'mlp_backward')
+    return dxs
+
+
+def terminal_value_gradient(alg, policy, last, weight):
+    """weight[i] * d/ds min_k Q_k(s, tanh(mu(s))) at the rows s = last[i] ([n, S]; mu: ``policy``'s
+    mean, Q_k: solver.critic's nets), the minimising critic selected per row as a constant (ties:
+    the lower k). The stand-alone forwards with their saves, then drpo_mlp_backward of the
+    critics to their state and action columns, (1 - a^2) in torch, and the policy net's backward
+    with that on its mu columns and zeros on its log-std columns. Returns (gradient [n, S], the
+    selected critic [n] int64). A zero weight gives an exactly zero row."""
+    L = _lib.lib()
+    critic = alg.solver.critic
+    last, weight = last.contiguous(), weight.contiguous()
+    _lib.require_device(policy.group.data, critic.group.data, last, weight)
+    n, S = last.shape
+    A = policy.action_dim
+    pnet = _saved_net(policy.group, 'net.', policy.spec, n)
+    _mlp([pnet], [(last, S)], n)
+    a = torch.empty(n, A, device=last.device)
+    _lib.check(L.drpo_policy_head(_lib.ptr(pnet.sy[-1]), n, A, 2, None, 0, 0, 0, None, None, None, None, _lib.ptr(a),
+                                  _lib.stream()), 'policy_head')
+    nets = [_saved_net(critic.group, f'{critic.prefix}qs.{i}.', critic.spec, n) for i in range(critic.n_critics)]
+    for k in range(0, len(nets), 3):
+        _mlp(nets[k:k + 3], [(last, S), (a, A)], n)
+    index = torch.stack([net.sy[-1].reshape(n) for net in nets]).argmin(dim=0)
+    zero = 0.0      # (a scalar operand of torch.where: no fill launch)
+    d = None
+    for k in range(0, len(nets), 3):
+        chunk = nets[k:k + 3]
+        gouts = [torch.where(index == k + j, weight, zero).reshape(n, 1) for j in range(len(chunk))]
+        for dx in _backward_dx(chunk, gouts, n, S + A):
+            d = dx if d is None else d + dx
+    g_mu = d[:, S:] * (1.0 - a * a)
+    (d_pi,) = _backward_dx([pnet], [torch.cat([g_mu, torch.zeros_like(g_mu)], dim=1)], n, S)
+    return d[:, :S] + d_pi, index
+
+
+def value_gradient(alg, policy, im, gamma):
+    """The gradient of ``im``'s value_lookahead[:, H] (one deterministic run under H given actions,
+    with its lookahead group) with respect to the actions and the start states: the upstream
+    g_rewards[i][t] = gamma^t * reward_scale and, for rows that did not terminate, g_states[i][len]
+    = gamma^len * terminal_value_gradient, backed through the run by rollout_vjp. Returns a
+    ValueGradient. No host sync."""
+    B, H = im.rewards.shape
+    S = alg.state_dim
+    dev = im.rewards.device
+    lens = im.lengths.clamp(0, H).to(torch.int64)
+    w = np.power(np.float64(gamma), np.arange(H + 1, dtype=np.float64))
+    scale = float(alg.reward_scale) if float(alg.reward_scale) != 0 else 1.0    # (drpo_rollout_lookahead's r')
+    zero = 0.0
+    gr = torch.where(im.mask, torch.as_tensor((w[:H] * scale).astype(np.float32)).to(dev).expand(B, H), zero)
+    alive = ~im.terminated.view(torch.bool)
+    weight = torch.where(alive, torch.as_tensor(w.astype(np.float32)).to(dev)[lens], zero)
+    at = lens.reshape(B, 1, 1).expand(B, 1, S)
+    last = torch.gather(im.states, 1, at).reshape(B, S)
+    g_last, index = terminal_value_gradient(alg, policy, last, weight)
+    gs = torch.zeros(B, H + 1, S, device=dev).scatter_(1, at, g_last.unsqueeze(1))
+    ga, g0 = rollout_vjp(alg, im, gs, gr)
+    return ValueGradient(ga, g0, im.value_lookahead[:, H], im, index)
+
+
+# ---------------------------------------------------------------------------
 # planning on the model (SMBPO.plan): the two launches of an iteration
 # ---------------------------------------------------------------------------
 # the limits and the draw site of csrc/plan.hip (literals so that this module imports before the
@@ -954,7 +1189,14 @@ class PlanResult:
       particles                  the member index of each particle, G ints
       risk, cert_risk            as given: 'mean', 'worst' or ('cvar', alpha); 'max' or 'mean'
       member_scores, member_certificates [G, P, N]   each member's score and certificate
-      score_spread [P, N]        the members' population std of a candidate's score"""
+      score_spread [P, N]        the members' population std of a candidate's score
+
+    Under plan(refine=R) ``actions`` / ``action``, ``score``, ``certificate`` and ``feasible`` are the
+    refined incumbent's (the other per-candidate fields stay the last sampling iteration's). Three
+    more, None otherwise (REFINE_FIELDS):
+      refine_score [R + 1, P]    the incumbent's score before and after each round
+      refine_accepted [R, P] int32   the trial j a round took (step refine_step * 2^-j), -1: none
+      refine_gradient [P, K, A]  the last round's gradient of the incumbent's value"""
     FIELDS =('actions', 'action', 'score', 'certificate', 'feasible', 'n_feasible', 'mean', 'std', 'history_score',
               'history_certificate', 'history_feasible', 'candidates', 'scores', 'certificates', 'ranks', 'imagined',
               'threshold', 'lookahead_kind')
@@ -962,16 +1204,20 @@ class PlanResult:
 
     MPC_FIELDS = ('noise_beta', 'warm_started', 'shift')
     PARTICLE_FIELDS = ('particles', 'risk', 'cert_risk', 'member_scores', 'member_certificates', 'score_spread')
+    REFINE_FIELDS = ('refine_score', 'refine_accepted', 'refine_gradient')
 
     def __init__(self, executed_actions=None, safe_action=None, interventions=None, filter_threshold=None,
                  noise_beta=None, warm_started=None, shift=None, particles=None, risk=None, cert_risk=None,
-                 member_scores=None, member_certificates=None, score_spread=None, **fields):
+                 member_scores=None, member_certificates=None, score_spread=None, refine_score=None,
+                 refine_accepted=None, refine_gradient=None, **fields):
         assert set(fields) == set(self.FIELDS), sorted(set(fields) ^ set(self.FIELDS))
         self.__dict__.update(fields, executed_actions=executed_actions, safe_action=safe_action,
                              interventions=interventions, filter_threshold=filter_threshold,
                              noise_beta=noise_beta, warm_started=warm_started, shift=shift,
                              particles=particles, risk=risk, cert_risk=cert_risk, member_scores=member_scores,
-                             member_certificates=member_certificates, score_spread=score_spread)
+                             member_certificates=member_certificates, score_spread=score_spread,
+                             refine_score=refine_score, refine_accepted=refine_accepted,
+                             refine_gradient=refine_gradient)
 
 
 def plan_sample(mean, std, incumbent, candidates, seed, ctr, lo=-1.0, hi=1.0, corr=0.0):

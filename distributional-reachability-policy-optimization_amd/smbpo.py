@@ -471,13 +471,78 @@ class SMBPO(Configurable, Module):
         # max_disagreement: >= 0, and 0 beyond a row's length
         im.set_group('uncertainty', max_disagreement=vals['disagreement'].max(dim=-1).values, **vals)
 
+    def imagine_vjp(self, im, grad_states=None, grad_rewards=None):
+        """The vector-Jacobian product of an imagined rollout: upstream gradients of its states
+        (grad_states [B, H+1, S]) and rewards (grad_rewards [B, H]; None: zeros) backed along the
+        stored trajectories to (grad_actions [B, H, A], grad_start [B, S]), for sensitivity
+        analysis and objectives of one's own. ``im`` is one run (not stacked) of the
+        deterministic model step, imagine(model_noise=False), whose ``members`` are H ints; the
+        Jacobians are the members' at the stored (states, actions), so lengths, dones and
+        constraint checks are constants and a row's steps at and beyond its length get zero.
+        drpo_rollout_adjoint has the definition; one launch where its kernel takes the model's
+        shapes, the per-step launches elsewhere (ops.rollout_vjp(path=) asks for either). Draws
+        nothing and changes nothing of the trainer."""
+        from . import ops
+        return ops.rollout_vjp(self, im, grad_states, grad_rewards)
+
+    GRADIENT_SALT = 0x6AD1
+
+    def value_gradient(self, states, actions, horizon=None, members=0, discount=None, policy=None, *, noise=None,
+                       model_noise=False, particles=None, shield=None, proposals=None, halt=None):
+        """Which way should this action sequence move: the gradient of a rollout's value with
+        respect to its actions and its start state (an ops.ValueGradient: grad_actions [B, H, A],
+        grad_states [B, S], value [B], imagined, critic_index). The value is value_lookahead[:, H]
+        of imagine(states, actions=actions, lookahead=True, deterministic=True,
+        model_noise=False): the discounted rewards in the critics' units, closed with min Q at the
+        state a row ends in, under the policy's mean action there, unless the row terminated.
+        Value and gradients come from one run. The minimising critic, the lengths, dones and
+        constraint checks are constants of the gradient; a terminated row gets no terminal term.
+
+        actions    [B, H, A]: every step given (K == horizon; [B, A] at horizon 1).
+        members    an int or H ints: a fixed model (default member 0).
+        discount, policy   as imagine's.
+        noise      default a stream private to value_gradient (the run draws nothing, but takes
+                   one counter of the object it is given).
+        The gradient is that of the deterministic run under given actions, so model_noise=True,
+        particles=, shield=, proposals= and halt= are refused (ValueError), as are members=None /
+        'each', fewer given steps than the horizon and a recorded tape. Nothing of the training
+        state changes: not the trainer's stream, the buffers or steps_sampled."""
+        from . import ops
+        from .rng import _mix64
+        for name, v in (('particles', particles), ('shield', shield), ('proposals', proposals), ('halt', halt)):
+            if v is not None and v is not False:
+                raise ValueError(f'{name}: value_gradient differentiates the deterministic run under given actions; '
+                                 f'{name}= is not part of it')
+        if model_noise:
+            raise ValueError('model_noise: value_gradient is the gradient of the deterministic model step')
+        if members is None or isinstance(members, str):
+            raise ValueError(f'members: {members!r} (an int or one int per step: the gradient needs a fixed model)')
+        if noise is not None and noise.parity:
+            raise ValueError('noise: a recorded tape fixes the draws of a rollout; value_gradient draws nothing')
+        H = self.horizon if horizon is None else int(horizon)
+        actions = torch.as_tensor(actions, dtype=torch.float32)
+        if actions.dim() == 2:
+            actions = actions.unsqueeze(1)
+        if actions.dim() != 3 or actions.shape[1] != H or actions.shape[2] != self.action_dim:
+            raise ValueError(f'actions: shape {tuple(actions.shape)}; value_gradient needs every step given, '
+                             f'[B, {H}, {self.action_dim}] for horizon {H}')
+        policy = self.actor if policy is None else policy
+        if noise is None:
+            if self.__dict__.get('_gradient_noise') is None:
+                self._gradient_noise = DeviceNoise(_mix64(self.noise.base_seed ^ self.GRADIENT_SALT), rank=0, world=1)
+            noise = self._gradient_noise
+        gamma = float(self.solver.discount if discount is None else discount)
+        im = self.imagine(states, policy, H, members=members, deterministic=True, model_noise=False, discount=gamma,
+                          noise=noise, actions=actions, lookahead=True)
+        return ops.value_gradient(self, policy, im, gamma)
+
     PLAN_SALT = 0x91A7
 
     def plan(self, states, horizon=None, *, candidates=64, iterations=4, steps=None, elites=None,
              temperature=float('inf'), momentum=0.0, init=None, init_std=0.5, min_std=0.05, threshold=None,
              lookahead=True, policy=None, members=None, model_noise=False, discount=None, noise=None,
              safety_filter=None, warm_start=None, shift=1, reset=None, tail=None, warm_std=None, noise_beta=0.0,
-             particles=None, risk='mean', cert_risk='max'):
+             particles=None, risk='mean', cert_risk='max', refine=0, refine_trials=8, refine_step=0.5):
         """The best of sampled action sequences from each of the P ``states``, by the model and the
         two critics: an MPPI / CEM planner whose score is imagine(actions=, lookahead=)'s
         value_lookahead[:, H] and whose constraint is its certificate_lookahead[:, H] (the
@@ -570,6 +635,26 @@ class SMBPO(Configurable, Module):
                      best key is never below warm_start's: candidate 0 is its best row, run
                      again from the same state. With shift >= 1 nothing of the kind holds: the
                      shifted sequence is scored from another state.
+        refine       R >= 0 rounds of gradient refinement of the incumbent after the last sampling
+                     iteration (0: none, the planner as it is, with the same launches). A round
+                     takes the gradient of every state's incumbent (one value_gradient of P rows),
+                     builds refine_trials = L sequences clamp(a + refine_step * 2^-j * g /
+                     max|g|, -1, 1), j = 0..L-1 (a backtracking line along the gradient, the
+                     largest step refine_step in action units), imagines the P * (L + 1) rows with
+                     the incumbent as candidate 0, closes them with the terminal critics and ranks
+                     them with drpo_plan_refit: the planner's own order, feasibility rule and
+                     tie-break. The best row becomes the incumbent, so its key never decreases;
+                     ``mean`` and ``std`` are not refit. A state without a feasible incumbent, or
+                     whose gradient is zero or not finite, is carried through unchanged (its
+                     trials repeat the incumbent). ``actions``, ``score``, ``certificate`` and
+                     ``feasible`` of the result are the refined incumbent's; ``candidates``,
+                     ``scores``, ``ranks``, ``n_feasible`` and ``imagined`` stay the last sampling
+                     iteration's. The result carries ``refine_score`` [R + 1, P] (the incumbent's
+                     score before and after each round), ``refine_accepted`` [R, P] (the j taken,
+                     -1: the incumbent stayed) and ``refine_gradient`` [P, K, A] (the last
+                     gradient). Needs a fixed deterministic model and every step planned: not
+                     with steps < horizon, members=None, model_noise=True, particles= or
+                     safety_filter= (ValueError). No host sync inside the rounds.
         Not with a recorded tape; NotImplementedError for an env without device constraint
         functions, as imagine. SMBPO.mpc wraps the warm start in a controller. halt= inside the
         planner is not built."""
@@ -630,7 +715,33 @@ class SMBPO(Configurable, Module):
                                  min_std=min_std, **refit)
             mean, std, incumbent = fit['mean'], fit['std'], fit['best_actions']
             history.append((fit['best_score'], fit['best_cert'], fit['best_feasible']))
+        best = {k: fit[k] for k in ('best_score', 'best_cert', 'best_feasible')}
         filtered = {}
+        if q['refine']:
+            # gradient refinement of the incumbent (the refusals left: no particles, no filter, K == H)
+            L, eta = q['refine_trials'], float(q['refine_step'])
+            sizes = torch.as_tensor([eta * 2.0 ** -j for j in range(L)], dtype=torch.float32).to(dev).view(1, L, 1, 1)
+            wide = states.repeat_interleave(L + 1, dim=0)
+            scores, accepted = [best['best_score']], []
+            for _ in range(q['refine']):
+                vg = self.value_gradient(states, incumbent, H, members, gamma, policy, noise=noise)
+                g = vg.grad_actions
+                gmax = g.abs().amax(dim=(1, 2))
+                ok = best['best_feasible'] & torch.isfinite(gmax) & (gmax > 0)
+                unit = (g / gmax.view(P, 1, 1)).unsqueeze(1)
+                trials = (incumbent.unsqueeze(1) + sizes * unit).clamp(-1.0, 1.0)
+                trials = torch.where(ok.view(P, 1, 1, 1), trials, incumbent.unsqueeze(1))
+                rcand = torch.cat([incumbent.unsqueeze(1), trials], dim=1).reshape(P * (L + 1), K, A)
+                rim = self.imagine(wide, policy, H, actions=rcand, **run)
+                tq, tqc = ops._terminal_critics(self, policy, rim, look)
+                rfit = ops.plan_refit(self, rim, tq, tqc, rcand, mean, std, gamma, candidates=L + 1,
+                                      threshold=threshold, elites=1, temperature=temperature, momentum=0.0,
+                                      min_std=min_std)
+                incumbent = rfit['best_actions']
+                best = {k: rfit[k] for k in best}
+                scores.append(best['best_score'])
+                accepted.append(rfit['best'] - 1)
+            filtered.update(refine_score=torch.stack(scores), refine_accepted=torch.stack(accepted), refine_gradient=g)
         if filt is not None:
             # the best row's filtered trajectory, gathered on the device (row p * N + best[p])
             rows = torch.arange(P, device=dev, dtype=torch.int64) * N + fit['best'].to(torch.int64)
@@ -645,8 +756,8 @@ class SMBPO(Configurable, Module):
         return ops.PlanResult(
             **filtered, noise_beta=float(noise_beta), warm_started=warm_start is not None,
             shift=None if warm_start is None else shift,
-            actions=incumbent, action=incumbent[:, 0], score=fit['best_score'], certificate=fit['best_cert'],
-            feasible=fit['best_feasible'], n_feasible=fit['n_feasible'], mean=mean, std=std,
+            actions=incumbent, action=incumbent[:, 0], score=best['best_score'], certificate=best['best_cert'],
+            feasible=best['best_feasible'], n_feasible=fit['n_feasible'], mean=mean, std=std,
             history_score=torch.stack([h[0] for h in history]),
             history_certificate=torch.stack([h[1] for h in history]),
             history_feasible=torch.stack([h[2] for h in history]),
@@ -656,7 +767,7 @@ class SMBPO(Configurable, Module):
     def _plan_checks(self, states, horizon, *, candidates, iterations, steps, elites, temperature, momentum, init,
                      init_std, min_std, threshold, lookahead, policy, members, model_noise, discount, noise,
                      safety_filter, warm_start, shift, reset, tail, warm_std, noise_beta, particles, risk, cert_risk,
-                     controller=False):
+                     refine=0, refine_trials=8, refine_step=0.5, controller=False):
         """Every refusal of plan's arguments, before any device work; returns what they resolve
         to. controller=True (SMBPO.mpc, which has no states yet): shift, tail and warm_std are
         checked as far as they can be without P and without a warm_start."""
@@ -740,6 +851,22 @@ class SMBPO(Configurable, Module):
             raise ValueError(f'shift: {shift!r} (an int, 0..steps {K})')
         if not (warm_std is None or is_num(warm_std) and warm_std >= 0):
             raise ValueError(f'warm_std: {warm_std!r} (None or a number >= 0)')
+        if not (is_int(refine) and refine >= 0):
+            raise ValueError(f'refine: {refine!r} (an int >= 0: the rounds of gradient refinement)')
+        if not (is_int(refine_trials) and 1 <= refine_trials < ops.PLAN_MAX_CANDIDATES):
+            raise ValueError(f'refine_trials: {refine_trials!r} (an int, 1..{ops.PLAN_MAX_CANDIDATES - 1})')
+        if not (is_num(refine_step) and 0 < refine_step < float('inf')):
+            raise ValueError(f'refine_step: {refine_step!r} (finite, > 0)')
+        if refine:
+            # the gradient is that of one deterministic run under K = H given actions (value_gradient)
+            for name, v, bad in (('steps', K, K != H), ('particles', particles, parts is not None),
+                                 ('members', members, members is None),
+                                 ('model_noise', model_noise, bool(model_noise)),
+                                 ('safety_filter', safety_filter, filt is not None)):
+                if bad:
+                    raise ValueError(f'refine with {name}={v!r}: gradient refinement needs every step planned (steps '
+                                     '== horizon) under a fixed deterministic model (members an int or H ints, '
+                                     'model_noise=False) without particles= or safety_filter=')
         A = self.action_dim
         if controller:
             # mpc: no states, no P and no warm start yet (act() makes them)
@@ -779,7 +906,8 @@ class SMBPO(Configurable, Module):
             if tail is not None and not (is_array(tail) and tuple(tail.shape) == (P, A)):
                 raise ValueError(f'tail: {tail!r} (None or a [{P}, {A}] tensor)')
         return dict(H=H, N=N, K=K, P=P, A=A, states=states, init=init, elites=elites, threshold=threshold, look=look,
-                    filt=filt, parts=parts, score_tail=score_tail, cert_mode=0 if cert_risk == 'max' else 1)
+                    filt=filt, parts=parts, score_tail=score_tail, cert_mode=0 if cert_risk == 'max' else 1,
+                    refine=refine, refine_trials=refine_trials, refine_step=refine_step)
 
     def mpc(self, *, fallback='safe', shift=1, warm_std=None, **plan_kwargs):
         """A receding-horizon controller on plan (an ops.PlanController): ``act(states)`` plans

@@ -416,6 +416,58 @@ typedef struct {
 
 int drpo_rollout_lookahead(const drpo_rollout_lookahead_t* d /* host */, drpo_stream_t stream);
 
+/* The adjoint of the imagined rollout: the reverse sweep along stored trajectories of the
+ * deterministic model step, which the reference (src/smbpo.py:229-249, rolled forward only) has
+ * no counterpart of. That step is s_{t+1} = s_t + diff_m(x_t)[:S], r_t = diff_m(x_t)[S] with
+ * x_t = [(s_t - mean) / (std + 1e-6), a_t] and diff_m member m's trunk -> diff-head output
+ * (S+1 columns): what a drpo_rollout_trajectories_given run without model noise executes
+ * (_forward1's means, src/dynamics.py:112-122). The call backs upstream gradients of the states
+ * and rewards of such a run through it, to the actions and the start state.
+ * For row i, with len = lengths[i] clamped to 0..H, m_t = members[t] and J_t the Jacobian of
+ * member m_t's diff-head output with respect to x, taken at the stored (states[i][t], actions[i][t]):
+ *   lam = g_states[i][len]                              [S]; entries beyond len are never read
+ *   for t = len-1 .. 0:
+ *       dx = J_t^T [lam, g_rewards[i][t]]               [S+A]
+ *       grad_actions[i][t] = dx[S:]
+ *       lam = g_states[i][t] + lam + dx[:S] / (std + 1e-6)
+ *   grad_start[i] = lam;   grad_actions[i][t] = 0 for t >= len
+ * g_states and g_rewards are the upstream gradients; either may be NULL, meaning zeros (and
+ * computing what explicit zeros compute). Dones, lengths and constraint checks are constants of
+ * the sweep; the log-var head is not read. The sum is formed left to right as written, in float32;
+ * the products are exact-float32 MFMA chains. One launch: a workgroup keeps a 16-row tile for the
+ * whole sweep, each step's forward (trunk, the diff head's hidden layer) and four backward-data
+ * products on chip; only grad_actions and, at the end, grad_start leave it. Every element of both
+ * outputs is written; the call makes no draw and has no workspace the caller must zero.
+ * DRPO_EINVAL before any launch: a null descriptor or required pointer, H outside
+ * 1..DRPO_ROLLOUT_FUSED_MAX_H, S < 1, A < 1, S + A > 64, S + 1 > 16, a hidden width other than
+ * 200 | 256 (drpo_rollout_adjoint_ok: the per-step launches drpo_mlp_forward +
+ * drpo_mlp_backward compose the same definition for the others), E < 1, a member index outside
+ * 0..E-1, B < 0, or B beyond one grid (a launch takes fewer than 2^32 threads: 2^23 - 1 tiles of
+ * 16 rows, 512 threads each). B == 0: DRPO_OK without a launch. */
+typedef struct {
+  int64_t B;                /* rows */
+  int H, S, A, Hm, E;       /* horizon, state and action dims, hidden width, ensemble members */
+  /* the ensemble's trunk and diff head as drpo_rollout_desc_t names them: packed forward mirrors
+     and biases of member 0 (member stride drpo_packed_size / the layer's outputs), swish hidden
+     layers; the output layer's forward is not run (it is linear and s_{t+1} is stored) */
+  const float *mW1, *mb1, *mW2, *mb2, *dW1, *db1;
+  /* the packed TRANSPOSED mirrors of the four layers (drpo_mlp_bwd_layer_t.W), member 0 */
+  const float *mT1, *mT2, *dT1, *dT2;
+  const float *norm_mean, *norm_std;   /* [S] */
+  const int* members;       /* host [H] */
+  /* the stored run, device, not written while the call runs */
+  const float* states;      /* [B][H+1][S] */
+  const float* actions;     /* [B][H][A] */
+  const int32_t* lengths;   /* [B]; clamped to 0..H as read */
+  const float* g_states;    /* [B][H+1][S] or NULL */
+  const float* g_rewards;   /* [B][H] or NULL */
+  /* outputs, device */
+  float* grad_actions;      /* [B][H][A] */
+  float* grad_start;        /* [B][S] */
+} drpo_rollout_adjoint_t;
+
+int drpo_rollout_adjoint(const drpo_rollout_adjoint_t* d /* host */, drpo_stream_t stream);
+
 /* Sampling-based planning on the learned model (MPPI / CEM over action sequences, for P start
  * states at once): the two launches around one drpo_rollout_trajectories_given run of
  * B = P * N rows and the terminal critic forwards. The reference has no counterpart on the
@@ -1212,6 +1264,9 @@ int drpo_mlp_fb_ok(int cols0, const drpo_mlp_net_t* trunk, const drpo_mlp_net_t*
 int drpo_ens_fit_paths(const drpo_mlp_fwd_t* fwd, const drpo_mlp_bwd_t* bwd, const drpo_ens_upstream_t* up);
 /* the engine (1 or 2) drpo_rollout runs for this descriptor (d->engine when it is not 0) */
 int drpo_rollout_engine(const drpo_rollout_desc_t* d);
+/* drpo_rollout_adjoint admits these dimensions: 1 <= S, S + 1 <= 16, 1 <= A, S + A <= 64 and a
+ * hidden width of 200 | 256 */
+int drpo_rollout_adjoint_ok(int S, int A, int Hm);
 
 #ifdef __cplusplus
 }
